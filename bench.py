@@ -6,11 +6,18 @@ A "step" is one Solver::tick = `timeSubsteps` (1) substep of BASELINE configs[1]
 particles, 649 156 distance + 539 334 tet-strain constraints), PBD, 20 iterations, node-node collisions off, synthetic
 perturbed rest state already resident in HBM.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W --full [--exhaustive]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one body per GPU)
 
 Rank 0 prints ONE JSON line.  `value` is whole-job substeps/s (N independent bodies, weak scaling; the only collective is
-the timing barrier / max-reduce).  How every other number is obtained:
+the timing barrier / max-reduce); `ms_per_step` is the wall time of one timed step.  A plain run does only that: it builds
+the scene, runs W warm-up and K timed steps and prints the line (`roofline` is null).  `--dump-outputs DIR` writes what the
+last timed step left for a caller - rank 0's node positions and velocities - to DIR/positions.npy and DIR/velocities.npy
+(float32; a fixed, seeded sample of rows if they exceed 64 MB), so that two builds can be compared output for output.
+
+Everything else is measured only under `--full` (which also writes bench_full.json); `--exhaustive` adds the sections that
+take minutes and lifts the time budget.  How every other number is obtained:
 
 * `roofline` (and the `roofline` of every `other_configs` entry): the dominant kernel class is timed IN SITU - whole
   substeps are launched eagerly and every launch of the class is bracketed by two HIP events on the solver's stream
@@ -977,9 +984,9 @@ def _pick(d, keys):
     return {k: _r(d[k]) for k in keys if d and k in d}
 
 
-def compact_line(full):
+def compact_line(full, full_report=True):
     """The ONE stdout line the driver parses: the contract keys, `roofline`, `cpu_baseline` and a dozen scalars.  Everything
-    else (prose, per-frame arrays, per-class latencies, order deviation) lives in bench_full.json."""
+    else (prose, per-frame arrays, per-class latencies, order deviation) lives in bench_full.json (full_report: it was written)."""
     c = {k: _r(full[k], 6) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                      "scaling", "vs_baseline", "dtype", "data") if k in full}
     c["config"] = dict(full["config"])
@@ -1050,7 +1057,8 @@ def compact_line(full):
         c["errors"] = len(full["errors"])
     if full.get("skipped"):
         c["skipped"] = len(full["skipped"])
-    c["full_report"] = "bench_full.json"
+    if full_report:
+        c["full_report"] = "bench_full.json"
     line = json.dumps(c, allow_nan=False, separators=(",", ":"))
     if len(line) > COMPACT_LIMIT:  # never let extras cost the record: drop the scalars, then the sample prose
         for k in list(s):
@@ -1091,6 +1099,24 @@ def write_full(full):
     print(text, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT = 64 << 20  # bytes over all arrays of --dump-outputs
+
+
+def dump_outputs(solver, out_dir):
+    """--dump-outputs: what the timed path leaves for a caller after its last step (the node state a Pies host reads back),
+    as float32 .npy files.  Above DUMP_LIMIT every array keeps the same fixed, seeded sample of rows (in index order)."""
+    arrays = {"positions": solver.positions, "velocities": solver.velocities}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        n = len(arrays["positions"])
+        rows = np.sort(np.random.default_rng(0).choice(n, size=n * DUMP_LIMIT // total, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log("outputs written to %s (%s)" % (out_dir, ", ".join("%s %s" % (k, a.shape) for k, a in arrays.items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1098,21 +1124,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--dims", type=int, nargs=3, default=list(scenes.L100K))
     ap.add_argument("--schedule", choices=["layered", "coloured", "exact"], default="layered")
-    ap.add_argument("--quick", action="store_true", help="headline + roofline + a one-tick CPU baseline only")
-    ap.add_argument("--full", action="store_true", help="also: order deviation, unstructured beam, config 5 share, contact scene, 1M "
-                    "particles, per-class latencies, CPU baselines of configs 3 and 4, the reference-order default tick (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the node positions and velocities of the last timed step to "
+                    "DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline, CPU baselines, the other schedules, "
+                    "tick-inclusive rates, configs 3-5, the 1M-particle and unstructured measurements; writes bench_full.json")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline + roofline + a one-tick CPU baseline only")
+    ap.add_argument("--exhaustive", action="store_true", help="--full, and also: order deviation, contact scene, per-class latencies, "
+                    "CPU baselines of configs 3 and 4, the reference-order default tick; no time budget (minutes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="skip the other schedules' throughput")
     ap.add_argument("--no-roofline", action="store_true", help="skip the in-situ timing pass (roofline = null)")
     ap.add_argument("--no-extras", action="store_true", help="skip BASELINE configs 3 and 4")
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds of CPU work per baseline sample")
     ap.add_argument("--config5-dims", type=int, nargs=3, default=list(scenes.L250K), help="the large body of the config-5 region (tests shrink it)")
-    ap.add_argument("--time-budget", type=float, default=80.0, help="seconds after which the default run starts no further optional section "
-                    "(they are named in `skipped`; --full ignores it)")
+    ap.add_argument("--time-budget", type=float, default=80.0, help="seconds after which a --full run starts no further optional section "
+                    "(they are named in `skipped`; --exhaustive ignores it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.exhaustive:
+        args.full = True
     if args.quick:
         args.no_exact = args.no_extras = True
-        args.full = False
+        args.exhaustive = False
         args.cpu_budget = min(args.cpu_budget, 1.0)
 
     rank, local_rank, world = dist_env()
@@ -1152,6 +1186,8 @@ def main():
     elapsed = timed_ticks(g, args.steps, args.warmup, barrier)
     elapsed, total_substeps = aggregate(elapsed, args.steps * substeps_per_tick, dist)
     assert np.isfinite(g.positions).all() and not g.failed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(g, args.dump_outputs)
 
     result = None
     if rank == 0:
@@ -1178,10 +1214,10 @@ def main():
                                    "every frame's positions delivered to the host (asynchronous export), pies_tick = the synchronous "
                                    "Pies::Solver::tick"},
             "projections_per_sec": value * proj,
-            "roofline": None if args.no_roofline else roofline(g, dom, per_unit, whole_graph=lc.get(dom, 0) == sum(lc.values()),
-                                                               note="algorithmic bytes = the projections and per-node steps "
-                                                               "a launch executes (160 B per tet, 52 per distance, 44 per position constraint, 136 per "
-                                                               "bend, 48 / 20 / 40 per node for predict / floor / velocity), tallied by the library"),
+            "roofline": None if args.no_roofline or not args.full else roofline(
+                g, dom, per_unit, whole_graph=lc.get(dom, 0) == sum(lc.values()),
+                note="algorithmic bytes = the projections and per-node steps a launch executes (160 B per tet, 52 per distance, 44 per "
+                     "position constraint, 136 per bend, 48 / 20 / 40 per node for predict / floor / velocity), tallied by the library"),
             "errors": [],
         }
         if result["roofline"]:
@@ -1200,13 +1236,13 @@ def main():
 
     # BASELINE configs[4] on every rank (N > 1: the second timed region; N = 1 runs the same scene as a section below)
     c5 = None
-    if world > 1:
+    if world > 1 and args.full:
         log("config 5 region (one contact scene per rank)")
         c5 = run_config5_rank(device_index, tuple(args.config5_dims), barrier, dist)
     if rank == 0 and c5 is not None:
         result["config5_all_ranks"] = c5
 
-    if rank == 0:
+    if rank == 0 and args.full:
         def section(name, fn, *a, **kw):
             """An extra must never cost the record: a failing section is logged and named in `errors`."""
             log(name)
@@ -1234,7 +1270,7 @@ def main():
                        "launches_per_substep": sum(c.launch_counts().values()), "steps": steps,
                        "roofline": roofline(c, "tet", BYTES["tet"], workload="none"),
                        "note": "schedule COLOURED: one launch per colour class (24 tet + 9 distance colours per iteration)"}
-                if args.full:
+                if args.exhaustive:
                     out["isolated_replay_latencies"] = replay_latencies(c)
                 c.close()
                 return out
@@ -1258,22 +1294,22 @@ def main():
             result["skipped"] = []
 
             def optional(name, fn, *a, **kw):
-                """Sections of the default run beyond configs 2-4: started only while the run is inside its time budget."""
-                if not args.full and time.perf_counter() - T_START > args.time_budget:
+                """Sections of a --full run beyond configs 2-4: started only while the run is inside its time budget."""
+                if not args.exhaustive and time.perf_counter() - T_START > args.time_budget:
                     result["skipped"].append(name)
                     log("skipped (time budget): " + name)
                     return None
                 return section(name, fn, *a, **kw)
 
             oc = result["other_configs"] = {}
-            oc["pd_config3"] = section("config 3 (PD)", run_config3, device_index, args.full)
+            oc["pd_config3"] = section("config 3 (PD)", run_config3, device_index, args.exhaustive)
             oc["collisions_config4"] = section("config 4 (500k particles, node-node collisions)", run_config4, device_index)
-            result["scale_1m"] = optional("1M-particle measurements", scale_profiles, device_index, args.full)
-            oc["pd_config5_per_gpu"] = optional("config 5 share (250k particles, PD, binding contacts)", run_config5_share, device_index, args.full)
-            oc["unstructured_config2"] = optional("unstructured beam (PBD and PD)", run_unstructured, device_index, args.full)
+            result["scale_1m"] = optional("1M-particle measurements", scale_profiles, device_index, args.exhaustive)
+            oc["pd_config5_per_gpu"] = optional("config 5 share (250k particles, PD, binding contacts)", run_config5_share, device_index, args.exhaustive)
+            oc["unstructured_config2"] = optional("unstructured beam (PBD and PD)", run_unstructured, device_index, args.exhaustive)
             result["config2_default_tick"] = optional("config 2 with the node-node pass on", run_config2_default_tick, device_index, dims,
-                                                      max(2, min(args.steps, 20)), args.full)
-            if args.full:
+                                                      max(2, min(args.steps, 20)), args.exhaustive)
+            if args.exhaustive:
                 oc["pd_contacts"] = section("PD contact scene", run_pd_contacts, device_index)
                 result["order_deviation"] = section("order deviation", order_deviation, device_index)
                 if not args.no_cpu_baseline:
@@ -1284,10 +1320,12 @@ def main():
                     if result.get("config2_default_tick"):
                         result["config2_default_tick"]["box_100k_distance_only"]["cpu_baseline"] = section("CPU baseline (config 2, node-node pass on)",
                                                                                  cpu_baseline_default_tick, dims, args.cpu_budget)
+    if rank == 0:
         log("done")
-        write_full(result)
+        if args.full:
+            write_full(result)
         sys.stderr.flush()
-        print(compact_line(result), flush=True)
+        print(compact_line(result, full_report=args.full), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -63,7 +63,7 @@ def test_two_rank_bench_end_to_end_on_one_gpu():
     env = dict(os.environ, PIES_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--dims", "10", "10", "60", "--config5-dims", "10", "10", "60", "--quick"]
+           "--dims", "10", "10", "60", "--config5-dims", "10", "10", "60", "--full", "--quick"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

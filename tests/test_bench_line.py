@@ -1,9 +1,11 @@
 """The one stdout line of bench.py: the driver parses it, so it must stay small (round 2's 30 KB line was dropped), strict
-JSON (no NaN) and carry the contract keys whatever the extras hold.  CPU only: compact_line() is fed a synthetic report."""
+JSON (no NaN) and carry the contract keys whatever the extras hold.  compact_line() is fed a synthetic report; the --dump-outputs
+writer a stand-in for the solver's state; one GPU test runs a plain benchmark end to end."""
 import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,3 +105,69 @@ def test_every_name_bench_uses_is_defined():
                     defined.add(n.id)
     used = {n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load)}
     assert not (used - defined), sorted(used - defined)
+
+
+def plain_report():
+    """What a plain run (no --full) reports: the headline and nothing measured beside it."""
+    rep = fake_report()
+    for k in ("cpu_baseline", "exact_order", "coloured_schedule", "tick_inclusive", "other_configs", "order_deviation"):
+        rep.pop(k)
+    rep["roofline"] = None
+    return rep
+
+
+def test_plain_line_carries_the_headline_and_names_no_full_report():
+    r = json.loads(bench.compact_line(plain_report(), full_report=False))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in r, k
+    assert r["roofline"] is None and "cpu_baseline" not in r and "full_report" not in r
+    assert json.loads(bench.compact_line(plain_report()))["full_report"] == "bench_full.json"
+
+
+class _State:
+    def __init__(self, n):
+        self.positions = np.arange(3 * n, dtype=np.float32).reshape(n, 3)
+        self.velocities = -self.positions
+
+
+def test_dump_outputs_writes_float32_state(tmp_path):
+    s = _State(1000)
+    bench.dump_outputs(s, str(tmp_path / "out"))
+    p, v = np.load(tmp_path / "out" / "positions.npy"), np.load(tmp_path / "out" / "velocities.npy")
+    assert p.dtype == np.float32 and v.dtype == np.float32
+    assert np.array_equal(p, s.positions) and np.array_equal(v, s.velocities)
+
+
+def test_dump_outputs_samples_the_same_rows_under_the_size_limit(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4800)  # 200 of 1000 rows of two n x 3 float32 arrays
+    s = _State(1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(s, str(tmp_path / d))
+    p = np.load(tmp_path / "a" / "positions.npy")
+    v = np.load(tmp_path / "a" / "velocities.npy")
+    assert p.nbytes + v.nbytes <= 4800 and len(p) == 200
+    rows = p[:, 0].astype(np.int64) // 3
+    assert np.all(np.diff(rows) > 0) and np.array_equal(v, -p)  # index order, the same rows in every array
+    assert np.array_equal(p, np.load(tmp_path / "b" / "positions.npy"))  # a fixed sample
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run end to end on a small beam, twice: the line's headline keys, `steps` as asked, no extras, and the dumped
+    state of the last timed step identical from run to run (same arguments, same inputs)."""
+    import subprocess
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dims", "10", "10", "60",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+        r = json.loads(out.stdout.strip().splitlines()[-1])
+        assert r["steps"] == 7 and r["warmup"] == 2 and r["value"] > 0 and r["ms_per_step"] > 0
+        assert r["value"] * r["ms_per_step"] * r["steps"] / 1e3 == pytest.approx(7, rel=1e-4)
+        assert r["roofline"] is None and "cpu_baseline" not in r and "full_report" not in r
+        outs.append({k: np.load(tmp_path / run / (k + ".npy")) for k in ("positions", "velocities")})
+    for k in ("positions", "velocities"):
+        a, b = outs[0][k], outs[1][k]
+        assert a.dtype == np.float32 and a.shape == (10 * 10 * 60, 3) and np.isfinite(a).all()
+        assert np.array_equal(a, b), k
