@@ -81,8 +81,10 @@ enum {
   PIES_PD_WINDOW_ENTRIES = 16, /* pies_count only: stored entries (padding included) of the windowed system matrix the CG iterations
                                   stream - value + 16-bit window slot each -, 0: not built (row dictionary, or the SELL arrays) */
   PIES_PD_WINDOW_HALO = 17,    /* pies_count only: its halo entries over all chunks (columns staged in LDS besides a chunk's own rows) */
-  PIES_NODE_PAIRS = 18         /* CollisionConstraint (node-node, PD)  CollisionConstraint.cpp:7-65: an EXTENSION container, see
+  PIES_NODE_PAIRS = 18,        /* CollisionConstraint (node-node, PD)  CollisionConstraint.cpp:7-65: an EXTENSION container, see
                                   pies_add_node_pair_constraints */
+  PIES_NODES_RENUMBERED = 19   /* pies_count only: 1 when the device holds the nodes in another numbering than the host's
+                                  (PIES_FLAG_RENUMBER_NODES, decided by pies_finalize), else 0 */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.
@@ -128,7 +130,16 @@ enum {
    *  GROUPS    : rounds 1-2's order (nodes grouped by minimum cell, 27 residue classes, ascending index inside a group);
    *              needs cell ranges of at most two cells per axis: a scene with gridSpacing < 2 (r_max + 0.5) runs REFERENCE instead.
    * PIES_FLAG_REFERENCE_COLLISION_ORDER = 0 selects PAIRS. */
-  PIES_FLAG_COLLISION_ORDER = 4
+  PIES_FLAG_COLLISION_ORDER = 4,
+  /* Extension, default 0.  1: pies_finalize may renumber the nodes of a PD scene on the device, for meshes whose ids do not
+   * follow space (a tetrahedraliser's output).  It sorts the nodes along a Hilbert curve of their positions and keeps that order
+   * when (a) the scene's own order would not give the system matrix a row dictionary (a createTetBox lattice keeps its order) and
+   * (b) the curve cuts the halo per row of the windowed matrix to 0.8 of the scene's own order or less.  Every id and every
+   * array the host sees stays in host numbering (node state, export frames, container ids, contacts, the tile plan); the
+   * results are the same solve in another summation order (within the PD tolerance).  PBD keeps the
+   * identity.  Takes effect at the next pies_finalize (the scene is rebuilt); pies_count(PIES_NODES_RENUMBERED) and
+   * pies_get_node_order report the outcome. */
+  PIES_FLAG_RENUMBER_NODES = 5
 };
 enum { PIES_COLLISION_ORDER_REFERENCE = 0, PIES_COLLISION_ORDER_GROUPS = 1, PIES_COLLISION_ORDER_PAIRS = 2 };
 
@@ -324,6 +335,9 @@ int pies_set_rest(pies_solver_t* s, int type, uint32_t first, uint32_t n, const 
  * batch_offsets (may be NULL) receives n_batches+1 slot offsets; batches run one after another. */
 int pies_get_order(pies_solver_t* s, int type, uint32_t* order, uint32_t capacity);
 int pies_get_batches(pies_solver_t* s, int type, uint32_t* batch_offsets, uint32_t capacity, uint32_t* n_batches);
+/* The node numbering of the device (PIES_FLAG_RENUMBER_NODES): order[internal] = host id, n = pies_count(PIES_NODES) entries; the
+ * identity when no renumbering is in effect.  Finalizes a changed scene first, like pies_get_order (also on PIES_DEVICE_NONE). */
+int pies_get_node_order(pies_solver_t* s, uint32_t* order, uint32_t capacity);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Times one kernel class in isolation: a graph holding only that class's launches of one substep is
@@ -361,7 +375,7 @@ int pies_profile_in_situ(pies_solver_t* s, int kernel, uint32_t substeps, uint32
 /* The tile plan of the PD strain + volume local step, computed from the host-side scene (also on PIES_DEVICE_NONE handles): tiles of
  * up to 128 element pairs on up to 128 nodes (one wavefront each).  n_tiles = 0 when the scene keeps per-(element, node) records
  * (no strain + volume pairs).  With info != NULL the plan is copied out at fixed strides per tile: info[t] = nodes | elements << 16,
- * node[128 t + k] = node of tile node k, elem[128 t + e] = host index of element slot e, local[128 t + e] = its four tile-local
+ * node[128 t + k] = node of tile node k (host id, also when the nodes are renumbered), elem[128 t + e] = host index of element slot e, local[128 t + e] = its four tile-local
  * node indices (8 bits each), nptr[132 t + k] .. nptr[132 t + k + 1] = tile node k's entries in inc[512 t + ..] (element << 2 |
  * corner).  Any array pointer but info may be NULL. */
 int pies_get_pd_tile_plan(pies_solver_t* s, uint32_t* n_tiles, uint32_t* info, uint32_t* node, uint32_t* elem, uint32_t* local, uint16_t* nptr,

@@ -19,6 +19,7 @@ SCHEDULE_EXACT, SCHEDULE_COLOURED, SCHEDULE_LAYERED = 0, 1, 2
 SCHEDULE_DEFAULT = SCHEDULE_LAYERED  # PIES_SCHEDULE_DEFAULT
 DEVICE_NONE = -1  # PIES_DEVICE_NONE: host-only handle (scenes and schedules, no compute)
 FLAG_RELEASE_HINGE, FLAG_NODE_COLLISIONS, FLAG_TRIANGLE_COLLISIONS, FLAG_REFERENCE_COLLISION_ORDER, FLAG_COLLISION_ORDER = 0, 1, 2, 3, 4
+FLAG_RENUMBER_NODES = 5  # PD: pies_finalize may renumber the nodes on the device (host ids stay the host's)
 COLLISION_ORDER_REFERENCE, COLLISION_ORDER_GROUPS, COLLISION_ORDER_PAIRS = 0, 1, 2
 NODE_POSITION, NODE_PREV_POSITION, NODE_VELOCITY, NODE_RADIUS, NODE_INV_MASS = range(5)
 KERNEL_NAMES = ["predict", "position", "distance", "tet", "bend", "floor", "velocity", "hash", "collide",
@@ -34,6 +35,7 @@ PD_TILE_RECORDS = 14
 PD_CG_SINGLE = 15
 PD_WINDOW_ENTRIES, PD_WINDOW_HALO = 16, 17
 NODE_PAIRS = 18  # the node-node CollisionConstraint extension container (PD)
+NODES_RENUMBERED = 19  # pies_count: 1 when the device holds the nodes in another numbering (FLAG_RENUMBER_NODES)
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
 SYMBOLS = [
@@ -51,7 +53,7 @@ SYMBOLS = [
     "pies_read_positions_strided", "pies_set_pcg_retry", "pies_get_pcg_health", "pies_profile_in_situ",
     "pies_collision_stats", "pies_get_collision_health", "pies_set_collision_rounds", "pies_set_solver", "pies_debug_pair_state", "pies_set_tuning",
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
-    "pies_add_node_pair_constraints",
+    "pies_add_node_pair_constraints", "pies_get_node_order",
 ]
 
 
@@ -126,6 +128,7 @@ def load():
         "pies_set_rest": [vp, i32, u32, u32, pf],
         "pies_get_collision_fallbacks": [vp, pu],
         "pies_get_order": [vp, i32, pu, u32], "pies_get_batches": [vp, i32, pu, u32, pu],
+        "pies_get_node_order": [vp, pu, u32],
         "pies_profile_substep": [vp, i32, pu, C.POINTER(C.c_double), C.POINTER(C.c_uint64)],
         "pies_launch_counts": [vp, pu],
         "pies_set_pcg": [vp, f32, u32],
@@ -511,6 +514,12 @@ class Solver:
     def order(self, ctype):
         out = np.empty(self.count(ctype), dtype=np.uint32)
         self._ck(self._L.pies_get_order(self._h, ctype, _pu(out), out.size))
+        return out
+
+    def node_order(self):
+        """pies_get_node_order: order[internal] = host id (the identity unless FLAG_RENUMBER_NODES renumbered the scene)"""
+        out = np.empty(self.count(NODES), dtype=np.uint32)
+        self._ck(self._L.pies_get_node_order(self._h, _pu(out), out.size))
         return out
 
     def pd_tile_plan(self):

@@ -15,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 
 using namespace pies;
 
@@ -39,6 +40,7 @@ void free_device(pies_solver* s) {
   s->allocations.clear();
   s->nd = NodeArrays{nullptr, nullptr, nullptr, nullptr, 0};
   s->d_pack = nullptr;
+  s->d_nodeInv = nullptr;
   s->d_pc_id = nullptr; s->d_pc_tw = nullptr;
   s->d_dc_ids = nullptr; s->d_dc_rw = nullptr;
   s->d_tc_ids = nullptr; s->d_tc_q0 = s->d_tc_q1 = s->d_tc_q2 = nullptr;
@@ -59,17 +61,25 @@ void free_device(pies_solver* s) {
 
 static int upload_nodes(pies_solver* s) {
   const uint32_t n = s->nodeCount();
+  // a renumbered scene: device index k holds host node order[k] (inside pies_finalize the host arrays are already translated)
+  const bool perm = s->nodeOrder.active() && !s->internalIds && s->nodeOrder.order.size() == n;
   std::vector<float4> pos(n), prev(n), vel(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    pos[i] = make_float4(s->h_pos[3 * i], s->h_pos[3 * i + 1], s->h_pos[3 * i + 2], s->h_invMass[i]);
-    prev[i] = make_float4(s->h_prev[3 * i], s->h_prev[3 * i + 1], s->h_prev[3 * i + 2], 0.f);
-    vel[i] = make_float4(s->h_vel[3 * i], s->h_vel[3 * i + 1], s->h_vel[3 * i + 2], 0.f);
+  std::vector<float> radius;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = perm ? s->nodeOrder.order[k] : k;
+    pos[k] = make_float4(s->h_pos[3 * i], s->h_pos[3 * i + 1], s->h_pos[3 * i + 2], s->h_invMass[i]);
+    prev[k] = make_float4(s->h_prev[3 * i], s->h_prev[3 * i + 1], s->h_prev[3 * i + 2], 0.f);
+    vel[k] = make_float4(s->h_vel[3 * i], s->h_vel[3 * i + 1], s->h_vel[3 * i + 2], 0.f);
+  }
+  if (perm) {
+    radius.resize(n);
+    for (uint32_t k = 0; k < n; ++k) radius[k] = s->h_radius[s->nodeOrder.order[k]];
   }
   if (n) {
     HIP_TRY(s, hipMemcpyAsync(s->nd.pos, pos.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipMemcpyAsync(s->nd.prev, prev.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipMemcpyAsync(s->nd.vel, vel.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->nd.radius, s->h_radius.data(), n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->nd.radius, perm ? radius.data() : s->h_radius.data(), n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     std::vector<float> lrad;
     if (s->d_layer.lrad && s->layer.nodeList.size() == n) {  // schedule LAYERED keeps the radii in level order as well
       lrad.resize(n);
@@ -96,7 +106,7 @@ static int download_nodes(pies_solver* s, uint32_t mask = 7u) {
     // packed on the device: 12 bytes per node cross the bus, and the mirror is one memcpy from the pinned stage (measured on
     // config 2: 654 ticks/s against 637 with four floats per node and an unpacking loop; the asynchronous export stays the
     // fast way out, 680)
-    launch_pack_xyz(s->stream, src[a], s->d_pack, n);
+    launch_pack_xyz(s->stream, src[a], s->d_pack, n, s->d_nodeInv);  // (a renumbered scene: packed in host numbering)
     HIP_TRY(s, hipMemcpyAsync(s->h_stage, s->d_pack, 3ull * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     std::memcpy(dst[a], s->h_stage, 3ull * n * sizeof(float));
@@ -226,6 +236,7 @@ int pies_clear(pies_solver_t* s) {
   s->h_shape.clear(); s->h_goal.clear();  // like the reference, the fixed-region list survives clear() (Solver.cpp:488-507)
   for (Plan& p : s->plan) { p.order.clear(); p.batches.clear(); }
   s->constraintId = 0;
+  s->nodeOrder = NodeOrder{};
   s->sceneDirty = true;
   s->stale = 0;
   s->hostNodesDirty = false;
@@ -256,6 +267,7 @@ int pies_set_flag(pies_solver_t* s, int flag, int value) {
   bool* target = flag == PIES_FLAG_RELEASE_HINGE       ? &s->releaseHinge
                  : flag == PIES_FLAG_NODE_COLLISIONS   ? &s->nodeCollisions
                  : flag == PIES_FLAG_TRIANGLE_COLLISIONS ? &s->triangleCollisions
+                 : flag == PIES_FLAG_RENUMBER_NODES    ? &s->renumberNodes
                                                          : nullptr;
   if (!target) return fail(s, PIES_ERR_INVALID, "pies_set_flag: unknown flag");
   if (*target != (value != 0)) {
@@ -380,7 +392,10 @@ static int build_plans(pies_solver* s, int sched) {
 int pies_finalize(pies_solver_t* s) {
   if (!s) return PIES_ERR_INVALID;
   if (s->device == PIES_DEVICE_NONE) {  // host-only handle: plans can be inspected, nothing is uploaded
-    if (s->sceneDirty) build_plans(s, s->opt.solver == PIES_SOLVER_PD ? -1 : s->schedule);
+    if (s->sceneDirty) {
+      decide_node_order(s);
+      build_plans(s, s->opt.solver == PIES_SOLVER_PD ? -1 : s->schedule);
+    }
     s->sceneDirty = false;
     return PIES_OK;
   }
@@ -401,6 +416,9 @@ int pies_finalize(pies_solver_t* s) {
   free_device(s);
 
   const uint32_t n = s->nodeCount();
+  // ---- node numbering (node_order.cpp): from here on the host containers hold the device's numbering, until this returns ----
+  decide_node_order(s);
+  InternalNumbering internal(s);
   // ---- plans (PD's local step is order independent: one batch per container, host order) ----
   build_plans(s, isPD ? -1 : s->schedule);
   // ---- node arrays ----
@@ -420,6 +438,8 @@ int pies_finalize(pies_solver_t* s) {
     }
   }
   if (int rc = upload_nodes(s)) return rc;
+  if (s->nodeOrder.active())
+    if (int rc = upload(s, s->nodeOrder.inv, &s->d_nodeInv)) return rc;
   // ---- constraint records, in schedule order ----
   {
     const Plan& pl = s->plan[PIES_POSITION];
@@ -855,7 +875,12 @@ int pies_tick_begin(pies_solver_t* s, uint64_t* frame) {
   if (n) {
     // d_export is free once the previous frame's D2H copy has read it; by now that copy finished long ago
     if (f > 1) HIP_TRY(s, hipStreamWaitEvent(s->stream, s->evCopied[b ^ 1], 0));
-    HIP_TRY(s, hipMemcpyAsync(s->d_export, s->nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    if (s->d_nodeInv) {  // a renumbered scene: the frame in host numbering
+      launch_gather_nodes(s->stream, s->nd.pos, s->d_export, s->d_nodeInv, n);
+      HIP_TRY(s, hipGetLastError());
+    } else {
+      HIP_TRY(s, hipMemcpyAsync(s->d_export, s->nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    }
   }
   HIP_TRY(s, hipEventRecord(s->evTick[b], s->stream));
   HIP_TRY(s, hipStreamWaitEvent(s->copyStream, s->evTick[b], 0));
@@ -935,6 +960,9 @@ int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, ui
     if (m > capacity) return fail(s, PIES_ERR_INVALID, "pies_get_tri_contacts: capacity too small");
     HIP_TRY(s, hipMemcpyAsync(ids, s->pd.tri.ids, static_cast<size_t>(m) * sizeof(uint4), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
+    if (s->d_nodeInv)  // a renumbered scene: the device lists internal ids
+      for (size_t k = 0; k < 4ull * m; ++k)
+        if (ids[k] < s->nodeOrder.order.size()) ids[k] = s->nodeOrder.order[ids[k]];
   }
   return PIES_OK;
 }
@@ -1040,6 +1068,7 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_PD_CG_SINGLE: *out = s->opt.solver == PIES_SOLVER_PD && pd_single_cg(s) ? 1u : 0u; break;
     case PIES_PD_WINDOW_ENTRIES: *out = s->pd.cg.wRows ? s->pdWindowEntries : 0u; break;
     case PIES_PD_WINDOW_HALO: *out = s->pd.cg.wRows ? s->pdWindowHalo : 0u; break;
+    case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
     default: return PIES_ERR_INVALID;
   }
   return PIES_OK;
@@ -1163,11 +1192,17 @@ int pies_get_batches(pies_solver_t* s, int type, uint32_t* offs, uint32_t capaci
 int pies_get_pd_tile_plan(pies_solver_t* s, uint32_t* n_tiles, uint32_t* info, uint32_t* node, uint32_t* elem, uint32_t* local, uint16_t* nptr,
                           uint16_t* inc, uint32_t tile_capacity) {
   if (!s || !n_tiles) return PIES_ERR_INVALID;
-  const bool paired = s->tetVolumePaired;
-  s->tetVolumePaired = tet_volume_pairs(s);
   PdTilePlan plan;
-  const bool ok = pd_plan_tiles(s, plan);
-  s->tetVolumePaired = paired;
+  bool ok = false;
+  {
+    InternalNumbering internal(s);  // the plan of the numbering the device holds; its node ids are mapped back below
+    const bool paired = s->tetVolumePaired;
+    s->tetVolumePaired = tet_volume_pairs(s);
+    ok = pd_plan_tiles(s, plan);
+    s->tetVolumePaired = paired;
+    if (ok && s->internalIds)
+      for (uint32_t& v : plan.node) v = s->nodeOrder.order[v];
+  }
   *n_tiles = ok ? static_cast<uint32_t>(plan.info.size()) : 0u;
   if (!ok || !info) return PIES_OK;
   if (plan.info.size() > tile_capacity) return fail(s, PIES_ERR_INVALID, "pies_get_pd_tile_plan: capacity too small");
@@ -1177,6 +1212,17 @@ int pies_get_pd_tile_plan(pies_solver_t* s, uint32_t* n_tiles, uint32_t* info, u
   if (local) std::memcpy(local, plan.local.data(), plan.local.size() * sizeof(uint32_t));
   if (nptr) std::memcpy(nptr, plan.nptr.data(), plan.nptr.size() * sizeof(uint16_t));
   if (inc) std::memcpy(inc, plan.inc.data(), plan.inc.size() * sizeof(uint16_t));
+  return PIES_OK;
+}
+
+int pies_get_node_order(pies_solver_t* s, uint32_t* order, uint32_t capacity) {
+  if (!s || !order) return PIES_ERR_INVALID;
+  if (s->sceneDirty)
+    if (int rc = pies_finalize(s)) return rc;
+  const uint32_t n = s->nodeCount();
+  if (n > capacity) return fail(s, PIES_ERR_INVALID, "pies_get_node_order: capacity too small");
+  if (s->nodeOrder.active() && s->nodeOrder.order.size() == n) std::memcpy(order, s->nodeOrder.order.data(), n * sizeof(uint32_t));
+  else std::iota(order, order + n, 0u);
   return PIES_OK;
 }
 

@@ -36,6 +36,14 @@ template <class T> int upload(pies_solver* s, const std::vector<T>& h, T** d) {
   return PIES_OK;
 }
 
+// The PD system matrix as CSR (pd_setup.cpp), in the numbering the host containers hold
+struct PdSystem {
+  std::vector<uint32_t> rowptr, col;
+  std::vector<float> val, kdiag;
+};
+void pd_assemble(const pies_solver* s, PdSystem& K);
+bool pd_row_dictionary_applies(const PdSystem& K);  // pd_build would give K a row dictionary (PIES_ROW_STENCILS > 0)
+uint32_t pd_window_chunk_rows();                    // rows per chunk of the windowed matrix (PIES_CG_CHUNK_ROWS, default 256)
 int pd_build(pies_solver* s);         // pd_setup.cpp
 int pd_upload_goals(pies_solver* s);  // pd_setup.cpp
 bool pd_plan_tiles(const pies_solver* s, PdTilePlan& out);  // pd_tiles.cpp; false: the scene keeps per-(element, node) records

@@ -91,7 +91,9 @@ void launch_lcopy(hipStream_t st, const NodeArrays& nd, const LayerData& D, bool
 // an empty kernel (one wavefront): calibrates the cost of an event bracket (pies_profile_in_situ)
 void launch_noop(hipStream_t st);
 // x, y, z of n four-float records, packed (the host mirrors' layout)
-void launch_pack_xyz(hipStream_t st, const float4* src, float* dst, uint32_t n);
+// inv (a renumbered PD scene): dst in host numbering, dst[h] = src[inv[h]]; nullptr: dst[i] = src[i]
+void launch_pack_xyz(hipStream_t st, const float4* src, float* dst, uint32_t n, const uint32_t* inv = nullptr);
+void launch_gather_nodes(hipStream_t st, const float4* src, float4* dst, const uint32_t* inv, uint32_t n);
 // Solver.cpp:47-52
 void launch_predict(hipStream_t st, const NodeArrays& nd, float dt, float gravity);
 // Solver.cpp:132-136

@@ -132,7 +132,8 @@ bool build_window_matrix(uint32_t n, const std::vector<uint32_t>& rowptr, const 
   return true;
 }
 
-int pd_build(pies_solver* s) {
+// K = diag(1/(invMass h^2)) + sum_c w_c A_c^T A_c as CSR (ascending columns), entries summed in the reference's container order
+void pd_assemble(const pies_solver* s, PdSystem& K) {
   const uint32_t n = s->nodeCount();
   const float h = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
   const float h2 = h * h;
@@ -160,8 +161,13 @@ int pd_build(pies_solver* s) {
   for (const HostNodePair& c : s->h_nodePair)  // CollisionConstraint.cpp:43-47 (extension container: the pairs are the scene's, so
     for (uint32_t id : c.ids) rows[id].push_back({id, kNodePairW});  // their diagonal terms are part of K, not rebuilt every substep)
 
-  std::vector<uint32_t> rowptr(n + 1, 0), col;
-  std::vector<float> val, kdiag(n, 0.f);
+  std::vector<uint32_t>& rowptr = K.rowptr;
+  std::vector<uint32_t>& col = K.col;
+  std::vector<float>& val = K.val;
+  rowptr.assign(n + 1, 0);
+  col.clear();
+  val.clear();
+  K.kdiag.assign(n, 0.f);
   col.reserve(static_cast<size_t>(n) * 16);
   val.reserve(static_cast<size_t>(n) * 16);
   for (uint32_t i = 0; i < n; ++i) {
@@ -173,19 +179,85 @@ int pd_build(pies_solver* s) {
       for (; m < r.size() && r[m].col == r[k].col; ++m) acc += r[m].val;
       col.push_back(r[k].col);
       val.push_back(acc);
-      if (r[k].col == i) kdiag[i] = acc;
+      if (r[k].col == i) K.kdiag[i] = acc;
       k = m;
     }
     rowptr[i + 1] = static_cast<uint32_t>(col.size());
     std::vector<Entry>().swap(r);
   }
+}
+
+namespace {
+// lanes per row of the sliced ELL arrays
+uint32_t sell_lanes() {
+  uint32_t lpr = 1u;
+  if (const char* e = tuning_env("PIES_SELL_LANES")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) lpr = static_cast<uint32_t>(v); }
+  return lpr;
+}
+
+// Row dictionary: every row as (column - row, value) pairs; rows with equal sequences share an entry.  Used when the scene
+// has few distinct rows (a lattice: the interior row and the classes of boundary rows, a few hundred at most).
+struct RowDictionary {
+  std::vector<uint32_t> rowStencil;
+  std::vector<int2_host> stencil;
+  uint32_t rows = 0;  // distinct rows
+};
+bool build_row_dictionary(const PdSystem& K, RowDictionary& D) {
+  const uint32_t n = static_cast<uint32_t>(K.kdiag.size());
+  const char* e = tuning_env("PIES_PD_ROW_DICT");
+  if (sell_lanes() != 1u || n == 0 || (e && e[0] == '0')) return false;
+  std::map<std::vector<int2_host>, uint16_t> ids;
+  D.rowStencil.assign(n, 0u);
+  D.stencil.clear();
+  std::vector<uint32_t> stencilAt(1, 0);
+  std::vector<int2_host> key;
+  for (uint32_t i = 0; i < n; ++i) {
+    key.clear();
+    for (uint32_t k = K.rowptr[i]; k < K.rowptr[i + 1]; ++k) {
+      int2_host p;
+      p.x = static_cast<int>(K.col[k]) - static_cast<int>(i);
+      std::memcpy(&p.y, &K.val[k], sizeof(float));
+      key.push_back(p);
+    }
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      if (ids.size() >= 4096 || (ids.size() + 1) * 8 > n || key.size() > 255 || D.stencil.size() + key.size() >= (1u << 24)) return false;  // no real compression: the SELL arrays
+      it = ids.emplace(key, static_cast<uint16_t>(ids.size())).first;
+      D.stencil.insert(D.stencil.end(), key.begin(), key.end());
+      stencilAt.push_back(static_cast<uint32_t>(D.stencil.size()));
+    }
+    D.rowStencil[i] = stencilAt[it->second] | (static_cast<uint32_t>(key.size()) << 24);
+  }
+  D.rows = static_cast<uint32_t>(ids.size());
+  return true;
+}
+}  // namespace
+
+bool pd_row_dictionary_applies(const PdSystem& K) {
+  RowDictionary D;
+  return build_row_dictionary(K, D);
+}
+
+uint32_t pd_window_chunk_rows() {
+  uint32_t R = 256;
+  if (const char* e = tuning_env("PIES_CG_CHUNK_ROWS")) { const int v = std::atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) R = static_cast<uint32_t>(v); }
+  return R;
+}
+
+int pd_build(pies_solver* s) {
+  const uint32_t n = s->nodeCount();
+  PdSystem K;
+  pd_assemble(s, K);
+  const std::vector<uint32_t>& rowptr = K.rowptr;
+  const std::vector<uint32_t>& col = K.col;
+  const std::vector<float>& val = K.val;
+  const std::vector<float>& kdiag = K.kdiag;
   s->pd_nnz = static_cast<uint32_t>(col.size());
   // CSR -> sliced ELL (see CgArrays).  A slice is one wavefront's worth of rows: 64 rows with one lane each.  (Several lanes
   // per row - lane L r + q taking entries q, q + L, ... of row r, partial sums combined by shuffles - were measured at 100k
   // rows: k_cg_ap 5.4 us with 1 lane per row, 7.8 / 10.4 / 14.5 us with 2 / 4 / 8: the extra wavefronts only add gather
   // instructions.  PIES_SELL_LANES keeps the experiment available.)  Entries keep their order (ascending column).
-  uint32_t lpr = 1u;
-  if (const char* e = tuning_env("PIES_SELL_LANES")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) lpr = static_cast<uint32_t>(v); }
+  const uint32_t lpr = sell_lanes();
   const uint32_t rps = 64u / lpr;
   const uint32_t nslices = (n + rps - 1u) / rps;
   std::vector<uint32_t> sliceOff(nslices + 1, 0), sellCol;
@@ -322,43 +394,17 @@ int pd_build(pies_solver* s) {
   if (int rc = upload(s, triCount, &d_tri)) return rc;
 
   cg.sliceOff = d_rowptr; cg.col = d_col; cg.val = d_val;
-  // Row dictionary: every row as (column - row, value) pairs; rows with equal sequences share an entry.  Used when the scene
-  // has few distinct rows (a lattice: the interior row and the classes of boundary rows, a few hundred at most).
+  // Row dictionary (build_row_dictionary)
   cg.rowStencil = nullptr; cg.stencil = nullptr;
   {
-    const char* e = tuning_env("PIES_PD_ROW_DICT");
-    if (lpr == 1u && n != 0 && !(e && e[0] == '0')) {
-      std::map<std::vector<int2_host>, uint16_t> ids;
-      std::vector<uint32_t> rowStencil(n);
-      std::vector<uint32_t> stencilAt(1, 0);
-      std::vector<int2_host> stencil;
-      bool ok = true;
-      std::vector<int2_host> key;
-      for (uint32_t i = 0; ok && i < n; ++i) {
-        key.clear();
-        for (uint32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-          int2_host p;
-          p.x = static_cast<int>(col[k]) - static_cast<int>(i);
-          std::memcpy(&p.y, &val[k], sizeof(float));
-          key.push_back(p);
-        }
-        auto it = ids.find(key);
-        if (it == ids.end()) {
-          if (ids.size() >= 4096 || (ids.size() + 1) * 8 > n || key.size() > 255 || stencil.size() + key.size() >= (1u << 24)) { ok = false; break; }  // no real compression: the SELL arrays
-          it = ids.emplace(key, static_cast<uint16_t>(ids.size())).first;
-          stencil.insert(stencil.end(), key.begin(), key.end());
-          stencilAt.push_back(static_cast<uint32_t>(stencil.size()));
-        }
-        rowStencil[i] = stencilAt[it->second] | (static_cast<uint32_t>(key.size()) << 24);
-      }
-      if (ok) {
-        uint32_t* d_rs;
-        int2_host* d_st;
-        if (int rc = upload(s, rowStencil, &d_rs)) return rc;
-        if (int rc = upload(s, stencil, &d_st)) return rc;
-        cg.rowStencil = d_rs; cg.stencil = reinterpret_cast<const int2*>(d_st);
-        s->pdRowStencils = static_cast<uint32_t>(ids.size());
-      }
+    RowDictionary D;
+    if (build_row_dictionary(K, D)) {
+      uint32_t* d_rs;
+      int2_host* d_st;
+      if (int rc = upload(s, D.rowStencil, &d_rs)) return rc;
+      if (int rc = upload(s, D.stencil, &d_st)) return rc;
+      cg.rowStencil = d_rs; cg.stencil = reinterpret_cast<const int2*>(d_st);
+      s->pdRowStencils = D.rows;
     }
   }
   cg.lanesPerRow = lpr;
@@ -373,8 +419,7 @@ int pd_build(pies_solver* s) {
   {
     int mode = 1;
     if (const char* e = tuning_env("PIES_PD_WINDOW")) mode = std::atoi(e);
-    uint32_t R = 256;
-    if (const char* e = tuning_env("PIES_CG_CHUNK_ROWS")) { const int v = std::atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) R = static_cast<uint32_t>(v); }
+    const uint32_t R = pd_window_chunk_rows();
     int sortMode = -1;
     if (const char* e = tuning_env("PIES_PD_WINDOW_SORT")) sortMode = std::atoi(e) ? 1 : 0;
     WindowMatrix W;

@@ -154,6 +154,14 @@ struct PdTilePlan {
   uint64_t tileNodes = 0;        // sum of the tiles' node counts
 };
 
+// Node renumbering of PD scenes (PIES_FLAG_RENUMBER_NODES, node_order.cpp).  Empty: the device holds node h at index h.
+// Otherwise the device holds the nodes in the internal numbering: order[k] is the host id of internal node k, inv its inverse.
+// The host mirror and every id the host sees stay in host numbering.
+struct NodeOrder {
+  std::vector<uint32_t> order, inv;
+  bool active() const { return !order.empty(); }
+};
+
 template <class T> struct DevArray {
   T* p = nullptr;
   size_t n = 0;
@@ -194,6 +202,10 @@ struct pies_solver {
   uint32_t pdRowStencils = 0;           // PD: distinct rows of the system matrix in its row dictionary (0: none)
   bool tetVolumePaired = false;    // PD: h_volume[k] and h_tet[k] are the same element for every k (fused local step)
   bool triangleCollisions = true;  // PD point-triangle CCD contacts (Solver.cpp:693-797); extension flag to switch off
+  bool renumberNodes = false;      // PIES_FLAG_RENUMBER_NODES: pies_finalize may renumber the nodes of a PD scene (node_order.cpp)
+  pies::NodeOrder nodeOrder;       // the numbering the device holds (decided by the last pies_finalize)
+  bool internalIds = false;        // the host containers hold the internal numbering (inside an InternalNumbering scope)
+  uint32_t* d_nodeInv = nullptr;   // HBM copy of nodeOrder.inv (nullptr: identity); freed with the device state
   bool simFailed = false;
   int schedule = PIES_SCHEDULE_DEFAULT;
   int collisionOrderFlag = -1;     // PIES_FLAG_COLLISION_ORDER: -1 follows the schedule (EXACT: reference order, otherwise pair order)
@@ -315,4 +327,28 @@ void build_plan(const OpView& ops, uint32_t nodeCount, int schedule, Plan& out);
 bool build_wave_plan(const pies_solver* s, WavePlan& out);
 // layer_plan.cpp : fills s->layer and the four PBD plans; false (nothing changed) when the scene does not suit it
 bool build_layer_plan(pies_solver* s);
+
+// node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
+void decide_node_order(pies_solver* s);
+// For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of
+// s->nodeOrder; the host numbering is put back on destruction.  Does nothing when the identity is in effect.
+class InternalNumbering {
+ public:
+  explicit InternalNumbering(pies_solver* s);
+  ~InternalNumbering();
+  InternalNumbering(const InternalNumbering&) = delete;
+  InternalNumbering& operator=(const InternalNumbering&) = delete;
+
+ private:
+  pies_solver* s_ = nullptr;
+  std::vector<float> pos_, prev_, vel_, radius_, invMass_;
+  std::vector<HostPosition> position_;
+  std::vector<HostDistance> distance_;
+  std::vector<HostTet> tet_, volume_;
+  std::vector<HostBend> bend_;
+  std::vector<HostNodePair> nodePair_;
+  std::vector<HostShape> shape_;
+  std::vector<HostGoal> goal_;
+  std::vector<uint32_t> triangles_, lines_;
+};
 }  // namespace pies
