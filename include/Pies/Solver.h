@@ -74,6 +74,7 @@ public:
   bool triangleCollisions = true;   // PD point-triangle contacts (Solver.cpp:693-797)
   bool renumberNodes = false;       // extension: PD may keep the nodes in a space-filling-curve order on the device
                                     // (PIES_FLAG_RENUMBER_NODES); getVertices() and every id stay the host's
+  bool pdNodeContacts = false;      // extension: PD detects node-node contacts every substep (PIES_FLAG_PD_NODE_CONTACTS)
 
   // Like the reference's (Solver.h:54-55: `Solver() = default`, a converting constructor from the options): constructing a
   // Solver touches no device.  The device handle is opened by the first call that needs it (add*/create*/tick), which is
@@ -88,7 +89,7 @@ public:
       rhs._h = nullptr;
       _options = rhs._options;
       _device = rhs._device;
-      for (int k = 0; k < 6; ++k) _pushed[k] = rhs._pushed[k];
+      for (int k = 0; k < 7; ++k) _pushed[k] = rhs._pushed[k];
       _vertices = std::move(rhs._vertices);
       _lines = std::move(rhs._lines);
       _triangles = std::move(rhs._triangles);
@@ -100,6 +101,7 @@ public:
       nodeCollisions = rhs.nodeCollisions;
       triangleCollisions = rhs.triangleCollisions;
       renumberNodes = rhs.renumberNodes;
+      pdNodeContacts = rhs.pdNodeContacts;
     }
     return *this;
   }
@@ -366,15 +368,16 @@ private:
   // the public flags, the schedule and the solver to run reach the handle when they differ from what it was last given
   void _pushState(SolverName solver) {
     pies_solver_t* h = _handle();
-    const int now[6] = {releaseHinge ? 1 : 0, nodeCollisions ? 1 : 0, triangleCollisions ? 1 : 0, schedule, static_cast<int>(solver),
-                        renumberNodes ? 1 : 0};
+    const int now[7] = {releaseHinge ? 1 : 0, nodeCollisions ? 1 : 0, triangleCollisions ? 1 : 0, schedule, static_cast<int>(solver),
+                        renumberNodes ? 1 : 0, pdNodeContacts ? 1 : 0};
     if (now[0] != _pushed[0]) _ck(pies_set_flag(h, PIES_FLAG_RELEASE_HINGE, now[0]));
     if (now[1] != _pushed[1]) _ck(pies_set_flag(h, PIES_FLAG_NODE_COLLISIONS, now[1]));
     if (now[2] != _pushed[2]) _ck(pies_set_flag(h, PIES_FLAG_TRIANGLE_COLLISIONS, now[2]));
     if (now[3] != _pushed[3] && now[3] >= 0) _ck(pies_set_schedule(h, now[3]));
     if (now[4] != _pushed[4]) _ck(pies_set_solver(h, now[4]));
     if (now[5] != _pushed[5]) _ck(pies_set_flag(h, PIES_FLAG_RENUMBER_NODES, now[5]));
-    for (int k = 0; k < 6; ++k) _pushed[k] = now[k];
+    if (now[6] != _pushed[6]) _ck(pies_set_flag(h, PIES_FLAG_PD_NODE_CONTACTS, now[6]));
+    for (int k = 0; k < 7; ++k) _pushed[k] = now[k];
   }
   void _tickAs(SolverName solver) {
     _pushState(solver);
@@ -385,8 +388,8 @@ private:
   pies_solver_t* _h = nullptr;
   SolverOptions _options;
   int _device = 0;
-  int _pushed[6] = {-2, -2, -2, -2, -2, -2};  // releaseHinge, nodeCollisions, triangleCollisions, schedule, solver, renumberNodes as last
-                                              // given to the handle
+  int _pushed[7] = {-2, -2, -2, -2, -2, -2, -2};  // releaseHinge, nodeCollisions, triangleCollisions, schedule, solver, renumberNodes,
+                                                  // pdNodeContacts as last given to the handle
   std::vector<Vertex> _vertices;
   std::vector<uint32_t> _lines;
   std::vector<Triangle> _triangles;

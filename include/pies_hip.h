@@ -83,8 +83,10 @@ enum {
   PIES_PD_WINDOW_HALO = 17,    /* pies_count only: its halo entries over all chunks (columns staged in LDS besides a chunk's own rows) */
   PIES_NODE_PAIRS = 18,        /* CollisionConstraint (node-node, PD)  CollisionConstraint.cpp:7-65: an EXTENSION container, see
                                   pies_add_node_pair_constraints */
-  PIES_NODES_RENUMBERED = 19   /* pies_count only: 1 when the device holds the nodes in another numbering than the host's
+  PIES_NODES_RENUMBERED = 19,  /* pies_count only: 1 when the device holds the nodes in another numbering than the host's
                                   (PIES_FLAG_RENUMBER_NODES, decided by pies_finalize), else 0 */
+  PIES_NODE_CONTACTS = 20      /* pies_count only: node-node contacts of the last PD substep (PIES_FLAG_PD_NODE_CONTACTS; synchronises),
+                                  0 before the first tick and without the flag */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.
@@ -139,7 +141,22 @@ enum {
    * results are the same solve in another summation order (within the PD tolerance).  PBD keeps the
    * identity.  Takes effect at the next pies_finalize (the scene is rebuilt); pies_count(PIES_NODES_RENUMBERED) and
    * pies_get_node_order report the outcome. */
-  PIES_FLAG_RENUMBER_NODES = 5
+  PIES_FLAG_RENUMBER_NODES = 5,
+  /* Extension, default 0.  1: a PD scene detects node-node contacts on the device once per substep, after the prediction
+   * (where tickPD would, Solver.cpp:240), with the rule of Solver::_parallelComputeCollisions (Solver.cpp:509-637, never called by
+   * the reference) made explicit: nodes i, j are in contact when they share a cell of the node grid (gridSpacing, each node's range
+   * from its radius - the grid of the PBD pass), |p_i - p_j|^2 < (r_i + r_j)^2 in fp32 (the test of CollisionConstraint.cpp:20-24),
+   * invMass_i + invMass_j > 0 (:36 divides by it), and no element joins them (distance, tetrahedral, volume or bend constraint,
+   * triangle, listed node pair: a non-overlapping CollisionConstraint anchors its nodes with w = 1e5).
+   * Every contact is a CollisionConstraint (CollisionConstraint.cpp:7-65, w = 1e5): w on the node's diagonal, w * projected in
+   * the right-hand side of every local step, and the friction loop of Solver.cpp:398-428 after the velocity update, in ascending
+   * order of a 64-bit mix of the pair's device ids (run in parallel rounds, the same result bit for bit); the contacts' nodes get
+   * their floor friction (:473-484) after it.  Nothing is summed with atomics: runs are reproducible.  A node holds at most
+   * PIES_PD_NODE_CONTACT_PARTNERS partners (pies_set_tuning, read at pies_finalize, default 32); more latch the failure
+   * (pies_failed, pies_last_error names the list).  Memory: nodes x partners x 4 bytes (1M nodes x 32 = 128 MB) plus the node
+   * grid.  With the flag the PD CG ceiling defaults to 256 iterations (pies_set_pcg overrides).  PBD ignores the flag (its own
+   * node-node pass: PIES_FLAG_NODE_COLLISIONS).  Takes effect at the next pies_finalize.  See pies_get_node_contacts. */
+  PIES_FLAG_PD_NODE_CONTACTS = 6
 };
 enum { PIES_COLLISION_ORDER_REFERENCE = 0, PIES_COLLISION_ORDER_GROUPS = 1, PIES_COLLISION_ORDER_PAIRS = 2 };
 
@@ -273,6 +290,10 @@ int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, ui
  * without a common node in a shared cell), out[1] = pairs with at least one hit, out[2..4] = longest range listed per class (in
  * cells of the class), out[5..7] = triangles listed per class. */
 int pies_get_tri_grid_stats(pies_solver_t* s, uint32_t out[8]);
+/* PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the last PD substep as (i, j) pairs of host ids (ids: 2 x count), in the
+ * order the friction loop ran them (ascending pair key).  ids may be NULL to query the count; synchronises.  The reference keeps
+ * them in Solver::_collisions (Solver.h), filled by _parallelComputeCollisions (Solver.cpp:509-637). */
+int pies_get_node_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, uint32_t* count);
 /* Node-node pairs resolved by the PBD collision pass since the last call (statistics). */
 int pies_collision_pairs(pies_solver_t* s, uint64_t* pairs);
 /* The same plus the candidates the pass looked at (bucket entries visited, the unit of SURVEY 8d's "16 B per candidate
@@ -289,6 +310,7 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * arrays only, no row dictionary), PIES_LAYER_PLAN (0: schedule LAYERED's original plan only, 1: + single-level constraints dealt to either group, 2: + slabs by position; default 2) / _PLAN_FORCE (candidate index) / _SLAB / _SLAB_OFFSET, PIES_LAYER_ONE_STRIP_MAX / _TILE_NODES / _STRIPS_MIN_NODES / PIES_LAYER_BLOCK,
  * PIES_PD_TILE_ELEMS (0: per-(element, node) records instead of the tile-resident local step), PIES_PD_CG_SINGLE / _SINGLE_ROWS (0: the
  * two-launch CG everywhere / in the contact-heavy variant), PIES_PD_FUSE_RHS (0: k_pd_rhs), PIES_PD_RHS_LANES,
+ * PIES_PD_NODE_CONTACT_PARTNERS (partners per node of PIES_FLAG_PD_NODE_CONTACTS, default 32) / _ROUNDS (pins the friction rounds captured),
  * PIES_COLOUR_ROUNDS, PIES_COLOUR_DSATUR, PIES_NO_COLOUR_HINT, PIES_SELL_LANES, PIES_CG_BLOCKS, PIES_COLLIDE_GLOBAL / _PASSES /
  * _SPIN_LIMIT; round 5: PIES_PD_WINDOW (0: no windowed matrix, 2: also beside a row dictionary) / _WINDOW_KERNELS (1 iterations, 2 first
  * product, 4 residual; default 3) / _WINDOW_SORT / _WINDOW_HALO32 (tests: 32-bit halo list), PIES_CG_CHUNK_ROWS, PIES_PCG_NEVER_EXIT (profiling: every captured CG launch works),

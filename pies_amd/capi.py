@@ -20,6 +20,7 @@ SCHEDULE_DEFAULT = SCHEDULE_LAYERED  # PIES_SCHEDULE_DEFAULT
 DEVICE_NONE = -1  # PIES_DEVICE_NONE: host-only handle (scenes and schedules, no compute)
 FLAG_RELEASE_HINGE, FLAG_NODE_COLLISIONS, FLAG_TRIANGLE_COLLISIONS, FLAG_REFERENCE_COLLISION_ORDER, FLAG_COLLISION_ORDER = 0, 1, 2, 3, 4
 FLAG_RENUMBER_NODES = 5  # PD: pies_finalize may renumber the nodes on the device (host ids stay the host's)
+FLAG_PD_NODE_CONTACTS = 6  # PD: node-node contacts detected on the device every substep
 COLLISION_ORDER_REFERENCE, COLLISION_ORDER_GROUPS, COLLISION_ORDER_PAIRS = 0, 1, 2
 NODE_POSITION, NODE_PREV_POSITION, NODE_VELOCITY, NODE_RADIUS, NODE_INV_MASS = range(5)
 KERNEL_NAMES = ["predict", "position", "distance", "tet", "bend", "floor", "velocity", "hash", "collide",
@@ -36,6 +37,7 @@ PD_CG_SINGLE = 15
 PD_WINDOW_ENTRIES, PD_WINDOW_HALO = 16, 17
 NODE_PAIRS = 18  # the node-node CollisionConstraint extension container (PD)
 NODES_RENUMBERED = 19  # pies_count: 1 when the device holds the nodes in another numbering (FLAG_RENUMBER_NODES)
+NODE_CONTACTS = 20  # pies_count: node-node contacts of the last PD substep (FLAG_PD_NODE_CONTACTS)
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
 SYMBOLS = [
@@ -53,7 +55,7 @@ SYMBOLS = [
     "pies_read_positions_strided", "pies_set_pcg_retry", "pies_get_pcg_health", "pies_profile_in_situ",
     "pies_collision_stats", "pies_get_collision_health", "pies_set_collision_rounds", "pies_set_solver", "pies_debug_pair_state", "pies_set_tuning",
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
-    "pies_add_node_pair_constraints", "pies_get_node_order",
+    "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
 ]
 
 
@@ -144,6 +146,7 @@ def load():
         "pies_create_shape_matching_sheet": [vp, u32, u32, pf, f32, f32],
         "pies_get_group": [vp, i32, u32, pu, u32, pu],
         "pies_get_tri_contacts": [vp, pu, u32, pu],
+        "pies_get_node_contacts": [vp, pu, u32, pu],
         "pies_get_tri_grid_stats": [vp, pu],
         "pies_tick_begin": [vp, C.POINTER(C.c_uint64)],
         "pies_export_acquire": [vp, C.c_uint64, C.POINTER(pf), pu],
@@ -414,6 +417,16 @@ class Solver:
         if n.value:
             self._ck(self._L.pies_get_tri_contacts(self._h, _pu(out), n.value, C.byref(n)))
         return out
+
+    def node_contacts(self):
+        """pies_get_node_contacts: the last PD substep's node-node contacts (FLAG_PD_NODE_CONTACTS) as an (m, 2) array of host ids,
+        in the order the friction loop ran them"""
+        n = C.c_uint32()
+        self._ck(self._L.pies_get_node_contacts(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 2), dtype=np.uint32)
+        if n.value:
+            self._ck(self._L.pies_get_node_contacts(self._h, _pu(out), n.value, C.byref(n)))
+        return out[: n.value]
 
     def tri_grid_stats(self):
         """pies_get_tri_grid_stats: the broad phase of the last PD substep's point-triangle detection."""

@@ -50,6 +50,8 @@ void free_device(pies_solver* s) {
   s->pd = PdArrays{};
   s->hash = HashArrays{};
   s->pairs = PairArrays{};
+  s->nc = NodeContactArrays{};
+  s->ncActive = false;
   s->d_pairDictIndex = nullptr;
   s->d_pairDictTable = nullptr;
   s->pairDictSets = 0;
@@ -268,6 +270,7 @@ int pies_set_flag(pies_solver_t* s, int flag, int value) {
                  : flag == PIES_FLAG_NODE_COLLISIONS   ? &s->nodeCollisions
                  : flag == PIES_FLAG_TRIANGLE_COLLISIONS ? &s->triangleCollisions
                  : flag == PIES_FLAG_RENUMBER_NODES    ? &s->renumberNodes
+                 : flag == PIES_FLAG_PD_NODE_CONTACTS  ? &s->pdNodeContacts
                                                          : nullptr;
   if (!target) return fail(s, PIES_ERR_INVALID, "pies_set_flag: unknown flag");
   if (*target != (value != 0)) {
@@ -310,6 +313,7 @@ int pies_set_schedule(pies_solver_t* s, int schedule) {
 
 int pies_set_pcg(pies_solver_t* s, float rel_tol, uint32_t max_iters) {
   if (!s || !(rel_tol >= 0.0f) || max_iters == 0 || max_iters > 4096) return fail(s, PIES_ERR_INVALID, "pies_set_pcg: bad argument");
+  s->pcgCeilingSet = true;
   if (rel_tol != s->pcgTol || max_iters != s->pcgMaxIters) {
     s->pcgTol = rel_tol;
     s->pcgMaxIters = max_iters;
@@ -389,6 +393,109 @@ static int build_plans(pies_solver* s, int sched) {
   return PIES_OK;
 }
 
+// PIES_FLAG_PD_NODE_CONTACTS: the element adjacency that excludes pairs from the contacts - per node, ascending, in the device's
+// numbering (inside pies_finalize the host containers hold it) -, the partner lists and the friction pass's cursors and words
+static int nc_build(pies_solver* s, uint32_t n) {
+  std::vector<uint64_t> e;  // a << 32 | b, both directions
+  auto join = [&](uint32_t a, uint32_t b) {
+    if (a == b || a >= n || b >= n) return;
+    e.push_back(static_cast<uint64_t>(a) << 32 | b);
+    e.push_back(static_cast<uint64_t>(b) << 32 | a);
+  };
+  auto clique = [&](const uint32_t* ids, int k) {
+    for (int a = 0; a < k; ++a)
+      for (int b = a + 1; b < k; ++b) join(ids[a], ids[b]);
+  };
+  for (const HostDistance& c : s->h_distance) clique(c.ids, 2);
+  for (const HostTet& c : s->h_tet) clique(c.ids, 4);
+  for (const HostTet& c : s->h_volume) clique(c.ids, 4);
+  for (const HostBend& c : s->h_bend) clique(c.ids, 4);
+  for (size_t t = 0; t + 2 < s->h_triangles.size(); t += 3) clique(&s->h_triangles[t], 3);
+  for (const HostNodePair& c : s->h_nodePair) clique(c.ids, 2);
+  std::sort(e.begin(), e.end());
+  e.erase(std::unique(e.begin(), e.end()), e.end());
+  std::vector<uint32_t> adjPtr(n + 1ull, 0u), adj(e.size());
+  for (size_t k = 0; k < e.size(); ++k) { ++adjPtr[(e[k] >> 32) + 1]; adj[k] = static_cast<uint32_t>(e[k]); }
+  for (uint32_t i = 0; i < n; ++i) adjPtr[i + 1] += adjPtr[i];
+  std::vector<uint64_t>().swap(e);
+  NodeContactArrays& C = s->nc;
+  C = NodeContactArrays{};
+  C.n = n;
+  C.cap = kNcDefaultPartners;
+  if (const char* v = tuning_env("PIES_PD_NODE_CONTACT_PARTNERS")) {
+    const long k = std::strtol(v, nullptr, 10);
+    if (k < 1 || k > 4096) return fail(s, PIES_ERR_INVALID, "PIES_PD_NODE_CONTACT_PARTNERS: 1 .. 4096");
+    C.cap = static_cast<uint32_t>(k);
+  }
+  s->ncRounds = 8;
+  if (const char* v = tuning_env("PIES_PD_NODE_CONTACT_ROUNDS")) {
+    const long k = std::strtol(v, nullptr, 10);
+    if (k >= 1 && k <= static_cast<long>(kNcMaxRounds)) s->ncRounds = static_cast<uint32_t>(k);
+  }
+  s->ncCalm = 0;
+  C.rounds = s->ncRounds;
+  uint32_t *adjPtrD = nullptr, *adjD = nullptr;
+  if (int rc = upload(s, adjPtr, &adjPtrD)) return rc;
+  if (adj.empty()) adj.push_back(0u);  // (a valid pointer; adjPtr says there is nothing)
+  if (int rc = upload(s, adj, &adjD)) return rc;
+  C.adjPtr = adjPtrD;
+  C.adj = adjD;
+  if (int rc = dev_alloc(s, static_cast<size_t>(n) * C.cap, &C.part)) return rc;
+  if (int rc = dev_alloc(s, n, &C.cnt, true)) return rc;
+  for (int b = 0; b < 2; ++b)
+    if (int rc = dev_alloc(s, n, &C.cur[b], true)) return rc;
+  if (int rc = dev_alloc(s, kNcCtlWords, &C.ctl, true)) return rc;
+  C.flags = s->hash.counters + kCounterFlags;
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  s->ncActive = true;
+  return PIES_OK;
+}
+
+// The contacts of the last substep as (a, b) pairs of device ids, a < b, in the order the friction pass ran them (ascending pair key)
+static int nc_download(pies_solver* s, std::vector<uint32_t>* pairs, uint32_t* count) {
+  const NodeContactArrays& C = s->nc;
+  std::vector<uint32_t> cnt(C.n);
+  HIP_TRY(s, hipSetDevice(s->device));
+  HIP_TRY(s, hipMemcpyAsync(cnt.data(), C.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  uint64_t total = 0;
+  for (uint32_t c : cnt) total += c;
+  if (count) *count = static_cast<uint32_t>(total / 2);
+  if (!pairs) return PIES_OK;
+  std::vector<uint32_t> part(static_cast<size_t>(C.n) * C.cap);
+  HIP_TRY(s, hipMemcpyAsync(part.data(), C.part, part.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  std::vector<std::pair<uint64_t, uint64_t>> list;
+  for (uint32_t i = 0; i < C.n; ++i)
+    for (uint32_t k = 0; k < std::min(cnt[i], C.cap); ++k) {
+      const uint32_t j = part[static_cast<size_t>(i) * C.cap + k];
+      if (i < j) list.push_back({pair_mix(i, j), static_cast<uint64_t>(i) << 32 | j});
+    }
+  std::sort(list.begin(), list.end());
+  pairs->resize(2 * list.size());
+  for (size_t k = 0; k < list.size(); ++k) {
+    (*pairs)[2 * k] = static_cast<uint32_t>(list[k].second >> 32);
+    (*pairs)[2 * k + 1] = static_cast<uint32_t>(list[k].second);
+  }
+  return PIES_OK;
+}
+
+int pies_get_node_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, uint32_t* count) {
+  if (!s || !count) return PIES_ERR_INVALID;
+  *count = 0;
+  if (s->device == PIES_DEVICE_NONE || !s->ncActive || s->nd.n == 0) return PIES_OK;
+  std::vector<uint32_t> pairs;
+  if (int rc = nc_download(s, &pairs, nullptr)) return rc;
+  const uint32_t m = static_cast<uint32_t>(pairs.size() / 2);
+  *count = m;
+  if (ids && m) {
+    if (m > capacity) return fail(s, PIES_ERR_INVALID, "pies_get_node_contacts: capacity too small");
+    const bool perm = s->nodeOrder.active();  // a renumbered scene: host ids
+    for (size_t k = 0; k < pairs.size(); ++k) ids[k] = perm && pairs[k] < s->nodeOrder.order.size() ? s->nodeOrder.order[pairs[k]] : pairs[k];
+  }
+  return PIES_OK;
+}
+
 int pies_finalize(pies_solver_t* s) {
   if (!s) return PIES_ERR_INVALID;
   if (s->device == PIES_DEVICE_NONE) {  // host-only handle: plans can be inspected, nothing is uploaded
@@ -406,6 +513,7 @@ int pies_finalize(pies_solver_t* s) {
   }
   const bool isPD = s->opt.solver == PIES_SOLVER_PD;
   const bool collide = s->nodeCollisions && !isPD;
+  const bool ncOn = isPD && s->pdNodeContacts;  // PIES_FLAG_PD_NODE_CONTACTS: the node grid, for the PD contacts
   // The parallel visiting order of the node-node pass needs ranges of at most 2 cells per axis (true for the reference
   // defaults r = 0.5, spacing 2); other scenes run the pass in the reference's own order (one sequential chain, any range
   // up to the reference's 50 cells per axis).
@@ -543,7 +651,7 @@ int pies_finalize(pies_solver_t* s) {
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     std::vector<uint32_t>().swap(s->wave.index);  // the levels (offsets, counts) stay on the host; the items live in HBM
   }
-  if (collide && n) {
+  if ((collide || ncOn) && n) {
     HashArrays& H = s->hash;
     H.n = n;
     uint64_t entries = 0;
@@ -572,7 +680,7 @@ int pies_finalize(pies_solver_t* s) {
       s->sortCalm = 0;
     }
     uint32_t cap = 1024;
-    const uint64_t want = s->collideFast ? 16ull * n : 2ull * H.maxEntries;  // distinct cells <= 8n resp. <= entries: load factor <= 0.5
+    const uint64_t want = (collide ? s->collideFast : fast) ? 16ull * n : 2ull * H.maxEntries;  // distinct cells <= 8n resp. <= entries: load factor <= 0.5
     while (cap < want && cap < (1u << 30)) cap <<= 1;
     H.capacity = cap;
     H.mask = cap - 1;
@@ -596,7 +704,7 @@ int pies_finalize(pies_solver_t* s) {
     if (int rc = dev_alloc(s, kHashCounters, &H.counters, true)) return rc;
     if (int rc = dev_alloc(s, 27ull * n, &H.passList, true)) return rc;
     s->pairs = PairArrays{};
-    {  // pair order: every node's list of partners (in pools), the frontier of the level launches
+    if (collide) {  // pair order: every node's list of partners (in pools), the frontier of the level launches
 
       PairArrays& P = s->pairs;
       P.n = n;
@@ -627,6 +735,8 @@ int pies_finalize(pies_solver_t* s) {
     }
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
+  if (ncOn && n)
+    if (int rc = nc_build(s, n)) return rc;
   if (isPD) {
     std::vector<uint4> id(s->h_volume.size());
     std::vector<float4> q0(id.size()), q1(id.size()), q2(id.size());
@@ -689,6 +799,10 @@ int pies_finalize(pies_solver_t* s) {
       if (s->pd.shape.count)
         if (int rc = dev_alloc(s, 4ull * s->pd.shape.count, &s->snapQuat)) return rc;
     }
+  }
+  if (!s->pcgCeilingSet) {  // node-node contacts stiffen the system (w = 1e5 per contact): a higher ceiling unless the host set one
+    const uint32_t ceiling = s->ncActive ? 256u : 128u;
+    if (s->pcgMaxIters != ceiling) { s->pcgMaxIters = ceiling; s->pcgBudget = std::min(s->pcgBudget, ceiling); }
   }
   if (int rc = capture_graph(s)) return rc;
   s->sceneDirty = false;
@@ -764,6 +878,7 @@ int pies_synchronize(pies_solver_t* s) {
   if (int rc = poll_failure(s)) return rc;  // a loop of pies_tick_async learns here that the simulation failed
   if (int rc = adapt_pair_rounds(s)) return rc;
   if (int rc = adapt_sort_passes(s)) return rc;
+  if (int rc = adapt_nc_rounds(s)) return rc;
   return adapt_pcg_budget(s);
 }
 
@@ -833,6 +948,7 @@ int pies_tick(pies_solver_t* s) {
   if (int rc = poll_failure(s)) return rc;
   if (int rc = adapt_pair_rounds(s)) return rc;
   if (int rc = adapt_sort_passes(s)) return rc;
+  if (int rc = adapt_nc_rounds(s)) return rc;
   return adapt_pcg_budget(s);
 }
 
@@ -1069,6 +1185,12 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_PD_WINDOW_ENTRIES: *out = s->pd.cg.wRows ? s->pdWindowEntries : 0u; break;
     case PIES_PD_WINDOW_HALO: *out = s->pd.cg.wRows ? s->pdWindowHalo : 0u; break;
     case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
+    case PIES_NODE_CONTACTS: {
+      *out = 0;
+      if (s->device != PIES_DEVICE_NONE && s->ncActive && s->nd.n)
+        if (int rc = nc_download(const_cast<pies_solver*>(s), nullptr, out)) return rc;
+      break;
+    }
     default: return PIES_ERR_INVALID;
   }
   return PIES_OK;

@@ -30,6 +30,7 @@ int adapt_pcg_budget(pies_solver* s);
 int adapt_pair_rounds(pies_solver* s);
 uint32_t sort_passes_for(uint32_t keyBits);
 int adapt_sort_passes(pies_solver* s);
+int adapt_nc_rounds(pies_solver* s);
 int poll_failure(pies_solver* s);
 // ---- capi.cpp ----
 void free_device(pies_solver* s);

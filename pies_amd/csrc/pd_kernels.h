@@ -210,8 +210,10 @@ void launch_pd_stabilize(hipStream_t st, const NodeArrays& nd, const PdArrays& p
 // staticFriction = false leaves the floor friction (Solver.cpp:473-484) to the contacts' friction pass (launch_tri_friction), which the
 // reference runs after the point-triangle friction
 void launch_pd_velocity(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, float h, float damping, float gravity,
-                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits = nullptr);
+                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits = nullptr,
+                        const uint32_t* ncCount = nullptr);
 // usedBits (the point-triangle pipeline's bitmap of nodes in contacts): floor friction for the nodes outside it only
+// ncCount (node-node contacts per node, PIES_FLAG_PD_NODE_CONTACTS): nor for the nodes with one (launch_nc_friction applies it)
 
 // workgroups of k_cg_update the device holds at once (0: unknown); the CG kernels' grid stays below it, see grid_barrier
 inline uint32_t window_lds_bytes(const CgArrays& A) { return (A.wLdsSlots + A.wRows) * 16u; }  // the largest window + a chunk's rows of 16 bytes (window_rows)

@@ -604,12 +604,15 @@ __global__ void __launch_bounds__(kBlock) k_pd_stabilize(float4* __restrict__ po
 __global__ void __launch_bounds__(kBlock) k_pd_velocity(const float4* __restrict__ pos, float4* __restrict__ prev,
                                                         float4* __restrict__ vel, const uint32_t* __restrict__ nstatic, uint32_t n,
                                                         float h, float damping, float gravity, float friction,
-                                                        float staticThreshold, bool staticFriction, const uint32_t* __restrict__ usedBits) {
+                                                        float staticThreshold, bool staticFriction, const uint32_t* __restrict__ usedBits,
+                                                        const uint32_t* __restrict__ ncCount) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   // usedBits: the floor friction of the nodes that are in a point-triangle contact comes after the contacts' friction
   // (launch_tri_friction applies it); every other node gets it here
   if (usedBits) staticFriction = ((usedBits[i >> 5] >> (i & 31u)) & 1u) == 0u;
+  // ncCount (PIES_FLAG_PD_NODE_CONTACTS): so does that of the nodes in a node-node contact (launch_nc_friction)
+  if (ncCount && ncCount[i] != 0u) staticFriction = false;
   const float4 p = pos[i];
   const float4 q = prev[i];
   const float k = 1.0f - damping;
@@ -714,10 +717,10 @@ void launch_pd_stabilize(hipStream_t st, const NodeArrays& nd, const PdArrays& p
                      closeSolve ? 1 : 0);
 }
 void launch_pd_velocity(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, float h, float damping, float gravity,
-                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits) {
+                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits, const uint32_t* ncCount) {
   if (nd.n == 0) return;
   hipLaunchKernelGGL(k_pd_velocity, grid_for(nd.n), dim3(kBlock), 0, st, nd.pos, nd.prev, nd.vel, pd.nstatic, nd.n, h, damping, gravity,
-                     friction, staticThreshold, staticFriction, usedBits);
+                     friction, staticThreshold, staticFriction, usedBits, ncCount);
 }
 
 }  // namespace pies

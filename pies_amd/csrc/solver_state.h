@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "pd_kernels.h"
 #include "hash_kernels.h"
+#include "pd_contact_kernels.h"
 #include "pair_kernels.h"
 
 namespace pies {
@@ -203,6 +204,8 @@ struct pies_solver {
   bool tetVolumePaired = false;    // PD: h_volume[k] and h_tet[k] are the same element for every k (fused local step)
   bool triangleCollisions = true;  // PD point-triangle CCD contacts (Solver.cpp:693-797); extension flag to switch off
   bool renumberNodes = false;      // PIES_FLAG_RENUMBER_NODES: pies_finalize may renumber the nodes of a PD scene (node_order.cpp)
+  bool pdNodeContacts = false;     // PIES_FLAG_PD_NODE_CONTACTS: PD detects node-node contacts on the device every substep
+  bool ncActive = false;           // ... and the last pies_finalize built its buffers (a PD scene with nodes)
   pies::NodeOrder nodeOrder;       // the numbering the device holds (decided by the last pies_finalize)
   bool internalIds = false;        // the host containers hold the internal numbering (inside an InternalNumbering scope)
   uint32_t* d_nodeInv = nullptr;   // HBM copy of nodeOrder.inv (nullptr: identity); freed with the device state
@@ -262,6 +265,10 @@ struct pies_solver {
   // ---- node-node collisions (PBD) ----
   pies::HashArrays hash{};
   pies::PairArrays pairs{};  // pair-ordered resolve
+  // ---- node-node contacts of PD (PIES_FLAG_PD_NODE_CONTACTS; the node grid above is built for them) ----
+  pies::NodeContactArrays nc{};
+  uint32_t ncRounds = 8;     // friction round launches captured per substep (adapt_nc_rounds follows the passes)
+  uint32_t ncCalm = 0;       // synchronisations in a row at which fewer would have done
 
   // ---- Projective Dynamics ----
   pies::PdArrays pd{};
@@ -270,6 +277,7 @@ struct pies_solver {
   uint32_t goalSlotBase = 0;  // first fp64 contribution slot of the goal constraints
   float pcgTol = 3.0e-7f;     // relative residual ||r|| / ||b|| per coordinate column
   uint32_t pcgMaxIters = 128; // upper bound of CG iterations per global step (thousands of w = 1e4 contacts need 40+)
+  bool pcgCeilingSet = false; // pies_set_pcg was called: pies_finalize leaves pcgMaxIters alone (else 256 with PD node-node contacts)
   uint32_t pcgBudget = 32;    // iterations currently captured in the graph (adapted to what the solves use)
   uint32_t pcgCalm = 0;       // synchronisations in the current observation window (all solves converged)
   uint32_t pcgWindowMax = 0;  // most CG iterations any solve used in that window

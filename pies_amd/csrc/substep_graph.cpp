@@ -342,6 +342,20 @@ bool pd_single_cg(const pies_solver* s) {
   return s->pdSingleCg && (!s->pd.cg.useCAp || s->pdSingleCgRows) && s->pd.cg.lanesPerRow == 1u;
 }
 
+// PIES_FLAG_PD_NODE_CONTACTS: launches of the node grid's build (launch_hash_build without the group lists)
+static uint32_t nc_hash_launches(const pies_solver* s) { return s->nd.n ? 6u + 3u * s->sortPasses : 0u; }
+// the contacts' friction (Solver.cpp:398-428) in ascending pair key, then their nodes' floor friction; accounted to COLLIDE, one
+// in-situ bracket around the whole pass
+static void enqueue_nc_friction(pies_solver* s, uint32_t* counts) {
+  probe_mark(s, PIES_KERNEL_COLLIDE);
+  NodeContactArrays C = s->nc;
+  C.rounds = s->ncRounds;
+  const uint32_t k = launch_nc_friction(s->stream, C, s->hash, s->nd, s->pd.nstatic, s->pd.tri.nt ? s->pd.tri.usedBits : nullptr, s->opt.friction,
+                                        s->opt.staticFrictionThreshold);
+  probe_mark(s, PIES_KERNEL_COLLIDE);
+  if (counts) counts[PIES_KERNEL_COLLIDE] += k;
+}
+
 // One PD substep as a launch sequence (Solver.cpp:228-485).  `only` >= 0 (profile pass) launches one kernel
 // class of the tetrahedral pipeline; units tallies the work items of the launches made.
 void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
@@ -376,6 +390,17 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     } else if (!levelsInLine) {
       launch_tri_levels(st, pd.tri);
     }
+  }
+  // PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the predicted positions (where Solver.cpp:240 detects), after the
+  // point-triangle detection so that dinv sees both contributions to the diagonal
+  const bool nc = s->ncActive;
+  if (nc) {
+    uint32_t nb = nc_hash_launches(s), nd = 1;  // (nd: the detection's launches)
+    if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->hash, s->nd, s->opt.gridSpacing, s->sortPasses, false); U(s->nd.n); }
+    probe_mark(s, PIES_KERNEL_HASH);
+    if (ON(PIES_KERNEL_COLLIDE)) { nd = launch_nc_detect(st, s->hash, s->nc, s->nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv); U(s->nd.n); }
+    probe_mark(s, PIES_KERNEL_COLLIDE);
+    if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nd; }
   }
   for (uint32_t it = 0; it < s->opt.iterations; ++it) {
     // local step (Solver.cpp:270-308): position constraints project to a constant, uploaded once
@@ -420,12 +445,17 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     // Solver.cpp:266, 310-349.  (When a node's records are a few tile sums, the residual kernel of the one-launch-per-iteration
     // CG evaluates the right-hand side itself.)
     // (contact-heavy variant: a node's contact records are gathered by four lanes in k_pd_rhs, not by the residual kernel's one)
-    const bool single = pd_single_cg(s), fuseRhs = single && only < 0 && pd.rhsLanes == 1 && s->pdFuseRhs && !pd.cg.useCAp;
+    // (node-node contacts: their terms are added to the array k_pd_rhs writes, so the residual kernel does not evaluate it)
+    const bool single = pd_single_cg(s), fuseRhs = single && only < 0 && pd.rhsLanes == 1 && s->pdFuseRhs && !pd.cg.useCAp && !nc;
     if (!fuseRhs) {
       if (ON(PIES_KERNEL_PD_RHS)) { launch_pd_rhs(st, s->nd, pd); U(s->nd.n); }
       C(PIES_KERNEL_PD_RHS);
     } else if (counts) {
       counts[PIES_KERNEL_PD_RHS] += 1;  // (the residual kernel that evaluates the right-hand side is counted - and bracketed - as this class)
+    }
+    if (nc) {  // the contacts' local step (CollisionConstraint.cpp:10-41, 49-65): w * projected, in list order
+      if (ON(PIES_KERNEL_COLLIDE)) { launch_nc_rhs(st, s->nc, s->nd, pd.rhs); U(s->nd.n); }
+      C(PIES_KERNEL_COLLIDE);
     }
     const int overflow = s->pcgOverflow ? (int)(s->pcgMaxIters > s->pcgBudget ? s->pcgMaxIters - s->pcgBudget : 0u) : 0;
     const bool lastSolve = it + 1 == s->opt.iterations && !statsInStabilize;
@@ -459,18 +489,23 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     if (s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
     // velocities, then the contacts' friction (:431-471), then the floor friction (:473-484).  The floor friction of a node that is
     // in no contact does not wait for the contacts: the velocity kernel applies it; the contacts' pass ends with that of its own nodes
-    launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits);
+    // (the nodes of node-node contacts get their floor friction after their contacts' friction as well)
+    launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits,
+                       nc ? s->nc.cnt : nullptr);
     if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
                                                s->opt.staticFrictionThreshold);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
+    if (nc && only < 0) enqueue_nc_friction(s, counts);
     launch_tri_friction(st, pd.tri, s->nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
   } else {
     if (only < 0 && s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));  // the floor snap is idempotent
     if (ON(PIES_KERNEL_PD_VELOCITY)) {
-      launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true);
+      launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true, nullptr,
+                         nc ? s->nc.cnt : nullptr);
       U(s->nd.n);
     }
     if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
                                                s->opt.staticFrictionThreshold);
+    if (nc && only < 0) enqueue_nc_friction(s, counts);
   }
   C(PIES_KERNEL_PD_VELOCITY);
 }
@@ -680,7 +715,7 @@ int adapt_pair_rounds(pies_solver* s) {
 uint32_t sort_passes_for(uint32_t keyBits) { return std::max(1u, std::min(6u, (keyBits + 5u + 10u) / 11u)); }
 int adapt_sort_passes(pies_solver* s) {
   if (!s->hash.counters || s->sceneDirty || under_profiler()) return PIES_OK;
-  if (s->opt.solver != PIES_SOLVER_PBD || !s->nodeCollisions) return PIES_OK;
+  if ((s->opt.solver != PIES_SOLVER_PBD || !s->nodeCollisions) && !s->ncActive) return PIES_OK;
   int box[6];
   HIP_TRY(s, hipMemcpyAsync(box, s->hash.counters + kCounterBoxMin, sizeof(box), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -702,15 +737,50 @@ int adapt_sort_passes(pies_solver* s) {
   return PIES_OK;
 }
 
+// PIES_FLAG_PD_NODE_CONTACTS: friction rounds captured per substep.  At host synchronisations they follow the deepest pass seen
+// (two more than it needed; one when no pass had a contact), growing at once and shrinking after 8 calm synchronisations.  A pass
+// deeper than captured is finished by the single-workgroup tail kernel: slow, never wrong.
+int adapt_nc_rounds(pies_solver* s) {
+  if (!s->ncActive || !s->nc.ctl || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
+  if (tuning_env("PIES_PD_NODE_CONTACT_ROUNDS")) return PIES_OK;  // pinned at finalize
+  uint32_t deepest = 0;
+  HIP_TRY(s, hipMemcpyAsync(&deepest, s->nc.ctl + kNcDeepest, sizeof(deepest), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  if (deepest == 0) return PIES_OK;  // no pass since the last look
+  HIP_TRY(s, hipMemsetAsync(s->nc.ctl + kNcDeepest, 0, sizeof(uint32_t), s->stream));
+  const uint32_t depth = deepest - 1u;
+  const uint32_t want = depth == 0 ? 1u : std::min(kNcMaxRounds, depth + 2u);
+  uint32_t rounds = s->ncRounds;
+  if (depth > rounds) { rounds = want; s->ncCalm = 0; }
+  else if (want < rounds) { if (++s->ncCalm >= 8) { rounds = want; s->ncCalm = 0; } }
+  else s->ncCalm = 0;
+  if (rounds != s->ncRounds) {
+    s->ncRounds = rounds;
+    return capture_graph(s);
+  }
+  return PIES_OK;
+}
+
 int poll_failure(pies_solver* s) {
   uint32_t* flagWord = s->hash.counters ? s->hash.counters + 3 : s->pd.tri.counters ? s->pd.tri.counters + 3 : nullptr;
   if (s->simFailed || !flagWord || s->device == PIES_DEVICE_NONE) return PIES_OK;
   uint32_t flag = 0;
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipMemcpyAsync(&flag, flagWord, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
+  if (s->ncActive && s->pd.tri.counters) {  // PD with node-node contacts: the point-triangle pipeline's word as well
+    uint32_t triFlag = 0;
+    HIP_TRY(s, hipMemcpyAsync(&triFlag, s->pd.tri.counters + 3, sizeof(triFlag), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    flag |= triFlag;
+  }
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (flag) {  // like the reference's latch (Solver.cpp:741-755, 853-856): tick becomes a no-op
     s->simFailed = true;
+    if (flag & kNcOverflowFlag) {
+      s->error = "PD node-node contact list overflow: a node has more contact partners than PIES_PD_NODE_CONTACT_PARTNERS (" +
+                 std::to_string(s->nc.cap) + ")";
+      return PIES_OK;
+    }
     s->error = flag & 2    ? "node-node collision grid overflow (more cells or entries than reserved)"
                : flag & 4  ? "runaway pile-up: a node-node pass that only the sequential loop can run (more than 1024 nodes within reach of one node, or more than 2048 in a cell under the group order) would cost more candidate tests than PIES_FALLBACK_VISITS allows (1e9: about a minute)"
                : flag & 16 ? "more than 1000 triangles in one grid cell, or more than 1000 cells in a triangle's search range (the reference's safety latches, Solver.cpp:741-755)"
