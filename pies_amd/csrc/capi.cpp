@@ -46,6 +46,7 @@ void free_device(pies_solver* s) {
   s->d_tc_ids = nullptr; s->d_tc_q0 = s->d_tc_q1 = s->d_tc_q2 = nullptr;
   s->d_bc_ids = nullptr; s->d_bc_aw = nullptr;
   s->d_np_ids = nullptr;
+  s->d_np_bits = nullptr; s->d_np_nodes = nullptr; s->npNodes = 0;
   s->d_vc_ids = nullptr; s->d_vc_q0 = s->d_vc_q1 = s->d_vc_q2 = nullptr;
   s->pd = PdArrays{};
   s->hash = HashArrays{};
@@ -609,6 +610,18 @@ int pies_finalize(pies_solver_t* s) {
     std::vector<uint2> id(s->h_nodePair.size());
     for (size_t k = 0; k < id.size(); ++k) id[k] = make_uint2(s->h_nodePair[k].ids[0], s->h_nodePair[k].ids[1]);
     if (int rc = upload(s, id, &s->d_np_ids)) return rc;
+    // the pairs' nodes (ids in device numbering here): the velocity kernel leaves their floor friction to
+    // launch_pd_node_pair_floor_friction, which runs after the pairs' friction (Solver.cpp:398-428 before :473-484)
+    const uint32_t n = s->nodeCount();
+    std::vector<uint32_t> bits((n + 31u) / 32u, 0u), nodes;
+    for (const uint2& p : id)
+      for (uint32_t i : {p.x, p.y})
+        if (i < n) bits[i >> 5] |= 1u << (i & 31u);
+    for (uint32_t i = 0; i < n; ++i)
+      if ((bits[i >> 5] >> (i & 31u)) & 1u) nodes.push_back(i);
+    if (int rc = upload(s, bits, &s->d_np_bits)) return rc;
+    if (int rc = upload(s, nodes, &s->d_np_nodes)) return rc;
+    s->npNodes = (uint32_t)nodes.size();
   }
   if (s->layer.active && !isPD) {
     const LayerPlan& L = s->layer;

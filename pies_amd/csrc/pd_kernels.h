@@ -165,8 +165,11 @@ void launch_pd_local_distance(hipStream_t st, const float4* pos, const uint2* id
 // the node-pair extension container (CollisionConstraint.cpp:7-65; Solver.cpp:398-428)
 constexpr float kNodePairW = 100000.0f;  // Include/Pies/CollisionConstraint.h:14
 void launch_pd_local_node_pair(hipStream_t st, const float4* pos, const float* radius, const uint2* ids, Vec3f* contrib, uint32_t count);
+// then the floor friction of the pairs' nodes (nodes: ascending, once each) that are in no point-triangle contact (usedBits) and in no
+// node-node contact (ncCount): the later passes of those end with it; nullptr: none
 void launch_pd_node_pair_friction(hipStream_t st, const float4* pos, float4* vel, const float* radius, const uint2* ids, uint32_t count,
-                                  float friction, float staticThreshold);
+                                  float friction, float staticThreshold, const uint32_t* nodes, uint32_t nodeCount, const uint32_t* nstatic,
+                                  const uint32_t* usedBits, const uint32_t* ncCount);
 void launch_pd_local_tet(hipStream_t st, bool volume, const float4* pos, const uint4* ids, const float4* q0, const float4* q1,
                          const float4* q2, Vec3f* contrib, uint32_t count);
 // strain + volume constraints over identical elements (same ids, same Qinv), fused
@@ -211,9 +214,10 @@ void launch_pd_stabilize(hipStream_t st, const NodeArrays& nd, const PdArrays& p
 // reference runs after the point-triangle friction
 void launch_pd_velocity(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, float h, float damping, float gravity,
                         float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits = nullptr,
-                        const uint32_t* ncCount = nullptr);
+                        const uint32_t* ncCount = nullptr, const uint32_t* npBits = nullptr);
 // usedBits (the point-triangle pipeline's bitmap of nodes in contacts): floor friction for the nodes outside it only
 // ncCount (node-node contacts per node, PIES_FLAG_PD_NODE_CONTACTS): nor for the nodes with one (launch_nc_friction applies it)
+// npBits (bitmap of the listed node pairs' nodes): nor for those (launch_pd_node_pair_friction applies it)
 
 // workgroups of k_cg_update the device holds at once (0: unknown); the CG kernels' grid stays below it, see grid_barrier
 inline uint32_t window_lds_bytes(const CgArrays& A) { return (A.wLdsSlots + A.wRows) * 16u; }  // the largest window + a chunk's rows of 16 bytes (window_rows)

@@ -138,6 +138,31 @@ __global__ void k_pd_node_pair_friction(const float4* __restrict__ pos, float4* 
     vel[id.y] = vb;
   }
 }
+// The floor friction (Solver.cpp:473-484) of the listed pairs' nodes, once per node after the pairs' friction above: k_pd_velocity
+// leaves them out (npBits).  A node in a point-triangle contact (usedBits) gets it from launch_tri_friction, one in a node-node
+// contact (ncCount) from launch_nc_friction: both run later and end with it.
+__global__ void __launch_bounds__(kBlock) k_pd_node_pair_floor_friction(const uint32_t* __restrict__ nodes, uint32_t count, float4* __restrict__ vel,
+                                                                        const uint32_t* __restrict__ nstatic, const uint32_t* __restrict__ usedBits,
+                                                                        const uint32_t* __restrict__ ncCount, float friction, float staticThreshold) {
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= count) return;
+  const uint32_t i = nodes[k];
+  if (usedBits && ((usedBits[i >> 5] >> (i & 31u)) & 1u)) return;
+  if (ncCount && ncCount[i] != 0u) return;
+  const uint32_t ns = nstatic[i];
+  if (ns == 0u) return;
+  const float4 v = vel[i];
+  float vx = v.x, vy = v.y, vz = v.z;
+  for (uint32_t c = 0; c < ns; ++c) {  // (k_pd_velocity's loop)
+    const float px = vx, pz = vz;
+    float fr = friction;
+    if (sqrtf(px * px + 0.0f * 0.0f + pz * pz) < staticThreshold) fr = 1.0f;
+    vx += -fr * px;
+    vy += -fr * 0.0f;
+    vz += -fr * pz;
+  }
+  vel[i] = make_float4(vx, vy, vz, v.w);
+}
 
 // Constraints.cpp:186-203.  The reference divides the three components by `den`; here one reciprocal (a correctly rounded
 // division) and three products - the last bit of D may differ, PD parity is by tolerance, and the
@@ -605,7 +630,7 @@ __global__ void __launch_bounds__(kBlock) k_pd_velocity(const float4* __restrict
                                                         float4* __restrict__ vel, const uint32_t* __restrict__ nstatic, uint32_t n,
                                                         float h, float damping, float gravity, float friction,
                                                         float staticThreshold, bool staticFriction, const uint32_t* __restrict__ usedBits,
-                                                        const uint32_t* __restrict__ ncCount) {
+                                                        const uint32_t* __restrict__ ncCount, const uint32_t* __restrict__ npBits) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   // usedBits: the floor friction of the nodes that are in a point-triangle contact comes after the contacts' friction
@@ -613,6 +638,8 @@ __global__ void __launch_bounds__(kBlock) k_pd_velocity(const float4* __restrict
   if (usedBits) staticFriction = ((usedBits[i >> 5] >> (i & 31u)) & 1u) == 0u;
   // ncCount (PIES_FLAG_PD_NODE_CONTACTS): so does that of the nodes in a node-node contact (launch_nc_friction)
   if (ncCount && ncCount[i] != 0u) staticFriction = false;
+  // npBits: and that of the listed node pairs' nodes (launch_pd_node_pair_friction, after the pairs' friction)
+  if (npBits && ((npBits[i >> 5] >> (i & 31u)) & 1u)) staticFriction = false;
   const float4 p = pos[i];
   const float4 q = prev[i];
   const float k = 1.0f - damping;
@@ -647,9 +674,13 @@ void launch_pd_local_node_pair(hipStream_t st, const float4* pos, const float* r
   hipLaunchKernelGGL(k_pd_local_node_pair, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, pos, radius, ids, contrib, count);
 }
 void launch_pd_node_pair_friction(hipStream_t st, const float4* pos, float4* vel, const float* radius, const uint2* ids, uint32_t count,
-                                  float friction, float staticThreshold) {
+                                  float friction, float staticThreshold, const uint32_t* nodes, uint32_t nodeCount, const uint32_t* nstatic,
+                                  const uint32_t* usedBits, const uint32_t* ncCount) {
   if (count == 0) return;
   hipLaunchKernelGGL(k_pd_node_pair_friction, dim3(1), dim3(64), 0, st, pos, vel, radius, ids, count, friction, staticThreshold);
+  if (nodeCount == 0) return;
+  hipLaunchKernelGGL(k_pd_node_pair_floor_friction, grid_for(nodeCount), dim3(kBlock), 0, st, nodes, nodeCount, vel, nstatic, usedBits, ncCount,
+                     friction, staticThreshold);
 }
 void launch_pd_local_distance(hipStream_t st, const float4* pos, const uint2* ids, const float2* rw, Vec3f* contrib, uint32_t count) {
   if (count == 0) return;
@@ -717,10 +748,11 @@ void launch_pd_stabilize(hipStream_t st, const NodeArrays& nd, const PdArrays& p
                      closeSolve ? 1 : 0);
 }
 void launch_pd_velocity(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, float h, float damping, float gravity,
-                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits, const uint32_t* ncCount) {
+                        float friction, float staticThreshold, bool staticFriction, const uint32_t* usedBits, const uint32_t* ncCount,
+                        const uint32_t* npBits) {
   if (nd.n == 0) return;
   hipLaunchKernelGGL(k_pd_velocity, grid_for(nd.n), dim3(kBlock), 0, st, nd.pos, nd.prev, nd.vel, pd.nstatic, nd.n, h, damping, gravity,
-                     friction, staticThreshold, staticFriction, usedBits, ncCount);
+                     friction, staticThreshold, staticFriction, usedBits, ncCount, npBits);
 }
 
 }  // namespace pies

@@ -259,6 +259,9 @@ struct pies_solver {
   uint4* d_bc_ids = nullptr;
   float2* d_bc_aw = nullptr;
   uint2* d_np_ids = nullptr;  // node-pair extension (PD)
+  uint32_t* d_np_bits = nullptr;   // bitmap over the nodes (device numbering): in a listed pair (floor friction after the pairs' friction)
+  uint32_t* d_np_nodes = nullptr;  // those nodes, ascending, once each
+  uint32_t npNodes = 0;
   uint4* d_vc_ids = nullptr;  // volume constraints (PD only), host order
   float4 *d_vc_q0 = nullptr, *d_vc_q1 = nullptr, *d_vc_q2 = nullptr;
 

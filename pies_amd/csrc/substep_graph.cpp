@@ -489,22 +489,24 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     if (s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
     // velocities, then the contacts' friction (:431-471), then the floor friction (:473-484).  The floor friction of a node that is
     // in no contact does not wait for the contacts: the velocity kernel applies it; the contacts' pass ends with that of its own nodes
-    // (the nodes of node-node contacts get their floor friction after their contacts' friction as well)
+    // (the nodes of node-node contacts and of listed node pairs get their floor friction after their pairs' friction as well)
     launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits,
-                       nc ? s->nc.cnt : nullptr);
+                       nc ? s->nc.cnt : nullptr, s->d_np_bits);
     if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
+                                               s->opt.staticFrictionThreshold, s->d_np_nodes, s->npNodes, pd.nstatic, pd.tri.usedBits,
+                                               nc ? s->nc.cnt : nullptr);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
     if (nc && only < 0) enqueue_nc_friction(s, counts);
     launch_tri_friction(st, pd.tri, s->nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
   } else {
     if (only < 0 && s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));  // the floor snap is idempotent
     if (ON(PIES_KERNEL_PD_VELOCITY)) {
       launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true, nullptr,
-                         nc ? s->nc.cnt : nullptr);
+                         nc ? s->nc.cnt : nullptr, s->d_np_bits);
       U(s->nd.n);
     }
     if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold);
+                                               s->opt.staticFrictionThreshold, s->d_np_nodes, s->npNodes, pd.nstatic, nullptr,
+                                               nc ? s->nc.cnt : nullptr);
     if (nc && only < 0) enqueue_nc_friction(s, counts);
   }
   C(PIES_KERNEL_PD_VELOCITY);
