@@ -93,6 +93,8 @@ public:
       _vertices = std::move(rhs._vertices);
       _lines = std::move(rhs._lines);
       _triangles = std::move(rhs._triangles);
+      _skinVertices = std::move(rhs._skinVertices);
+      _skinNormals = std::move(rhs._skinNormals);
       _frames[0] = rhs._frames[0];
       _frames[1] = rhs._frames[1];
       renderStateDirty = rhs.renderStateDirty;
@@ -137,6 +139,12 @@ public:
     _ck(pies_export_acquire(_handle(), f, &p, &n));
     const size_t m = n < _vertices.size() ? n : _vertices.size();
     for (size_t i = 0; i < m; ++i) _vertices[i].position = glm::vec3(p[4 * i], p[4 * i + 1], p[4 * i + 2]);
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) {  // the frame's skins, from its pinned buffers
+      const float *x = nullptr, *nr = nullptr;
+      uint32_t nv = 0;
+      _ck(pies_export_acquire_skin(_handle(), f, k, &x, &nr, &nv));
+      _copySkin(k, x, nr, nv);
+    }
     _ck(pies_export_release(_handle(), f));
   }
 
@@ -144,9 +152,14 @@ public:
   const std::vector<uint32_t>& getLines() const { return _lines; }
   const std::vector<Triangle>& getTriangles() const { return _triangles; }
   const SolverOptions& getOptions() const { return _options; }
+  // extension (see addSkin): deformed vertices and vertex normals of skin `skin`, refreshed by tick* / endTick like getVertices()
+  const std::vector<glm::vec3>& getSkinVertices(uint32_t skin) const { return _skinVertices.at(skin); }
+  const std::vector<glm::vec3>& getSkinNormals(uint32_t skin) const { return _skinNormals.at(skin); }
 
   void clear() {
     if (_h) _ck(pies_clear(_h));
+    _skinVertices.clear();
+    _skinNormals.clear();
     _vertices.clear();
     _lines.clear();
     _triangles.clear();
@@ -234,6 +247,27 @@ public:
     }
     _addTetMesh(vertices, tetIndices, surface, initialVelocity, density, strainStiffness, minStrain, maxStrain, volumeStiffness,
                 compression, stretching);
+  }
+  // Extension (pies_add_skin in pies_hip.h): an embedded surface mesh for hosts that tetrahedralise offline and draw a finer
+  // surface than the simulation's own boundary - what addTriMeshVolume's "input vertices are the first nodes" gives a reference
+  // host.  Every vertex is bound once to one of the listed elements (`tetIndices`: GLOBAL node ids, four per element, e.g. the
+  // ids an addTetMeshVolume call produced) with barycentric weights; a vertex may lie up to `maxDistance` outside the elements'
+  // boxes.  `triIndices` (three per triangle, into `vertices`; may be empty) serve the normals.  The deformed vertices and
+  // normals are evaluated on the device every tick.  Returns the skin's id; throws when a vertex cannot be bound.  getSkin*
+  // hold the bound rest state afterwards (evaluated on the device: the scene is finalized by this call).
+  uint32_t addSkin(const std::vector<glm::vec3>& vertices, const std::vector<uint32_t>& triIndices, const std::vector<uint32_t>& tetIndices,
+                   float maxDistance = 0.0f) {
+    std::vector<float> p = _flatten(vertices);
+    uint32_t id = 0;
+    _ck(pies_add_skin(_handle(), static_cast<uint32_t>(vertices.size()), p.data(), static_cast<uint32_t>(triIndices.size() / 3),
+                      triIndices.empty() ? nullptr : triIndices.data(), static_cast<uint32_t>(tetIndices.size() / 4), tetIndices.data(),
+                      maxDistance, &id));
+    _skinVertices.resize(id + 1);
+    _skinNormals.resize(id + 1);
+    _skinVertices[id].resize(vertices.size());
+    _skinNormals[id].resize(vertices.size());
+    _refreshSkin(id);
+    return id;
   }
   void addFixedRegions(const std::vector<glm::mat4>& regionMatrices, float w) {
     std::vector<float> m = _flattenMats(regionMatrices);
@@ -355,6 +389,20 @@ private:
     _ck(pies_read_positions_strided(_handle(), &_vertices[0].position, sizeof(Vertex), n));
   }
 
+  void _copySkin(uint32_t k, const float* x, const float* nr, uint32_t nv) {
+    const size_t m = nv < _skinVertices[k].size() ? nv : _skinVertices[k].size();
+    for (size_t i = 0; i < m; ++i) {
+      _skinVertices[k][i] = glm::vec3(x[3 * i], x[3 * i + 1], x[3 * i + 2]);
+      _skinNormals[k][i] = glm::vec3(nr[3 * i], nr[3 * i + 1], nr[3 * i + 2]);
+    }
+  }
+  void _refreshSkin(uint32_t k) {
+    const uint32_t nv = static_cast<uint32_t>(_skinVertices[k].size());
+    _skinScratch.resize(6 * size_t(nv));
+    _ck(pies_read_skin(_handle(), k, _skinScratch.data(), _skinScratch.data() + 3 * size_t(nv), nv));
+    _copySkin(k, _skinScratch.data(), _skinScratch.data() + 3 * size_t(nv), nv);
+  }
+
   // opens the device handle on first use
   pies_solver_t* _handle() {
     if (!_h) {
@@ -383,6 +431,7 @@ private:
     _pushState(solver);
     _ck(pies_tick(_handle()));
     _refreshPositions();
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
   }
 
   pies_solver_t* _h = nullptr;
@@ -393,6 +442,8 @@ private:
   std::vector<Vertex> _vertices;
   std::vector<uint32_t> _lines;
   std::vector<Triangle> _triangles;
+  std::vector<std::vector<glm::vec3>> _skinVertices, _skinNormals;  // per skin (addSkin)
+  std::vector<float> _skinScratch;
   uint64_t _frames[2] = {0, 0};  // ticks begun and not yet ended (beginTick / endTick)
 };
 }  // namespace Pies

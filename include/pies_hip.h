@@ -85,8 +85,10 @@ enum {
                                   pies_add_node_pair_constraints */
   PIES_NODES_RENUMBERED = 19,  /* pies_count only: 1 when the device holds the nodes in another numbering than the host's
                                   (PIES_FLAG_RENUMBER_NODES, decided by pies_finalize), else 0 */
-  PIES_NODE_CONTACTS = 20      /* pies_count only: node-node contacts of the last PD substep (PIES_FLAG_PD_NODE_CONTACTS; synchronises),
+  PIES_NODE_CONTACTS = 20,     /* pies_count only: node-node contacts of the last PD substep (PIES_FLAG_PD_NODE_CONTACTS; synchronises),
                                   0 before the first tick and without the flag */
+  PIES_SKINS = 21,             /* pies_count only: embedded surface meshes (pies_add_skin), an EXTENSION */
+  PIES_SKIN_VERTICES = 22      /* pies_count only: their vertices, over all skins */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.
@@ -230,6 +232,30 @@ int pies_create_box(pies_solver_t* s, uint32_t W, uint32_t H, uint32_t D, const 
 int pies_create_sheet(pies_solver_t* s, uint32_t W, uint32_t H, const float translation[3], float scale, float mass, float w);
 int pies_create_bend_sheet(pies_solver_t* s, uint32_t W, uint32_t H, const float translation[3], float scale, float w);
 
+/* EXTENSION (the reference draws the simulation nodes themselves; Include/Pies/Tetrahedron.h and Solver.h's _spatialHashTets /
+ * TetCompRange are the unfinished element grid this stands in for): an embedded surface mesh, a SKIN.  Each of the n_vertices
+ * render vertices (positions: n x 3) is bound once, here, to one of the n_tets listed tetrahedra (tet_node_ids: n x 4 global node
+ * ids; they need not be constraints of the scene) with barycentric weights; after any tick pies_read_skin /
+ * pies_export_acquire_skin deliver the deformed vertices and their normals, evaluated on the device.  tri_ids (n_triangles x 3
+ * indices into THIS skin's vertices; NULL with 0) only serve the normals.
+ * The binding rule, in fp32 on the node positions at the time of the call: the candidates of vertex v are the listed tetrahedra
+ * whose axis-aligned box, grown by max_distance on every side, contains v (bounds included); a tetrahedron whose
+ * det [p1 - p0, p2 - p0, p3 - p0] is below FLT_MIN in magnitude, or whose inverse is not finite, is never a candidate.  The
+ * barycentric coordinates are w_k = det(with column k replaced by v - p0) / det for k = 1, 2, 3 and w0 = 1 - (w1 + w2 + w3);
+ * the candidate with the largest min(w0, w1, w2, w3) wins, the lowest index on a tie.  A vertex without a candidate fails the
+ * call with PIES_ERR_INVALID (pies_last_error names the vertex) and nothing is added; so do a node id out of range, a triangle
+ * index >= n_vertices, n_vertices == 0 and a negative or non-finite max_distance.  Candidates are found through a uniform grid
+ * over the element boxes (host side, like all scene construction).
+ * The binding is kept in host numbering and survives pies_finalize, later add* / create* calls (node ids never shift),
+ * pies_set_solver and PIES_FLAG_RENUMBER_NODES; pies_clear drops every skin.  skin_id (may be NULL) receives 0, 1, ... */
+int pies_add_skin(pies_solver_t* s, uint32_t n_vertices, const float* positions, uint32_t n_triangles, const uint32_t* tri_ids,
+                  uint32_t n_tets, const uint32_t* tet_node_ids, float max_distance, uint32_t* skin_id);
+/* The stored binding of a skin, per vertex: tet = index into the tetrahedra given, node_ids = its four nodes (host ids), weights =
+ * (w0, w1, w2, w3) with w0 = 1 - (w1 + w2 + w3) exactly as the device evaluates it.  Any array may be NULL; n receives the
+ * vertex count, capacity is in vertices.  Works on PIES_DEVICE_NONE handles. */
+int pies_get_skin_binding(const pies_solver_t* s, uint32_t skin, uint32_t* tet, uint32_t* node_ids, float* weights, uint32_t capacity,
+                          uint32_t* n);
+
 /* ---- configuration -------------------------------------------------------------------------- */
 int pies_set_flag(pies_solver_t* s, int flag, int value);
 /* Solver::tickPBD / Solver::tickPD (Solver.h:62-63) run the named solver whatever SolverOptions::solver says: this switches
@@ -278,6 +304,19 @@ int pies_synchronize(pies_solver_t* s);
 int pies_tick_begin(pies_solver_t* s, uint64_t* frame);
 int pies_export_acquire(pies_solver_t* s, uint64_t frame, const float** pos4, uint32_t* n);
 int pies_export_release(pies_solver_t* s, uint64_t frame);
+/* Skins (pies_add_skin).  Vertex i of a skin is x_i = p0 + w1 (p1 - p0) + w2 (p2 - p0) + w3 (p3 - p0), summed left to right in
+ * fp32 without fused multiply-adds; its normal is normalize(sum over the triangles that name i, in ascending triangle index, of
+ * cross(x_b - x_a, x_c - x_a)) = sum / sqrt(|sum|^2), and (0, 0, 0) when |sum|^2 is 0 or not finite (a vertex no triangle names,
+ * a skin without triangles).  Nothing is summed with atomics: two runs agree bit for bit.  The two kernels are launched outside
+ * the captured substep; a scene without skins launches, allocates and copies nothing for them.
+ * pies_read_skin evaluates skin `skin` from the device's current node positions on the solver's stream, synchronises and copies
+ * out (positions: n x 3; normals: n x 3, may be NULL; n must be the skin's vertex count).
+ * pies_export_acquire_skin: pies_tick_begin evaluates every skin behind the frame's position copy and the frame's copy stream
+ * carries the result into per-frame pinned buffers; this waits for frame `frame` like pies_export_acquire and returns pointers
+ * into them (n x 3 each; normals may be NULL), valid exactly as long as that frame's pos4 pointer.  A skin added after the frame
+ * was begun is not part of it (PIES_ERR_STATE). */
+int pies_read_skin(pies_solver_t* s, uint32_t skin, float* positions, float* normals, uint32_t n);
+int pies_export_acquire_skin(pies_solver_t* s, uint64_t frame, uint32_t skin, const float** positions, const float** normals, uint32_t* n);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:

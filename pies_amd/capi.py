@@ -38,6 +38,7 @@ PD_WINDOW_ENTRIES, PD_WINDOW_HALO = 16, 17
 NODE_PAIRS = 18  # the node-node CollisionConstraint extension container (PD)
 NODES_RENUMBERED = 19  # pies_count: 1 when the device holds the nodes in another numbering (FLAG_RENUMBER_NODES)
 NODE_CONTACTS = 20  # pies_count: node-node contacts of the last PD substep (FLAG_PD_NODE_CONTACTS)
+SKINS, SKIN_VERTICES = 21, 22  # pies_count: embedded surface meshes (pies_add_skin) and their vertices over all skins
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
 SYMBOLS = [
@@ -56,6 +57,7 @@ SYMBOLS = [
     "pies_collision_stats", "pies_get_collision_health", "pies_set_collision_rounds", "pies_set_solver", "pies_debug_pair_state", "pies_set_tuning",
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
+    "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
 ]
 
 
@@ -162,6 +164,10 @@ def load():
         "pies_profile_in_situ": [vp, i32, u32, pu, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
     }
     sig["pies_set_tuning"] = [C.c_char_p, C.c_char_p]
+    sig["pies_add_skin"] = [vp, u32, pf, u32, pu, u32, pu, f32, pu]
+    sig["pies_get_skin_binding"] = [vp, u32, pu, pu, pf, u32, pu]
+    sig["pies_read_skin"] = [vp, u32, pf, pf, u32]
+    sig["pies_export_acquire_skin"] = [vp, C.c_uint64, u32, C.POINTER(pf), C.POINTER(pf), pu]
     sig["pies_get_pd_tile_plan"] = [vp, pu, pu, pu, pu, pu, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), u32]
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -329,6 +335,47 @@ class Solver:
     def create_bend_sheet(self, W, H, translation=(0, 0, 0), scale=1.0, w=1.0):
         t = _f32(translation)
         self._ck(self._L.pies_create_bend_sheet(self._h, W, H, _pf(t), scale, w))
+
+    def add_skin(self, vertices, tets, triangles=None, max_distance=0.0):
+        """pies_add_skin: binds the render vertices (n x 3) to the listed tetrahedra (m x 4 global node ids), each vertex to one
+        element with barycentric weights; `triangles` (k x 3 indices into the vertices, or None) serve the normals.  Returns the
+        skin's id."""
+        v = _f32(vertices).reshape(-1, 3)
+        t = _u32(tets).reshape(-1, 4)
+        tri = None if triangles is None else _u32(triangles).reshape(-1, 3)
+        k = C.c_uint32()
+        self._ck(self._L.pies_add_skin(self._h, len(v), _pf(v), 0 if tri is None else len(tri), None if tri is None else _pu(tri),
+                                       len(t), _pu(t), max_distance, C.byref(k)))
+        return k.value
+
+    def skin_binding(self, skin):
+        """pies_get_skin_binding: (tet, node_ids, weights) per vertex - the index into the tetrahedra given, its four nodes (host
+        ids) and (w0, w1, w2, w3) as stored (w0 = 1 - (w1 + w2 + w3))."""
+        n = C.c_uint32()
+        if self._L.pies_get_skin_binding(self._h, skin, None, None, None, 0, C.byref(n)) != OK:
+            raise PiesError("pies_get_skin_binding: no skin %d" % skin)
+        tet, ids, w = np.empty(n.value, np.uint32), np.empty((n.value, 4), np.uint32), np.empty((n.value, 4), np.float32)
+        if self._L.pies_get_skin_binding(self._h, skin, _pu(tet), _pu(ids), _pf(w), n.value, C.byref(n)) != OK:
+            raise PiesError("pies_get_skin_binding failed")
+        return tet, ids, w
+
+    def read_skin(self, skin, normals=True):
+        """pies_read_skin: the skin evaluated from the device's current node positions; (positions, normals) as (n, 3) arrays,
+        or positions alone with normals=False (the normals are then not computed)."""
+        n = C.c_uint32()
+        if self._L.pies_get_skin_binding(self._h, skin, None, None, None, 0, C.byref(n)) != OK:
+            raise PiesError("pies_read_skin: no skin %d" % skin)
+        x = np.empty((n.value, 3), np.float32)
+        nr = np.empty((n.value, 3), np.float32) if normals else None
+        self._ck(self._L.pies_read_skin(self._h, skin, _pf(x), None if nr is None else _pf(nr), n.value))
+        return (x, nr) if normals else x
+
+    def export_acquire_skin(self, frame, skin):
+        """pies_export_acquire_skin: (positions, normals) of `skin` in frame `frame` as (n, 3) float32 views of the frame's
+        pinned buffers, valid until export_release(frame) like export_acquire's view."""
+        p, q, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_uint32()
+        self._ck(self._L.pies_export_acquire_skin(self._h, frame, skin, C.byref(p), C.byref(q), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value, 3)), np.ctypeslib.as_array(q, shape=(n.value, 3))
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

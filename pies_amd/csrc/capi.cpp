@@ -36,6 +36,7 @@ bool tet_volume_pairs(const pies_solver* s) {
 
 void free_device(pies_solver* s) {
   destroy_graph(s);
+  skin_free_device(s);
   for (void* p : s->allocations) (void)hipFree(p);
   s->allocations.clear();
   s->nd = NodeArrays{nullptr, nullptr, nullptr, nullptr, 0};
@@ -211,7 +212,10 @@ int pies_destroy(pies_solver_t* s) {
   if (s->copyStream) (void)hipStreamSynchronize(s->copyStream);
   free_device(s);
   if (s->h_stage) (void)hipHostFree(s->h_stage);
+  if (s->h_skinStage) (void)hipHostFree(s->h_skinStage);
+  if (s->d_skinExport) (void)hipFree(s->d_skinExport);
   for (int b = 0; b < 2; ++b) {
+    if (s->h_skinExport[b]) (void)hipHostFree(s->h_skinExport[b]);
     if (s->h_export[b]) (void)hipHostFree(s->h_export[b]);
     if (s->evTick[b]) (void)hipEventDestroy(s->evTick[b]);
     if (s->evCopied[b]) (void)hipEventDestroy(s->evCopied[b]);
@@ -228,6 +232,8 @@ int pies_destroy(pies_solver_t* s) {
 
 int pies_clear(pies_solver_t* s) {
   if (!s) return PIES_ERR_INVALID;
+  s->h_skins.clear();
+  s->skinDirty = false;
   if (s->device != PIES_DEVICE_NONE) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
@@ -820,6 +826,8 @@ int pies_finalize(pies_solver_t* s) {
   if (int rc = capture_graph(s)) return rc;
   s->sceneDirty = false;
   s->graphDirty = false;
+  if (!s->h_skins.empty())  // the skins' records, in the numbering just decided
+    if (int rc = skin_upload(s)) return rc;
   return PIES_OK;
 }
 
@@ -833,6 +841,8 @@ int pies_internal_ensure_ready(pies_solver* s) {
     if (int rc = capture_graph(s)) return rc;
     s->graphDirty = false;
   }
+  if (s->skinDirty)  // a skin was added to a finalized scene: its records only
+    if (int rc = skin_upload(s)) return rc;
   return PIES_OK;
 }
 
@@ -987,6 +997,21 @@ static int export_prepare(pies_solver* s) {
     HIP_TRY(s, hipMalloc((void**)&s->d_export, std::max<size_t>(n, 1) * sizeof(float4)));
     s->h_export_n = n;
   }
+  const size_t nv = s->skin.nVerts;  // skins: positions and normals of every skin, one device buffer and one pinned buffer per frame
+  if (nv && (s->skinExport_n < nv || !s->d_skinExport)) {
+    HIP_TRY(s, hipStreamSynchronize(s->copyStream));
+    for (int b = 0; b < 2; ++b) {
+      if (s->h_skinExport[b]) (void)hipHostFree(s->h_skinExport[b]);
+      s->h_skinExport[b] = nullptr;
+      s->frameSkinVerts[b] = 0;
+    }
+    if (s->d_skinExport) (void)hipFree(s->d_skinExport);
+    s->d_skinExport = nullptr;
+    s->skinExport_n = 0;
+    for (int b = 0; b < 2; ++b) HIP_TRY(s, hipHostMalloc((void**)&s->h_skinExport[b], 6 * nv * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(s, hipMalloc((void**)&s->d_skinExport, 6 * nv * sizeof(float)));
+    s->skinExport_n = nv;
+  }
   return PIES_OK;
 }
 
@@ -1011,9 +1036,17 @@ int pies_tick_begin(pies_solver_t* s, uint64_t* frame) {
       HIP_TRY(s, hipMemcpyAsync(s->d_export, s->nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
     }
   }
+  const uint32_t nv = n ? s->skin.nVerts : 0u;  // skins: evaluated behind the position copy (d_skinExport is free like d_export)
+  if (nv) {
+    launch_skin_positions(s->stream, s->skin, s->nd.pos, s->d_skinExport, 0, nv);
+    launch_skin_normals(s->stream, s->skin, s->d_skinExport, s->d_skinExport + 3ull * nv, 0, nv);
+    HIP_TRY(s, hipGetLastError());
+  }
   HIP_TRY(s, hipEventRecord(s->evTick[b], s->stream));
   HIP_TRY(s, hipStreamWaitEvent(s->copyStream, s->evTick[b], 0));
   if (n) HIP_TRY(s, hipMemcpyAsync(s->h_export[b], s->d_export, n * sizeof(float4), hipMemcpyDeviceToHost, s->copyStream));
+  if (nv) HIP_TRY(s, hipMemcpyAsync(s->h_skinExport[b], s->d_skinExport, 6ull * nv * sizeof(float), hipMemcpyDeviceToHost, s->copyStream));
+  s->frameSkinVerts[b] = nv;
   HIP_TRY(s, hipEventRecord(s->evCopied[b], s->copyStream));
   s->frameBegun = f;
   *frame = f;
@@ -1198,6 +1231,12 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_PD_WINDOW_ENTRIES: *out = s->pd.cg.wRows ? s->pdWindowEntries : 0u; break;
     case PIES_PD_WINDOW_HALO: *out = s->pd.cg.wRows ? s->pdWindowHalo : 0u; break;
     case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
+    case PIES_SKINS: *out = (uint32_t)s->h_skins.size(); break;
+    case PIES_SKIN_VERTICES: {
+      *out = 0;
+      for (const HostSkin& k : s->h_skins) *out += k.vertexCount();
+      break;
+    }
     case PIES_NODE_CONTACTS: {
       *out = 0;
       if (s->device != PIES_DEVICE_NONE && s->ncActive && s->nd.n)

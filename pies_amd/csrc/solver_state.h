@@ -15,6 +15,7 @@
 #include "hash_kernels.h"
 #include "pd_contact_kernels.h"
 #include "pair_kernels.h"
+#include "skin_kernels.h"
 
 namespace pies {
 
@@ -62,6 +63,17 @@ struct HostGoal {  // GoalMatchingConstraint (Src/ShapeMatchingConstraint.cpp:12
   std::vector<float> mat;  // 3 x n world positions at creation
   float transform[16];     // column-major mat4
   float w;
+};
+// An embedded surface mesh (pies_add_skin, skin.cpp): every vertex bound to one tetrahedron.  Node ids are HOST ids, always (the
+// InternalNumbering scope of pies_finalize leaves skins alone; skin_upload translates through nodeOrder.inv).
+struct HostSkin {
+  std::vector<uint32_t> tet;     // per vertex: index into the tetrahedra the host listed
+  std::vector<uint32_t> ids;     // 4 per vertex
+  std::vector<float> w;          // 4 per vertex: w0 = 1 - (w1 + w2 + w3), w1, w2, w3
+  std::vector<uint32_t> tris;    // 3 per triangle, indices into this skin's vertices
+  std::vector<uint32_t> incPtr;  // vertex -> triangles that name it, CSR, ascending triangle index per vertex
+  std::vector<uint32_t> inc;
+  uint32_t vertexCount() const { return static_cast<uint32_t>(tet.size()); }
 };
 struct HostFixedRegion {  // Solver::FixedRegion (Include/Pies/Solver.h:147-151)
   float invInitialTransform[16];
@@ -232,6 +244,7 @@ struct pies_solver {
   bool goalDirty = false;  // a goal transform changed: refresh its projected positions in HBM
   std::vector<uint32_t> h_triangles;  // 3 per triangle
   std::vector<uint32_t> h_lines;
+  std::vector<pies::HostSkin> h_skins;  // extension: embedded surface meshes (pies_add_skin)
   uint32_t constraintId = 0;
 
   bool sceneDirty = true;    // topology/rest data changed: rebuild plans + upload everything
@@ -301,6 +314,18 @@ struct pies_solver {
   float4* d_export = nullptr;
   uint64_t frameBegun = 0;      // frames begun so far (frame ids start at 1)
   uint64_t frameAcquired = 0;   // frame the host currently holds (0: none)
+  // ---- skins: device records of h_skins (built by skin_upload at pies_finalize / before the next use), outputs, export ----
+  pies::SkinArrays skin{};
+  bool skinDirty = false;            // h_skins and the device records differ
+  std::vector<void*> skinAllocations;
+  std::vector<uint32_t> skinFirst;   // first vertex of every skin in the concatenated arrays, + the total
+  float* d_skinOut = nullptr;        // pies_read_skin: positions (3 x nVerts) then normals (3 x nVerts)
+  float* h_skinStage = nullptr;      // pinned, same layout
+  size_t h_skinStage_n = 0;          // vertices it holds
+  float* d_skinExport = nullptr;     // pies_tick_begin: same layout, one frame
+  float* h_skinExport[2] = {nullptr, nullptr};  // pinned, per frame parity
+  size_t skinExport_n = 0;           // vertices the three export buffers hold
+  uint32_t frameSkinVerts[2] = {0, 0};  // skin vertices frame (parity) carries
   // ---- PD: a substep whose solve ends above the tolerance is run again with a larger CG budget (pies_tick) ----
   float4 *snapPos = nullptr, *snapPrev = nullptr, *snapVel = nullptr;
   double* snapQuat = nullptr;
@@ -339,6 +364,9 @@ bool build_wave_plan(const pies_solver* s, WavePlan& out);
 // layer_plan.cpp : fills s->layer and the four PBD plans; false (nothing changed) when the scene does not suit it
 bool build_layer_plan(pies_solver* s);
 
+// skin.cpp : device records of the skins (no-ops without skins); skin_free_device forgets them (free_device, pies_clear)
+int skin_upload(pies_solver* s);
+void skin_free_device(pies_solver* s);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of
