@@ -1,10 +1,10 @@
-// C ABI (include/pies_hip.h): handle lifetime, upload to HBM, tick, state access (the launch sequence of a substep and its
-// graph capture: substep_graph.cpp; timing passes: profiling.cpp; pies_set_tuning: tuning.cpp).
+// C ABI (include/pies_hip.h): handle lifetime, pies_finalize, tick, state access (the steps that build a scene in HBM and
+// free_device: device_scene.cpp; the launch sequence of a substep and its graph capture: substep_graph.cpp; timing passes:
+// profiling.cpp; pies_set_tuning: tuning.cpp).
 // The substep itself is Solver::tickPBD (Src/Solver.cpp:40-160) / tickPD (:162-486) re-expressed as a
 // fixed sequence of kernel launches captured once into a hipGraph: at 100k particles a conflict-free
 // batch runs for a few microseconds, so un-graphed launches would be host-bound.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,119 +12,9 @@
 
 #include "capi_internal.h"
 
-#include <map>
-#include <memory>
-#include <mutex>
 #include <numeric>
 
 using namespace pies;
-
-namespace pies {
-
-// strain and volume constraints added pairwise over the same elements (createTetBox and addTriMeshVolume add them that way,
-// PrimitiveUtilities.cpp:401-514): one gather, one SVD, one tile plan for both
-bool tet_volume_pairs(const pies_solver* s) {
-  bool paired = !s->h_tet.empty() && s->h_tet.size() == s->h_volume.size();
-  const bool planned = s->plan[PIES_TET].order.size() == s->h_tet.size();  // (PD: host order; a handle that has not been finalized has no plan yet)
-  for (size_t k = 0; paired && k < s->h_tet.size(); ++k) {
-    const HostTet &a = s->h_tet[planned ? s->plan[PIES_TET].order[k] : k], &b = s->h_volume[k];
-    paired = std::memcmp(a.ids, b.ids, sizeof(a.ids)) == 0 && std::memcmp(a.qinv, b.qinv, sizeof(a.qinv)) == 0;
-  }
-  if (const char* e = tuning_env("PIES_NO_TET_PAIRS"); e && e[0] == '1') paired = false;
-  return paired;
-}
-
-void free_device(pies_solver* s) {
-  destroy_graph(s);
-  skin_free_device(s);
-  for (void* p : s->allocations) (void)hipFree(p);
-  s->allocations.clear();
-  s->nd = NodeArrays{nullptr, nullptr, nullptr, nullptr, 0};
-  s->d_pack = nullptr;
-  s->d_nodeInv = nullptr;
-  s->d_pc_id = nullptr; s->d_pc_tw = nullptr;
-  s->d_dc_ids = nullptr; s->d_dc_rw = nullptr;
-  s->d_tc_ids = nullptr; s->d_tc_q0 = s->d_tc_q1 = s->d_tc_q2 = nullptr;
-  s->d_bc_ids = nullptr; s->d_bc_aw = nullptr;
-  s->d_np_ids = nullptr;
-  s->d_np_bits = nullptr; s->d_np_nodes = nullptr; s->npNodes = 0;
-  s->d_vc_ids = nullptr; s->d_vc_q0 = s->d_vc_q1 = s->d_vc_q2 = nullptr;
-  s->pd = PdArrays{};
-  s->hash = HashArrays{};
-  s->pairs = PairArrays{};
-  s->nc = NodeContactArrays{};
-  s->ncActive = false;
-  s->d_pairDictIndex = nullptr;
-  s->d_pairDictTable = nullptr;
-  s->pairDictSets = 0;
-  s->pdRowStencils = 0;
-  s->d_layer = LayerDevice{};
-  s->snapPos = s->snapPrev = s->snapVel = nullptr;
-  s->snapQuat = nullptr;
-}
-
-static int upload_nodes(pies_solver* s) {
-  const uint32_t n = s->nodeCount();
-  // a renumbered scene: device index k holds host node order[k] (inside pies_finalize the host arrays are already translated)
-  const bool perm = s->nodeOrder.active() && !s->internalIds && s->nodeOrder.order.size() == n;
-  std::vector<float4> pos(n), prev(n), vel(n);
-  std::vector<float> radius;
-  for (uint32_t k = 0; k < n; ++k) {
-    const uint32_t i = perm ? s->nodeOrder.order[k] : k;
-    pos[k] = make_float4(s->h_pos[3 * i], s->h_pos[3 * i + 1], s->h_pos[3 * i + 2], s->h_invMass[i]);
-    prev[k] = make_float4(s->h_prev[3 * i], s->h_prev[3 * i + 1], s->h_prev[3 * i + 2], 0.f);
-    vel[k] = make_float4(s->h_vel[3 * i], s->h_vel[3 * i + 1], s->h_vel[3 * i + 2], 0.f);
-  }
-  if (perm) {
-    radius.resize(n);
-    for (uint32_t k = 0; k < n; ++k) radius[k] = s->h_radius[s->nodeOrder.order[k]];
-  }
-  if (n) {
-    HIP_TRY(s, hipMemcpyAsync(s->nd.pos, pos.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->nd.prev, prev.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->nd.vel, vel.data(), n * sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->nd.radius, perm ? radius.data() : s->h_radius.data(), n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    std::vector<float> lrad;
-    if (s->d_layer.lrad && s->layer.nodeList.size() == n) {  // schedule LAYERED keeps the radii in level order as well
-      lrad.resize(n);
-      for (uint32_t i = 0; i < n; ++i) lrad[i] = s->h_radius[s->layer.nodeList[i]];
-      HIP_TRY(s, hipMemcpyAsync(s->d_layer.lrad, lrad.data(), n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    }
-    HIP_TRY(s, hipStreamSynchronize(s->stream));  // the staging vectors die with this scope
-  }
-  s->hostNodesDirty = false;
-  s->stale = 0;
-  return PIES_OK;
-}
-
-// Host mirror <- HBM: the arrays of `mask` (bit 0 positions, 1 previous positions, 2 velocities) that are stale, one
-// copy each through the pinned staging buffer.
-static int download_nodes(pies_solver* s, uint32_t mask = 7u) {
-  const uint32_t n = s->nd.n;
-  mask &= s->stale;
-  if (n == 0 || !s->h_stage || !s->d_pack) { s->stale = 0; return PIES_OK; }
-  float* dst[3] = {s->h_pos.data(), s->h_prev.data(), s->h_vel.data()};
-  const float4* src[3] = {s->nd.pos, s->nd.prev, s->nd.vel};
-  for (int a = 0; a < 3; ++a) {
-    if (!(mask & (1u << a))) continue;
-    // packed on the device: 12 bytes per node cross the bus, and the mirror is one memcpy from the pinned stage (measured on
-    // config 2: 654 ticks/s against 637 with four floats per node and an unpacking loop; the asynchronous export stays the
-    // fast way out, 680)
-    launch_pack_xyz(s->stream, src[a], s->d_pack, n, s->d_nodeInv);  // (a renumbered scene: packed in host numbering)
-    HIP_TRY(s, hipMemcpyAsync(s->h_stage, s->d_pack, 3ull * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-    std::memcpy(dst[a], s->h_stage, 3ull * n * sizeof(float));
-    s->stale &= ~(1u << a);
-  }
-  return PIES_OK;
-}
-
-int scene_sync_host(pies_solver* s) {
-  if (s->device == PIES_DEVICE_NONE) return PIES_OK;
-  if (hipSetDevice(s->device) != hipSuccess) return fail(s, PIES_ERR_HIP, "hipSetDevice failed");
-  return download_nodes(s);
-}
-}  // namespace pies
 
 extern "C" {
 
@@ -339,9 +229,9 @@ int pies_set_pcg_retry(pies_solver_t* s, int enabled) {
 int pies_get_pcg_stats(pies_solver_t* s, float* max_rel_residual, uint32_t* max_iters_used, uint32_t* solves) {
   if (!s) return PIES_ERR_INVALID;
   float st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (s->opt.solver == PIES_SOLVER_PD && s->pd.cg.stats) {
+  if (s->opt.solver == PIES_SOLVER_PD && s->dev.pd.cg.stats) {
     HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(st, s->pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
   if (max_rel_residual) *max_rel_residual = std::sqrt(st[0]);
@@ -353,9 +243,9 @@ int pies_get_pcg_stats(pies_solver_t* s, float* max_rel_residual, uint32_t* max_
 int pies_get_pcg_health(pies_solver_t* s, uint64_t* short_solves, uint64_t* solves_total, uint32_t* substeps_retried, uint32_t* budget) {
   if (!s) return PIES_ERR_INVALID;
   float st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (s->opt.solver == PIES_SOLVER_PD && s->pd.cg.stats) {
+  if (s->opt.solver == PIES_SOLVER_PD && s->dev.pd.cg.stats) {
     HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(st, s->pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
   // stats[4], [5]: solves left above the tolerance / solves run by the substeps whose result was kept (a substep
@@ -369,98 +259,9 @@ int pies_get_pcg_health(pies_solver_t* s, uint64_t* short_solves, uint64_t* solv
   return PIES_OK;
 }
 
-static int build_plans(pies_solver* s, int sched) {
-  const uint32_t n = s->nodeCount();
-  s->layer = LayerPlan{};
-  s->wave = WavePlan{};
-  if (sched == PIES_SCHEDULE_LAYERED) {
-    if (build_layer_plan(s)) return PIES_OK;
-    sched = PIES_SCHEDULE_COLOURED;  // wide bodies (two levels do not fit in LDS), scenes without constraints
-  }
-  std::vector<uint32_t> ids;
-  ids.resize(s->h_position.size());
-  for (size_t i = 0; i < ids.size(); ++i) ids[i] = s->h_position[i].id;
-  build_plan({ids.data(), 1, (uint32_t)s->h_position.size(), 0x1}, n, sched, s->plan[PIES_POSITION]);
-  ids.resize(2 * s->h_distance.size());
-  for (size_t i = 0; i < s->h_distance.size(); ++i) { ids[2 * i] = s->h_distance[i].ids[0]; ids[2 * i + 1] = s->h_distance[i].ids[1]; }
-  // a distance projection moves node a only (Constraints.cpp:34-36); node b is read
-  std::vector<uint16_t> hint(s->h_distance.size());
-  for (size_t i = 0; i < hint.size(); ++i) hint[i] = s->h_distance[i].hint;
-  build_plan({ids.data(), 2, (uint32_t)s->h_distance.size(), 0x1, hint.data()}, n, sched, s->plan[PIES_DISTANCE]);
-  ids.resize(4 * s->h_tet.size());
-  for (size_t i = 0; i < s->h_tet.size(); ++i) std::memcpy(&ids[4 * i], s->h_tet[i].ids, 16);
-  hint.resize(s->h_tet.size());
-  for (size_t i = 0; i < hint.size(); ++i) hint[i] = s->h_tet[i].hint;
-  build_plan({ids.data(), 4, (uint32_t)s->h_tet.size(), 0xF, hint.data()}, n, sched, s->plan[PIES_TET]);
-  ids.resize(4 * s->h_bend.size());
-  for (size_t i = 0; i < s->h_bend.size(); ++i) std::memcpy(&ids[4 * i], s->h_bend[i].ids, 16);
-  build_plan({ids.data(), 4, (uint32_t)s->h_bend.size(), 0xF}, n, sched, s->plan[PIES_BEND]);
-  const char* noWave = tuning_env("PIES_NO_WAVEFRONT");
-  if (sched == PIES_SCHEDULE_EXACT && !(noWave && noWave[0] == '1')) build_wave_plan(s, s->wave);
-  return PIES_OK;
-}
-
-// PIES_FLAG_PD_NODE_CONTACTS: the element adjacency that excludes pairs from the contacts - per node, ascending, in the device's
-// numbering (inside pies_finalize the host containers hold it) -, the partner lists and the friction pass's cursors and words
-static int nc_build(pies_solver* s, uint32_t n) {
-  std::vector<uint64_t> e;  // a << 32 | b, both directions
-  auto join = [&](uint32_t a, uint32_t b) {
-    if (a == b || a >= n || b >= n) return;
-    e.push_back(static_cast<uint64_t>(a) << 32 | b);
-    e.push_back(static_cast<uint64_t>(b) << 32 | a);
-  };
-  auto clique = [&](const uint32_t* ids, int k) {
-    for (int a = 0; a < k; ++a)
-      for (int b = a + 1; b < k; ++b) join(ids[a], ids[b]);
-  };
-  for (const HostDistance& c : s->h_distance) clique(c.ids, 2);
-  for (const HostTet& c : s->h_tet) clique(c.ids, 4);
-  for (const HostTet& c : s->h_volume) clique(c.ids, 4);
-  for (const HostBend& c : s->h_bend) clique(c.ids, 4);
-  for (size_t t = 0; t + 2 < s->h_triangles.size(); t += 3) clique(&s->h_triangles[t], 3);
-  for (const HostNodePair& c : s->h_nodePair) clique(c.ids, 2);
-  std::sort(e.begin(), e.end());
-  e.erase(std::unique(e.begin(), e.end()), e.end());
-  std::vector<uint32_t> adjPtr(n + 1ull, 0u), adj(e.size());
-  for (size_t k = 0; k < e.size(); ++k) { ++adjPtr[(e[k] >> 32) + 1]; adj[k] = static_cast<uint32_t>(e[k]); }
-  for (uint32_t i = 0; i < n; ++i) adjPtr[i + 1] += adjPtr[i];
-  std::vector<uint64_t>().swap(e);
-  NodeContactArrays& C = s->nc;
-  C = NodeContactArrays{};
-  C.n = n;
-  C.cap = kNcDefaultPartners;
-  if (const char* v = tuning_env("PIES_PD_NODE_CONTACT_PARTNERS")) {
-    const long k = std::strtol(v, nullptr, 10);
-    if (k < 1 || k > 4096) return fail(s, PIES_ERR_INVALID, "PIES_PD_NODE_CONTACT_PARTNERS: 1 .. 4096");
-    C.cap = static_cast<uint32_t>(k);
-  }
-  s->ncRounds = 8;
-  if (const char* v = tuning_env("PIES_PD_NODE_CONTACT_ROUNDS")) {
-    const long k = std::strtol(v, nullptr, 10);
-    if (k >= 1 && k <= static_cast<long>(kNcMaxRounds)) s->ncRounds = static_cast<uint32_t>(k);
-  }
-  s->ncCalm = 0;
-  C.rounds = s->ncRounds;
-  uint32_t *adjPtrD = nullptr, *adjD = nullptr;
-  if (int rc = upload(s, adjPtr, &adjPtrD)) return rc;
-  if (adj.empty()) adj.push_back(0u);  // (a valid pointer; adjPtr says there is nothing)
-  if (int rc = upload(s, adj, &adjD)) return rc;
-  C.adjPtr = adjPtrD;
-  C.adj = adjD;
-  if (int rc = dev_alloc(s, static_cast<size_t>(n) * C.cap, &C.part)) return rc;
-  if (int rc = dev_alloc(s, n, &C.cnt, true)) return rc;
-  for (int b = 0; b < 2; ++b)
-    if (int rc = dev_alloc(s, n, &C.cur[b], true)) return rc;
-  if (int rc = dev_alloc(s, kNcCtlWords, &C.ctl, true)) return rc;
-  C.flags = s->hash.counters + kCounterFlags;
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  s->ncActive = true;
-  return PIES_OK;
-}
-
 // The contacts of the last substep as (a, b) pairs of device ids, a < b, in the order the friction pass ran them (ascending pair key)
 static int nc_download(pies_solver* s, std::vector<uint32_t>* pairs, uint32_t* count) {
-  const NodeContactArrays& C = s->nc;
+  const NodeContactArrays& C = s->dev.nc;
   std::vector<uint32_t> cnt(C.n);
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipMemcpyAsync(cnt.data(), C.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
@@ -490,7 +291,7 @@ static int nc_download(pies_solver* s, std::vector<uint32_t>* pairs, uint32_t* c
 int pies_get_node_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, uint32_t* count) {
   if (!s || !count) return PIES_ERR_INVALID;
   *count = 0;
-  if (s->device == PIES_DEVICE_NONE || !s->ncActive || s->nd.n == 0) return PIES_OK;
+  if (s->device == PIES_DEVICE_NONE || !s->dev.ncActive || s->dev.nd.n == 0) return PIES_OK;
   std::vector<uint32_t> pairs;
   if (int rc = nc_download(s, &pairs, nullptr)) return rc;
   const uint32_t m = static_cast<uint32_t>(pairs.size() / 2);
@@ -514,10 +315,7 @@ int pies_finalize(pies_solver_t* s) {
     return PIES_OK;
   }
   HIP_TRY(s, hipSetDevice(s->device));
-  if (!s->sceneDirty) {
-    if (s->hostNodesDirty) return upload_nodes(s);
-    return PIES_OK;
-  }
+  if (!s->sceneDirty) return s->hostNodesDirty ? upload_nodes(s) : PIES_OK;
   const bool isPD = s->opt.solver == PIES_SOLVER_PD;
   const bool collide = s->nodeCollisions && !isPD;
   const bool ncOn = isPD && s->pdNodeContacts;  // PIES_FLAG_PD_NODE_CONTACTS: the node grid, for the PD contacts
@@ -531,298 +329,29 @@ int pies_finalize(pies_solver_t* s) {
   free_device(s);
 
   const uint32_t n = s->nodeCount();
-  // ---- node numbering (node_order.cpp): from here on the host containers hold the device's numbering, until this returns ----
+  // node numbering (node_order.cpp): from here on the host containers hold the device's numbering, until this returns
   decide_node_order(s);
   InternalNumbering internal(s);
-  // ---- plans (PD's local step is order independent: one batch per container, host order) ----
-  build_plans(s, isPD ? -1 : s->schedule);
-  // ---- node arrays ----
-  if (n) {
-    void* p;
-    HIP_TRY(s, hipMalloc(&p, n * sizeof(float4))); s->allocations.push_back(p); s->nd.pos = (float4*)p;
-    HIP_TRY(s, hipMalloc(&p, n * sizeof(float4))); s->allocations.push_back(p); s->nd.prev = (float4*)p;
-    HIP_TRY(s, hipMalloc(&p, n * sizeof(float4))); s->allocations.push_back(p); s->nd.vel = (float4*)p;
-    HIP_TRY(s, hipMalloc(&p, n * sizeof(float))); s->allocations.push_back(p); s->nd.radius = (float*)p;
-    HIP_TRY(s, hipMalloc(&p, 3ull * n * sizeof(float))); s->allocations.push_back(p); s->d_pack = (float*)p;
-    s->nd.n = n;
-    if (s->h_stage_n < n) {
-      if (s->h_stage) (void)hipHostFree(s->h_stage);
-      s->h_stage = nullptr;
-      HIP_TRY(s, hipHostMalloc((void**)&s->h_stage, n * sizeof(float4), hipHostMallocDefault));
-      s->h_stage_n = n;
-    }
-  }
-  if (int rc = upload_nodes(s)) return rc;
-  if (s->nodeOrder.active())
-    if (int rc = upload(s, s->nodeOrder.inv, &s->d_nodeInv)) return rc;
-  // ---- constraint records, in schedule order ----
-  {
-    const Plan& pl = s->plan[PIES_POSITION];
-    std::vector<uint32_t> id(pl.order.size());
-    std::vector<float4> tw(pl.order.size());
-    for (size_t k = 0; k < pl.order.size(); ++k) {
-      const HostPosition& c = s->h_position[pl.order[k]];
-      id[k] = c.id;
-      tw[k] = make_float4(c.target[0], c.target[1], c.target[2], c.w);
-    }
-    if (int rc = upload(s, id, &s->d_pc_id)) return rc;
-    if (int rc = upload(s, tw, &s->d_pc_tw)) return rc;
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  {
-    const Plan& pl = s->plan[PIES_DISTANCE];
-    std::vector<uint2> id(pl.order.size());
-    std::vector<float2> rw(pl.order.size());
-    for (size_t k = 0; k < pl.order.size(); ++k) {
-      const HostDistance& c = s->h_distance[pl.order[k]];
-      id[k] = make_uint2(c.ids[0], c.ids[1]);
-      rw[k] = make_float2(c.target, c.w);
-    }
-    if (int rc = upload(s, id, &s->d_dc_ids)) return rc;
-    if (int rc = upload(s, rw, &s->d_dc_rw)) return rc;
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  {
-    const Plan& pl = s->plan[PIES_TET];
-    std::vector<uint4> id(pl.order.size());
-    std::vector<float4> q0(pl.order.size()), q1(pl.order.size()), q2(pl.order.size());
-    for (size_t k = 0; k < pl.order.size(); ++k) {
-      const HostTet& c = s->h_tet[pl.order[k]];
-      id[k] = make_uint4(c.ids[0], c.ids[1], c.ids[2], c.ids[3]);
-      q0[k] = make_float4(c.qinv[0], c.qinv[1], c.qinv[2], c.qinv[3]);
-      q1[k] = make_float4(c.qinv[4], c.qinv[5], c.qinv[6], c.qinv[7]);
-      q2[k] = make_float4(c.qinv[8], c.lo, c.hi, c.w);
-    }
-    if (int rc = upload(s, id, &s->d_tc_ids)) return rc;
-    if (int rc = upload(s, q0, &s->d_tc_q0)) return rc;
-    if (int rc = upload(s, q1, &s->d_tc_q1)) return rc;
-    if (int rc = upload(s, q2, &s->d_tc_q2)) return rc;
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  {
-    const Plan& pl = s->plan[PIES_BEND];
-    std::vector<uint4> id(pl.order.size());
-    std::vector<float2> aw(pl.order.size());
-    for (size_t k = 0; k < pl.order.size(); ++k) {
-      const HostBend& c = s->h_bend[pl.order[k]];
-      id[k] = make_uint4(c.ids[0], c.ids[1], c.ids[2], c.ids[3]);
-      aw[k] = make_float2(c.angle, c.w);
-    }
-    if (int rc = upload(s, id, &s->d_bc_ids)) return rc;
-    if (int rc = upload(s, aw, &s->d_bc_aw)) return rc;
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  if (isPD && !s->h_nodePair.empty()) {  // the node-pair extension (container order: a pair's slot is its index)
-    std::vector<uint2> id(s->h_nodePair.size());
-    for (size_t k = 0; k < id.size(); ++k) id[k] = make_uint2(s->h_nodePair[k].ids[0], s->h_nodePair[k].ids[1]);
-    if (int rc = upload(s, id, &s->d_np_ids)) return rc;
-    // the pairs' nodes (ids in device numbering here): the velocity kernel leaves their floor friction to
-    // launch_pd_node_pair_floor_friction, which runs after the pairs' friction (Solver.cpp:398-428 before :473-484)
-    const uint32_t n = s->nodeCount();
-    std::vector<uint32_t> bits((n + 31u) / 32u, 0u), nodes;
-    for (const uint2& p : id)
-      for (uint32_t i : {p.x, p.y})
-        if (i < n) bits[i >> 5] |= 1u << (i & 31u);
-    for (uint32_t i = 0; i < n; ++i)
-      if ((bits[i >> 5] >> (i & 31u)) & 1u) nodes.push_back(i);
-    if (int rc = upload(s, bits, &s->d_np_bits)) return rc;
-    if (int rc = upload(s, nodes, &s->d_np_nodes)) return rc;
-    s->npNodes = (uint32_t)nodes.size();
-  }
-  if (s->layer.active && !isPD) {
-    const LayerPlan& L = s->layer;
-    LayerDevice& d = s->d_layer;
-    int maxLds = 0;
-    HIP_TRY(s, hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
-    if (static_cast<size_t>(L.maxGroupNodes) * 20 + 4096 > static_cast<size_t>(maxLds))
-      return fail(s, PIES_ERR_UNSUPPORTED, "schedule LAYERED: the device's LDS is smaller than this build assumes");
-    HIP_TRY(s, layer_prepare(L.maxGroupNodes));
-    if (int rc = upload(s, L.nodeList, &d.nodeList)) return rc;
-    if (int rc = dev_alloc(s, L.nodeList.size(), &d.lpos, true)) return rc;
-    {
-      std::vector<float> lrad(L.nodeList.size());
-      for (size_t i = 0; i < lrad.size(); ++i) lrad[i] = s->h_radius[L.nodeList[i]];
-      if (int rc = upload(s, lrad, &d.lrad)) return rc;
-    }
-    for (int ph = 0; ph < 4; ++ph)
-      if (int rc = upload(s, L.tiles[ph], &d.tiles[ph])) return rc;
-    for (int k = 0; k < 5; ++k)
-      for (int ph = 0; ph < 4; ++ph)
-        if (int rc = upload(s, L.kind[k].colOff[ph], &d.colOff[k][ph])) return rc;
-    if (int rc = upload(s, L.kind[PIES_POSITION].local, &d.pc_lid)) return rc;
-    {
-      const std::vector<uint32_t>& l = L.kind[PIES_DISTANCE].local;
-      std::vector<uint32_t> packed(l.size() / 2);
-      for (size_t k = 0; k < packed.size(); ++k) packed[k] = l[2 * k] | (l[2 * k + 1] << 16);
-      if (int rc = upload(s, packed, &d.dc_lid)) return rc;
-    }
-    for (int k : {PIES_TET, PIES_BEND}) {
-      const std::vector<uint32_t>& l = L.kind[k].local;
-      std::vector<uint2> packed(l.size() / 4);
-      for (size_t c = 0; c < packed.size(); ++c) packed[c] = make_uint2(l[4 * c] | (l[4 * c + 1] << 16), l[4 * c + 2] | (l[4 * c + 3] << 16));
-      if (int rc = upload(s, packed, k == PIES_TET ? &d.tc_lid : &d.bc_lid)) return rc;
-    }
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  s->d_waveIndex = nullptr;
-  if (s->wave.active && !isPD) {
-    if (int rc = upload(s, s->wave.index, &s->d_waveIndex)) return rc;
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-    std::vector<uint32_t>().swap(s->wave.index);  // the levels (offsets, counts) stay on the host; the items live in HBM
-  }
-  if ((collide || ncOn) && n) {
-    HashArrays& H = s->hash;
-    H.n = n;
-    uint64_t entries = 0;
-    bool fast = true;
-    collision_grid_bound(s, entries, fast);
-    if (n >= (1u << 25)) return fail(s, PIES_ERR_UNSUPPORTED, "node-node collisions: more than 2^25 nodes");
-    if (entries > 0x7fff0000ull) return fail(s, PIES_ERR_UNSUPPORTED, "node-node collisions: more than 2^31 (cell, node) entries (gridSpacing is tiny against the radii)");
-    H.maxEntries = static_cast<uint32_t>(entries + 64);
-    {  // sort passes to start with: from the cell box of the scene as it stands (adapt_sort_passes follows it from there)
-      float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      float rmax = 0.0f;
-      for (float r : s->h_radius) if (std::isfinite(r)) rmax = std::max(rmax, r);
-      const size_t stride = s->h_pos.size() / std::max<size_t>(1, n);
-      for (size_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-          const float v = s->h_pos[i * stride + a];
-          if (std::isfinite(v)) { lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
-        }
-      uint32_t bits = 0;
-      for (int a = 0; a < 3; ++a) {
-        const double cells = hi[a] >= lo[a] ? (static_cast<double>(hi[a]) - lo[a] + 2.0 * (rmax + 0.5)) / s->opt.gridSpacing + 2.0 : 1.0;
-        uint64_t ext = static_cast<uint64_t>(std::min(cells, 4.0e9));
-        while (ext) { ++bits; ext >>= 1; }
-      }
-      s->sortPasses = sort_passes_for(bits);
-      s->sortCalm = 0;
-    }
-    uint32_t cap = 1024;
-    const uint64_t want = (collide ? s->collideFast : fast) ? 16ull * n : 2ull * H.maxEntries;  // distinct cells <= 8n resp. <= entries: load factor <= 0.5
-    while (cap < want && cap < (1u << 30)) cap <<= 1;
-    H.capacity = cap;
-    H.mask = cap - 1;
-    if (int rc = dev_alloc(s, n, &H.rng, true)) return rc;
-    if (int rc = dev_alloc(s, n + 1ull, &H.entCount, true)) return rc;
-    if (int rc = dev_alloc(s, n + 1ull, &H.entOff, true)) return rc;
-    if (int rc = dev_alloc(s, (n + 1ull) / 2048 + 2, &H.scanSums, true)) return rc;
-    if (int rc = dev_alloc(s, 6ull * ((n + 1ull + 255) / 256), &H.boxPart, true)) return rc;
-    for (int b = 0; b < 2; ++b) {
-      if (int rc = dev_alloc(s, H.maxEntries, &H.key[b], true)) return rc;
-      if (int rc = dev_alloc(s, H.maxEntries, &H.val[b], true)) return rc;
-    }
-    if (int rc = dev_alloc(s, 2048ull * ((H.maxEntries + kRadixTile - 1) / kRadixTile) + 2048, &H.hist, true)) return rc;  // (digit, workgroup) counts of a pass + the digit totals
-    if (int rc = dev_alloc(s, cap, &H.keys)) return rc;
-    HIP_TRY(s, hipMemsetAsync(H.keys, 0xFF, static_cast<size_t>(cap) * sizeof(uint64_t), s->stream));
-    if (int rc = dev_alloc(s, cap, &H.start, true)) return rc;
-    if (int rc = dev_alloc(s, cap, &H.end, true)) return rc;
-    if (int rc = dev_alloc(s, cap, &H.gcnt, true)) return rc;
-    if (int rc = dev_alloc(s, cap, &H.done, true)) return rc;
-    if (int rc = dev_alloc(s, std::min<uint64_t>(cap, H.maxEntries), &H.used, true)) return rc;
-    if (int rc = dev_alloc(s, kHashCounters, &H.counters, true)) return rc;
-    if (int rc = dev_alloc(s, 27ull * n, &H.passList, true)) return rc;
-    s->pairs = PairArrays{};
-    if (collide) {  // pair order: every node's list of partners (in pools), the frontier of the level launches
-
-      PairArrays& P = s->pairs;
-      P.n = n;
-      // list entries: 96 per node on average (BASELINE config 4 lists 15-50), in kPairPools pools; a small scene may list every
-      // pair (a body that has collapsed into a few cells: quirk Q2 does that to a tetrahedral PBD body within a tick)
-      // (only a small scene: the n * n floor used to apply to every scene of 8 192 nodes and more - 270 MB per handle)
-      const uint64_t everyPair = n <= 8192u ? static_cast<uint64_t>(n) * n : 0ull;
-      P.poolCap = static_cast<uint32_t>(std::min<uint64_t>((std::max<uint64_t>(96ull * n, everyPair) + 65536) / kPairPools + 4096, 0x7fff0000ull / kPairPools));
-      if (int rc = dev_alloc(s, 4ull * n, &P.node, true)) return rc;
-      if (int rc = dev_alloc(s, n, &P.vel0)) return rc;
-      if (int rc = dev_alloc(s, n, &P.exc, true)) return rc;
-      if (int rc = dev_alloc(s, n, &P.turnCnt, true)) return rc;
-      if (int rc = dev_alloc(s, static_cast<size_t>(P.poolCap) * kPairPools, &P.nbr)) return rc;
-      if (!s->collideFast)  // ranges wider than two cells per axis: the shared-cell count of an entry does not fit its four bits
-        if (int rc = dev_alloc(s, static_cast<size_t>(P.poolCap) * kPairPools, &P.nbrM)) return rc;
-      P.frCap = n / 32 + 256;  // a chunk of 64 lanes appends at most 128 nodes to the one sub-list it is dealt to
-      for (int b = 0; b < 2; ++b)
-        if (int rc = dev_alloc(s, static_cast<size_t>(P.frCap) * kPairLists, &P.fr[b])) return rc;
-      if (int rc = dev_alloc(s, 3ull * kPairLists * kPairPad, &P.frCount, true)) return rc;
-      if (int rc = dev_alloc(s, static_cast<size_t>(kPairStripes) * kPairPad, &P.hitStripe, true)) return rc;
-      if (int rc = dev_alloc(s, n, &P.bq)) return rc;
-      if (int rc = dev_alloc(s, 64ull * kPairPad, &P.stat, true)) return rc;
-      if (int rc = dev_alloc(s, 4ull * n, &P.grp)) return rc;
-      if (int rc = dev_alloc(s, n, &P.spill)) return rc;
-      if (int rc = dev_alloc(s, n, &P.left, true)) return rc;
-      if (int rc = dev_alloc(s, static_cast<size_t>(kPairPools) * kPairPad, &P.pool, true)) return rc;
-      if (int rc = dev_alloc(s, kPairWords, &P.ctl, true)) return rc;
-    }
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
+  build_plans(s, isPD ? -1 : s->schedule);  // (PD's local step is order independent: one batch per container, host order)
+  // the steps, device_scene.cpp
+  if (int rc = alloc_nodes(s)) return rc;
+  if (int rc = upload_constraints(s)) return rc;
+  if (isPD && !s->h_nodePair.empty())
+    if (int rc = upload_node_pairs(s)) return rc;
+  if (s->layer.active && !isPD)
+    if (int rc = upload_layer_tables(s)) return rc;
+  if (s->wave.active && !isPD)
+    if (int rc = upload_wave_index(s)) return rc;
+  if ((collide || ncOn) && n)
+    if (int rc = alloc_node_grid(s, collide)) return rc;
   if (ncOn && n)
-    if (int rc = nc_build(s, n)) return rc;
+    if (int rc = nc_build(s)) return rc;
   if (isPD) {
-    std::vector<uint4> id(s->h_volume.size());
-    std::vector<float4> q0(id.size()), q1(id.size()), q2(id.size());
-    for (size_t k = 0; k < id.size(); ++k) {
-      const HostTet& c = s->h_volume[k];
-      id[k] = make_uint4(c.ids[0], c.ids[1], c.ids[2], c.ids[3]);
-      q0[k] = make_float4(c.qinv[0], c.qinv[1], c.qinv[2], c.qinv[3]);
-      q1[k] = make_float4(c.qinv[4], c.qinv[5], c.qinv[6], c.qinv[7]);
-      q2[k] = make_float4(c.qinv[8], c.lo, c.hi, c.w);
-    }
-    if (int rc = upload(s, id, &s->d_vc_ids)) return rc;
-    if (int rc = upload(s, q0, &s->d_vc_q0)) return rc;
-    if (int rc = upload(s, q1, &s->d_vc_q1)) return rc;
-    if (int rc = upload(s, q2, &s->d_vc_q2)) return rc;
-    // strain and volume constraints added pairwise over the same elements share one gather and one SVD
-    s->tetVolumePaired = tet_volume_pairs(s);
-    // Rest dictionary: the 64 bytes of constants of an element pair are the same for every element of one shape and material.
-    // With few distinct sets (a createTetBox lattice: one per orientation) the local step reads a 16-bit index per element.
-    s->d_pairDictIndex = nullptr;
-    s->d_pairDictTable = nullptr;
-    s->pairDictSets = 0;
-    s->h_pairDictIndex.clear();
-    const char* de = tuning_env("PIES_PD_REST_DICT");
-    if (s->tetVolumePaired && !(de && de[0] == '0')) {
-      struct Set { float v[16]; bool operator<(const Set& o) const { return std::memcmp(v, o.v, sizeof(v)) < 0; } };
-      std::map<Set, uint16_t> sets;
-      std::vector<uint16_t> index(id.size());
-      std::vector<float4> table;
-      bool ok = true;
-      for (size_t k = 0; ok && k < id.size(); ++k) {
-        const HostTet &a = s->h_tet[s->plan[PIES_TET].order[k]], &b = s->h_volume[k];
-        Set key;
-        std::memcpy(key.v, a.qinv, 9 * sizeof(float));
-        key.v[9] = a.lo; key.v[10] = a.hi; key.v[11] = a.w;
-        key.v[12] = b.qinv[8]; key.v[13] = b.lo; key.v[14] = b.hi; key.v[15] = b.w;
-        auto it = sets.find(key);
-        if (it == sets.end()) {
-          if (sets.size() >= 4096 || (sets.size() + 1) * 16 > id.size()) { ok = false; break; }  // no real compression: per-element arrays
-          it = sets.emplace(key, static_cast<uint16_t>(sets.size())).first;
-          table.push_back(make_float4(key.v[0], key.v[1], key.v[2], key.v[3]));
-          table.push_back(make_float4(key.v[4], key.v[5], key.v[6], key.v[7]));
-          table.push_back(make_float4(key.v[8], key.v[9], key.v[10], key.v[11]));
-          table.push_back(make_float4(key.v[12], key.v[13], key.v[14], key.v[15]));
-        }
-        index[k] = it->second;
-      }
-      s->h_pairDictIndex.clear();
-      if (ok && !index.empty()) {
-        s->h_pairDictIndex = index;
-        if (int rc = upload(s, index, &s->d_pairDictIndex)) return rc;
-        if (int rc = upload(s, table, &s->d_pairDictTable)) return rc;
-        s->pairDictSets = static_cast<uint32_t>(sets.size());
-      }
-    }
+    if (int rc = pd_rest_dictionary(s)) return rc;
     if (int rc = pd_build(s)) return rc;
-    if (n) {  // input of a substep, kept until its solves are known to have met the tolerance (pd_tick_checked)
-      if (int rc = dev_alloc(s, n, &s->snapPos)) return rc;
-      if (int rc = dev_alloc(s, n, &s->snapPrev)) return rc;
-      if (int rc = dev_alloc(s, n, &s->snapVel)) return rc;
-      if (s->pd.shape.count)
-        if (int rc = dev_alloc(s, 4ull * s->pd.shape.count, &s->snapQuat)) return rc;
-    }
+    if (int rc = alloc_pd_snapshots(s)) return rc;
   }
-  if (!s->pcgCeilingSet) {  // node-node contacts stiffen the system (w = 1e5 per contact): a higher ceiling unless the host set one
-    const uint32_t ceiling = s->ncActive ? 256u : 128u;
-    if (s->pcgMaxIters != ceiling) { s->pcgMaxIters = ceiling; s->pcgBudget = std::min(s->pcgBudget, ceiling); }
-  }
+  pcg_ceiling_rule(s);
   if (int rc = capture_graph(s)) return rc;
   s->sceneDirty = false;
   s->graphDirty = false;
@@ -861,7 +390,7 @@ int pies_tick_async(pies_solver_t* s) {
   if (s->device == PIES_DEVICE_NONE) return fail(s, PIES_ERR_HIP, "host-only handle (PIES_DEVICE_NONE): there is no CPU solver");
   if (s->simFailed) return PIES_OK;  // Solver.cpp:26-28
   if (int rc = pies_internal_ensure_ready(s)) return rc;
-  if (s->nd.n == 0) return PIES_OK;
+  if (s->dev.nd.n == 0) return PIES_OK;
   if (s->opt.solver == PIES_SOLVER_PD) {
     // The captured CG budget can only follow the solves at a host synchronisation.  A caller that queues tick after tick
     // without one gets one here every 16 ticks (the queue drains once, ~50 us of idle device): measured without it, 150
@@ -874,8 +403,8 @@ int pies_tick_async(pies_solver_t* s) {
     ++s->asyncSinceSync;
     if (s->goalDirty)
       if (int rc = pd_upload_goals(s)) return rc;
-    if (s->asyncSinceSync == 1) HIP_TRY(s, hipMemsetAsync(s->pd.cg.stats, 0, 4 * sizeof(float), s->stream));
-  } else if (s->nodeCollisions && s->hash.counters) {
+    if (s->asyncSinceSync == 1) HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, 4 * sizeof(float), s->stream));
+  } else if (s->nodeCollisions && s->dev.hash.counters) {
     // The node grid's captured radix passes hold the scene's cell box plus five key bits, and the host can only follow a
     // growing box at a synchronisation (adapt_sort_passes): a caller that queues PBD ticks blindly gets one every 16 ticks,
     // like the PD path above, so that a burst that spreads the particles never outruns the captured passes.
@@ -910,19 +439,19 @@ int pies_synchronize(pies_solver_t* s) {
 // stiffen the system from one substep to the next) is therefore not kept: the node state is put back and the substep
 // runs again with four times the budget, up to the ceiling of pies_set_pcg.
 static int pd_tick_checked(pies_solver* s) {
-  const uint32_t n = s->nd.n;
+  const uint32_t n = s->dev.nd.n;
   float before[8], after[8];
-  HIP_TRY(s, hipMemsetAsync(s->pd.cg.stats, 0, 4 * sizeof(float), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, 4 * sizeof(float), s->stream));
   for (uint32_t sub = 0; sub < s->opt.timeSubsteps; ++sub) {
-    HIP_TRY(s, hipMemcpyAsync(before, s->pd.cg.stats, sizeof(before), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->snapPos, s->nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->snapPrev, s->nd.prev, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->snapVel, s->nd.vel, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    if (s->snapQuat)
-      HIP_TRY(s, hipMemcpyAsync(s->snapQuat, s->pd.shape.quat, 4ull * s->pd.shape.count * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(before, s->dev.pd.cg.stats, sizeof(before), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->dev.snapPos, s->dev.nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->dev.snapPrev, s->dev.nd.prev, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->dev.snapVel, s->dev.nd.vel, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    if (s->dev.snapQuat)
+      HIP_TRY(s, hipMemcpyAsync(s->dev.snapQuat, s->dev.pd.shape.quat, 4ull * s->dev.pd.shape.count * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     for (;;) {
       if (int rc = launch_substep(s)) return rc;
-      HIP_TRY(s, hipMemcpyAsync(after, s->pd.cg.stats, sizeof(after), hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(after, s->dev.pd.cg.stats, sizeof(after), hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(s, hipStreamSynchronize(s->stream));
       const bool ranShort = after[3] > before[3];
       if (!ranShort || s->pcgBudget >= s->pcgMaxIters || s->pcgPinned) {
@@ -930,12 +459,12 @@ static int pd_tick_checked(pies_solver* s) {
         break;
       }
       // put the substep's input back (the statistics too: the attempt does not count) and capture a larger budget
-      HIP_TRY(s, hipMemcpyAsync(s->nd.pos, s->snapPos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(s, hipMemcpyAsync(s->nd.prev, s->snapPrev, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(s, hipMemcpyAsync(s->nd.vel, s->snapVel, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-      if (s->snapQuat)
-        HIP_TRY(s, hipMemcpyAsync(s->pd.shape.quat, s->snapQuat, 4ull * s->pd.shape.count * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(s, hipMemcpyAsync(s->pd.cg.stats, before, sizeof(before), hipMemcpyHostToDevice, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(s->dev.nd.pos, s->dev.snapPos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(s->dev.nd.prev, s->dev.snapPrev, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(s->dev.nd.vel, s->dev.snapVel, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+      if (s->dev.snapQuat)
+        HIP_TRY(s, hipMemcpyAsync(s->dev.pd.shape.quat, s->dev.snapQuat, 4ull * s->dev.pd.shape.count * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(s->dev.pd.cg.stats, before, sizeof(before), hipMemcpyHostToDevice, s->stream));
       HIP_TRY(s, hipStreamSynchronize(s->stream));
       s->pcgBudget = std::min(s->pcgMaxIters, std::max(32u, 4u * s->pcgBudget));
       s->pcgCalm = 0;
@@ -955,7 +484,7 @@ int pies_tick(pies_solver_t* s) {
   if (s->simFailed) return PIES_OK;
   if (s->opt.solver == PIES_SOLVER_PD && s->pcgRetry && s->device != PIES_DEVICE_NONE && !under_profiler()) {
     if (int rc = pies_internal_ensure_ready(s)) return rc;
-    if (s->nd.n == 0) return PIES_OK;
+    if (s->dev.nd.n == 0) return PIES_OK;
     if (s->goalDirty)
       if (int rc = pd_upload_goals(s)) return rc;
     if (int rc = pd_tick_checked(s)) return rc;
@@ -963,7 +492,7 @@ int pies_tick(pies_solver_t* s) {
   } else {
     if (int rc = pies_tick_async(s)) return rc;
   }
-  const uint32_t n = s->nd.n;
+  const uint32_t n = s->dev.nd.n;
   if (n == 0) return PIES_OK;
   // Solver.cpp:157 : _vertices[i].position = position -- one D2H copy per tick; the host mirror's positions are
   // current afterwards (pies_read_nodes / pies_read_positions_strided copy from it without touching the device)
@@ -977,7 +506,7 @@ int pies_tick(pies_solver_t* s) {
 
 // ---- render-state export: frame k leaves through a copy stream while frame k+1 computes -----------------------
 static int export_prepare(pies_solver* s) {
-  const uint32_t n = s->nd.n;
+  const uint32_t n = s->dev.nd.n;
   if (!s->copyStream) {
     HIP_TRY(s, hipStreamCreateWithFlags(&s->copyStream, hipStreamNonBlocking));
     for (int b = 0; b < 2; ++b) {
@@ -1024,21 +553,21 @@ int pies_tick_begin(pies_solver_t* s, uint64_t* frame) {
     return fail(s, PIES_ERR_STATE, "pies_tick_begin: the frame two ticks back is still acquired (pies_export_release it first)");
   if (int rc = pies_tick_async(s)) return rc;  // a failed simulation still hands out (unchanged) frames
   if (int rc = export_prepare(s)) return rc;
-  const uint32_t n = s->nd.n;
+  const uint32_t n = s->dev.nd.n;
   const int b = static_cast<int>(f & 1u);
   if (n) {
     // d_export is free once the previous frame's D2H copy has read it; by now that copy finished long ago
     if (f > 1) HIP_TRY(s, hipStreamWaitEvent(s->stream, s->evCopied[b ^ 1], 0));
-    if (s->d_nodeInv) {  // a renumbered scene: the frame in host numbering
-      launch_gather_nodes(s->stream, s->nd.pos, s->d_export, s->d_nodeInv, n);
+    if (s->dev.d_nodeInv) {  // a renumbered scene: the frame in host numbering
+      launch_gather_nodes(s->stream, s->dev.nd.pos, s->d_export, s->dev.d_nodeInv, n);
       HIP_TRY(s, hipGetLastError());
     } else {
-      HIP_TRY(s, hipMemcpyAsync(s->d_export, s->nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+      HIP_TRY(s, hipMemcpyAsync(s->d_export, s->dev.nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
     }
   }
   const uint32_t nv = n ? s->skin.nVerts : 0u;  // skins: evaluated behind the position copy (d_skinExport is free like d_export)
   if (nv) {
-    launch_skin_positions(s->stream, s->skin, s->nd.pos, s->d_skinExport, 0, nv);
+    launch_skin_positions(s->stream, s->skin, s->dev.nd.pos, s->d_skinExport, 0, nv);
     launch_skin_normals(s->stream, s->skin, s->d_skinExport, s->d_skinExport + 3ull * nv, 0, nv);
     HIP_TRY(s, hipGetLastError());
   }
@@ -1063,7 +592,7 @@ int pies_export_acquire(pies_solver_t* s, uint64_t frame, const float** pos4, ui
   HIP_TRY(s, hipEventSynchronize(s->evCopied[frame & 1u]));
   s->frameAcquired = frame;
   *pos4 = reinterpret_cast<const float*>(s->h_export[frame & 1u]);
-  if (n) *n = s->nd.n;
+  if (n) *n = s->dev.nd.n;
   return PIES_OK;
 }
 
@@ -1095,13 +624,13 @@ int pies_failed(pies_solver_t* s, int* failed) {
 int pies_get_tri_grid_stats(pies_solver_t* s, uint32_t out[8]) {
   if (!s || !out) return PIES_ERR_INVALID;
   for (int i = 0; i < 8; ++i) out[i] = 0;
-  if (s->device == PIES_DEVICE_NONE || !s->pd.tri.counters) return PIES_OK;
+  if (s->device == PIES_DEVICE_NONE || !s->dev.pd.tri.counters) return PIES_OK;
   HIP_TRY(s, hipSetDevice(s->device));
   uint32_t c[16];
-  HIP_TRY(s, hipMemcpyAsync(c, s->pd.tri.counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(c, s->dev.pd.tri.counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   uint32_t lists[64 * 16];
-  HIP_TRY(s, hipMemcpyAsync(lists, s->pd.tri.workCnt, sizeof(lists), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(lists, s->dev.pd.tri.workCnt, sizeof(lists), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   for (int i = 0; i < 64; ++i) out[0] += lists[16 * i];
   out[1] = c[9];
@@ -1112,17 +641,17 @@ int pies_get_tri_grid_stats(pies_solver_t* s, uint32_t out[8]) {
 int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, uint32_t* count) {
   if (!s || !count) return PIES_ERR_INVALID;
   *count = 0;
-  if (s->device == PIES_DEVICE_NONE || !s->pd.tri.counters) return PIES_OK;
+  if (s->device == PIES_DEVICE_NONE || !s->dev.pd.tri.counters) return PIES_OK;
   HIP_TRY(s, hipSetDevice(s->device));
   uint32_t m = 0;
-  HIP_TRY(s, hipMemcpyAsync(&m, s->pd.tri.counters + 2, sizeof(m), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&m, s->dev.pd.tri.counters + 2, sizeof(m), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   *count = m;
   if (ids && m) {
     if (m > capacity) return fail(s, PIES_ERR_INVALID, "pies_get_tri_contacts: capacity too small");
-    HIP_TRY(s, hipMemcpyAsync(ids, s->pd.tri.ids, static_cast<size_t>(m) * sizeof(uint4), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(ids, s->dev.pd.tri.ids, static_cast<size_t>(m) * sizeof(uint4), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
-    if (s->d_nodeInv)  // a renumbered scene: the device lists internal ids
+    if (s->dev.d_nodeInv)  // a renumbered scene: the device lists internal ids
       for (size_t k = 0; k < 4ull * m; ++k)
         if (ids[k] < s->nodeOrder.order.size()) ids[k] = s->nodeOrder.order[ids[k]];
   }
@@ -1132,23 +661,23 @@ int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, ui
 int pies_collision_pairs(pies_solver_t* s, uint64_t* pairs) {
   if (!s || !pairs) return PIES_ERR_INVALID;
   *pairs = 0;
-  if (!s->hash.counters) return PIES_OK;
+  if (!s->dev.hash.counters) return PIES_OK;
   uint32_t v = 0;
   HIP_TRY(s, hipSetDevice(s->device));
-  HIP_TRY(s, hipMemcpyAsync(&v, s->hash.counters + 31, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&v, s->dev.hash.counters + 31, sizeof(v), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  HIP_TRY(s, hipMemsetAsync(s->hash.counters + 31, 0, sizeof(v), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.hash.counters + 31, 0, sizeof(v), s->stream));
   *pairs = v;
   return PIES_OK;
 }
 
 int pies_debug_pair_state(pies_solver_t* s, float* slack, float* excursion, uint32_t* degree, uint32_t n) {
-  if (!s || !s->pairs.ctl || n != s->pairs.n) return PIES_ERR_INVALID;
+  if (!s || !s->dev.pairs.ctl || n != s->dev.pairs.n) return PIES_ERR_INVALID;
   std::vector<float4> node(4ull * n);
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  HIP_TRY(s, hipMemcpy(node.data(), s->pairs.node, node.size() * sizeof(float4), hipMemcpyDeviceToHost));
-  if (excursion) HIP_TRY(s, hipMemcpy(excursion, s->pairs.exc, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(s, hipMemcpy(node.data(), s->dev.pairs.node, node.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  if (excursion) HIP_TRY(s, hipMemcpy(excursion, s->dev.pairs.exc, n * sizeof(float), hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < n; ++i) {
     if (slack) slack[i] = node[4ull * i + 2].w;
     if (degree) std::memcpy(&degree[i], &node[4ull * i + 3].y, sizeof(uint32_t));
@@ -1169,9 +698,9 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds) {
 int pies_get_collision_health(pies_solver_t* s, uint32_t* rounds, uint32_t* pairs_listed, uint32_t* passes_repeated, uint32_t* passes_inexact) {
   if (!s) return PIES_ERR_INVALID;
   uint32_t v[kPairWords] = {0};
-  if (s->pairs.ctl) {
+  if (s->dev.pairs.ctl) {
     HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(v, s->pairs.ctl, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(v, s->dev.pairs.ctl, sizeof(v), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
   if (rounds) *rounds = v[kPairRounds];
@@ -1184,9 +713,9 @@ int pies_get_collision_health(pies_solver_t* s, uint32_t* rounds, uint32_t* pair
 int pies_get_collision_fallbacks(pies_solver_t* s, uint32_t* passes) {
   if (!s || !passes) return PIES_ERR_INVALID;
   *passes = 0;
-  if (s->pairs.ctl) {
+  if (s->dev.pairs.ctl) {
     HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(passes, s->pairs.ctl + kPairFallbacks, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(passes, s->dev.pairs.ctl + kPairFallbacks, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
   return PIES_OK;
@@ -1196,13 +725,13 @@ int pies_collision_stats(pies_solver_t* s, uint64_t* pairs, uint64_t* candidates
   if (!s) return PIES_ERR_INVALID;
   if (pairs) *pairs = 0;
   if (candidates) *candidates = 0;
-  if (!s->hash.counters) return PIES_OK;
+  if (!s->dev.hash.counters) return PIES_OK;
   uint32_t v[kHashCounters];
   HIP_TRY(s, hipSetDevice(s->device));
-  HIP_TRY(s, hipMemcpyAsync(v, s->hash.counters, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(v, s->dev.hash.counters, sizeof(v), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  HIP_TRY(s, hipMemsetAsync(s->hash.counters + kCounterPairs, 0, sizeof(uint32_t), s->stream));
-  HIP_TRY(s, hipMemsetAsync(s->hash.counters + kCounterCandidates, 0, 2 * sizeof(uint32_t), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.hash.counters + kCounterPairs, 0, sizeof(uint32_t), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.hash.counters + kCounterCandidates, 0, 2 * sizeof(uint32_t), s->stream));
   if (pairs) *pairs = v[kCounterPairs];
   if (candidates) *candidates = static_cast<uint64_t>(v[kCounterCandidates]) | (static_cast<uint64_t>(v[kCounterCandidates + 1]) << 32);
   return PIES_OK;
@@ -1223,13 +752,13 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_LINES: *out = (uint32_t)s->h_lines.size(); break;
     case PIES_NODES: *out = s->nodeCount(); break;
     case PIES_SYSTEM_NNZ: *out = s->pd_nnz; break;
-    case PIES_REST_SETS: *out = s->pdLocalPacked && s->d_pairDictIndex ? s->pairDictSets : 0u; break;
-    case PIES_ROW_STENCILS: *out = s->pd.cg.rowStencil ? s->pdRowStencils : 0u; break;
-    case PIES_PD_TILES: *out = s->pd.tiles.ntiles; break;
-    case PIES_PD_TILE_RECORDS: *out = s->pd.tiles.ntiles ? s->pdTileRecords : 0u; break;
+    case PIES_REST_SETS: *out = s->pdLocalPacked && s->dev.d_pairDictIndex ? s->dev.pairDictSets : 0u; break;
+    case PIES_ROW_STENCILS: *out = s->dev.pd.cg.rowStencil ? s->dev.pdRowStencils : 0u; break;
+    case PIES_PD_TILES: *out = s->dev.pd.tiles.ntiles; break;
+    case PIES_PD_TILE_RECORDS: *out = s->dev.pd.tiles.ntiles ? s->pdTileRecords : 0u; break;
     case PIES_PD_CG_SINGLE: *out = s->opt.solver == PIES_SOLVER_PD && pd_single_cg(s) ? 1u : 0u; break;
-    case PIES_PD_WINDOW_ENTRIES: *out = s->pd.cg.wRows ? s->pdWindowEntries : 0u; break;
-    case PIES_PD_WINDOW_HALO: *out = s->pd.cg.wRows ? s->pdWindowHalo : 0u; break;
+    case PIES_PD_WINDOW_ENTRIES: *out = s->dev.pd.cg.wRows ? s->pdWindowEntries : 0u; break;
+    case PIES_PD_WINDOW_HALO: *out = s->dev.pd.cg.wRows ? s->pdWindowHalo : 0u; break;
     case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
     case PIES_SKINS: *out = (uint32_t)s->h_skins.size(); break;
     case PIES_SKIN_VERTICES: {
@@ -1239,7 +768,7 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     }
     case PIES_NODE_CONTACTS: {
       *out = 0;
-      if (s->device != PIES_DEVICE_NONE && s->ncActive && s->nd.n)
+      if (s->device != PIES_DEVICE_NONE && s->dev.ncActive && s->dev.nd.n)
         if (int rc = nc_download(const_cast<pies_solver*>(s), nullptr, out)) return rc;
       break;
     }
@@ -1283,11 +812,11 @@ int pies_write_nodes(pies_solver_t* s, int what, const float* in, uint32_t n) {
   }
   if (!dst->empty()) std::memcpy(dst->data(), in, dst->size() * sizeof(float));
   s->hostNodesDirty = true;
-  if (what == PIES_NODE_RADIUS && s->hash.counters && !s->sceneDirty) {  // the collision grid is sized from the radii
+  if (what == PIES_NODE_RADIUS && s->dev.hash.counters && !s->sceneDirty) {  // the collision grid is sized from the radii
     uint64_t entries;
     bool fast;
     collision_grid_bound(s, entries, fast);
-    if (entries + 64 > s->hash.maxEntries || fast != s->collideFast) s->sceneDirty = true;
+    if (entries + 64 > s->dev.hash.maxEntries || fast != s->collideFast) s->sceneDirty = true;
   }
   return PIES_OK;
 }

@@ -1,4 +1,5 @@
-// Internals shared by the translation units behind the C ABI (capi.cpp: handle lifetime, upload, tick, state access;
+// Internals shared by the translation units behind the C ABI (capi.cpp: handle lifetime, pies_finalize, tick, state access;
+// device_scene.cpp: the steps of pies_finalize that build the scene in HBM, free_device, node upload and read-back;
 // substep_graph.cpp: the substep as a launch sequence, graph capture, the adaptations that follow the scene; profiling.cpp: the
 // timing passes; tuning.cpp: the registry of pies_set_tuning).
 #pragma once
@@ -32,10 +33,24 @@ uint32_t sort_passes_for(uint32_t keyBits);
 int adapt_sort_passes(pies_solver* s);
 int adapt_nc_rounds(pies_solver* s);
 int poll_failure(pies_solver* s);
-// ---- capi.cpp ----
-void free_device(pies_solver* s);
+// ---- device_scene.cpp ----
 bool tet_volume_pairs(const pies_solver* s);
-
+void free_device(pies_solver* s);  // the captured graph, the skins' records, every allocation of s->dev; s->dev starts over
+int upload_nodes(pies_solver* s);
+int download_nodes(pies_solver* s, uint32_t mask = 7u);
+int scene_sync_host(pies_solver* s);  // brings the host mirror up to date before a scene edit
+int build_plans(pies_solver* s, int sched);
+// the steps of pies_finalize, in its order; each returns a PIES_* code
+int alloc_nodes(pies_solver* s);          // node arrays, the read-back stage, the node state, the inverse numbering
+int upload_constraints(pies_solver* s);   // position, distance, strain and bend records in plan order
+int upload_node_pairs(pies_solver* s);    // the node-pair extension: ids, bitmap, node list
+int upload_layer_tables(pies_solver* s);  // schedule LAYERED
+int upload_wave_index(pies_solver* s);    // schedule EXACT
+int alloc_node_grid(pies_solver* s, bool collide);  // ... and, with `collide`, the pair-order lists
+int nc_build(pies_solver* s);             // PIES_FLAG_PD_NODE_CONTACTS
+int pd_rest_dictionary(pies_solver* s);   // PD: volume records and the rest dictionary (before pd_build)
+int alloc_pd_snapshots(pies_solver* s);   // PD: the retry snapshots (after pd_build)
+void pcg_ceiling_rule(pies_solver* s);
 
 }  // namespace pies
 

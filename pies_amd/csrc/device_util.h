@@ -21,7 +21,7 @@ template <class T> int dev_alloc(pies_solver* s, size_t count, T** d, bool zero 
   if (count == 0) return PIES_OK;
   void* p = nullptr;
   HIP_TRY(s, hipMalloc(&p, count * sizeof(T)));
-  s->allocations.push_back(p);
+  s->dev.allocations.push_back(p);
   if (zero) HIP_TRY(s, hipMemsetAsync(p, 0, count * sizeof(T), s->stream));
   *d = static_cast<T*>(p);
   return PIES_OK;

@@ -5,7 +5,7 @@
 // has many more, and the CG iteration slows down about threefold.  pies_finalize therefore sorts the nodes
 // of such a scene along a Hilbert curve of their positions and builds the device scene in that numbering.  The host keeps its
 // own: the host mirror and the containers stay in host numbering, the device scene is built from translated copies
-// (InternalNumbering), and node state crosses the bus through the permutation (capi.cpp: upload_nodes, download_nodes, export).
+// (InternalNumbering), and node state crosses the bus through the permutation (device_scene.cpp: upload_nodes, download_nodes; capi.cpp: export).
 //
 // The decision, made on the host and deterministic:
 //   1. the flag is set and the solver is PD (PBD keeps the identity: its orders are the reference's);

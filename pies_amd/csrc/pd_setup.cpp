@@ -362,7 +362,7 @@ int pd_build(pies_solver* s) {
   }
 
   // ---- HBM ---------------------------------------------------------------------------------------------
-  PdArrays& pd = s->pd;
+  PdArrays& pd = s->dev.pd;
   CgArrays& cg = pd.cg;
   cg.n = n;
   // blocks of every CG launch: one per four slices (4 wavefronts per block).  Measured at 100k rows (substeps/s of config 3):
@@ -404,7 +404,7 @@ int pd_build(pies_solver* s) {
       if (int rc = upload(s, D.rowStencil, &d_rs)) return rc;
       if (int rc = upload(s, D.stencil, &d_st)) return rc;
       cg.rowStencil = d_rs; cg.stencil = reinterpret_cast<const int2*>(d_st);
-      s->pdRowStencils = D.rows;
+      s->dev.pdRowStencils = D.rows;
     }
   }
   cg.lanesPerRow = lpr;
@@ -462,7 +462,7 @@ int pd_build(pies_solver* s) {
     if (int rc = upload(s, tiles.inc, &d_inc)) return rc;
     T.ntiles = static_cast<uint32_t>(tiles.info.size());
     T.info = d_info; T.node = d_node; T.local = d_local; T.nptr = d_nptr; T.inc = d_inc;
-    if (!s->h_pairDictIndex.empty() && s->d_pairDictTable) {
+    if (!s->h_pairDictIndex.empty() && s->dev.d_pairDictTable) {
       std::vector<uint16_t> idx(tiles.elem.size());
       for (size_t k = 0; k < idx.size(); ++k) idx[k] = s->h_pairDictIndex[tiles.elem[k]];
       uint16_t* d_idx;
@@ -655,7 +655,7 @@ int pd_build(pies_solver* s) {
 // transform * (material, 1) in float (glm mat4*vec4), stored as double.  The targets only change when a
 // transform does, so they are evaluated on the host and copied into the fp64 contribution slots.
 int pd_upload_goals(pies_solver* s) {
-  if (!s->goalDirty || !s->pd.contribD) { s->goalDirty = false; return PIES_OK; }
+  if (!s->goalDirty || !s->dev.pd.contribD) { s->goalDirty = false; return PIES_OK; }
   std::vector<double4> out;
   for (const HostGoal& c : s->h_goal)
     for (size_t i = 0; i < c.ids.size(); ++i) {
@@ -666,7 +666,7 @@ int pd_upload_goals(pies_solver* s) {
       out.push_back(make_double4(o[0], o[1], o[2], c.w));
     }
   if (!out.empty()) {
-    HIP_TRY(s, hipMemcpyAsync(s->pd.contribD + s->goalSlotBase, out.data(), out.size() * sizeof(double4), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->dev.pd.contribD + s->goalSlotBase, out.data(), out.size() * sizeof(double4), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
   }
   s->goalDirty = false;

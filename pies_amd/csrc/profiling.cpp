@@ -23,19 +23,19 @@ struct StateGuard {
   float4 *pos = nullptr, *prev = nullptr, *vel = nullptr;
   bool ok = false;
   explicit StateGuard(pies_solver* s_) : s(s_) {
-    const size_t bytes = static_cast<size_t>(s->nd.n) * sizeof(float4);
+    const size_t bytes = static_cast<size_t>(s->dev.nd.n) * sizeof(float4);
     if (!bytes) { ok = true; return; }
     if (hipMalloc((void**)&pos, bytes) != hipSuccess || hipMalloc((void**)&prev, bytes) != hipSuccess || hipMalloc((void**)&vel, bytes) != hipSuccess) return;
-    ok = hipMemcpyAsync(pos, s->nd.pos, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
-         hipMemcpyAsync(prev, s->nd.prev, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
-         hipMemcpyAsync(vel, s->nd.vel, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess;
+    ok = hipMemcpyAsync(pos, s->dev.nd.pos, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
+         hipMemcpyAsync(prev, s->dev.nd.prev, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
+         hipMemcpyAsync(vel, s->dev.nd.vel, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess;
   }
   ~StateGuard() {
-    const size_t bytes = static_cast<size_t>(s->nd.n) * sizeof(float4);
+    const size_t bytes = static_cast<size_t>(s->dev.nd.n) * sizeof(float4);
     if (ok && bytes) {
-      (void)hipMemcpyAsync(s->nd.pos, pos, bytes, hipMemcpyDeviceToDevice, s->stream);
-      (void)hipMemcpyAsync(s->nd.prev, prev, bytes, hipMemcpyDeviceToDevice, s->stream);
-      (void)hipMemcpyAsync(s->nd.vel, vel, bytes, hipMemcpyDeviceToDevice, s->stream);
+      (void)hipMemcpyAsync(s->dev.nd.pos, pos, bytes, hipMemcpyDeviceToDevice, s->stream);
+      (void)hipMemcpyAsync(s->dev.nd.prev, prev, bytes, hipMemcpyDeviceToDevice, s->stream);
+      (void)hipMemcpyAsync(s->dev.nd.vel, vel, bytes, hipMemcpyDeviceToDevice, s->stream);
       (void)hipStreamSynchronize(s->stream);
     }
     if (pos) (void)hipFree(pos);
@@ -55,7 +55,7 @@ int pies_profile_substep(pies_solver_t* s, int kernel, uint32_t* launches, doubl
   if (launches) *launches = 0;
   if (total_ms) *total_ms = 0.0;
   if (units) *units = 0;
-  if (s->nd.n == 0 || s->launchCounts[kernel] == 0) return PIES_OK;
+  if (s->dev.nd.n == 0 || s->launchCounts[kernel] == 0) return PIES_OK;
   // a graph holding ONLY this class's launches of one substep, replayed back to back: the launches form one dependent
   // chain, so wall time / launches is the per-launch device time incl. the kernel boundary.  The working set of one
   // class usually fits the caches: these are isolated-replay times, NOT bandwidth figures (pies_profile_in_situ).
@@ -121,7 +121,7 @@ int pies_profile_in_situ(pies_solver_t* s, int kernel, uint32_t substeps, uint32
   if (launches) *launches = 0;
   if (total_ms) *total_ms = 0.0;
   if (units) *units = 0;
-  if (s->nd.n == 0) return PIES_OK;
+  if (s->dev.nd.n == 0) return PIES_OK;
   StateGuard keep(s);
   if (!keep.ok) return fail(s, PIES_ERR_HIP, "pies_profile_in_situ: no memory to keep the node state aside");
   Probe probe;

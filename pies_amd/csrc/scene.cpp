@@ -259,7 +259,7 @@ void lines_from_distances(pies_solver* s, size_t firstDistance) {
 
 }  // namespace
 
-// declared for capi.cpp
+// device_scene.cpp
 int scene_sync_host(pies_solver* s);  // brings the host mirror up to date before a scene edit
 
 }  // namespace pies

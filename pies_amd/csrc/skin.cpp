@@ -12,7 +12,6 @@
 using namespace pies;
 
 namespace pies {
-int scene_sync_host(pies_solver* s);  // capi.cpp
 
 namespace {
 
@@ -304,7 +303,7 @@ int pies_read_skin(pies_solver_t* s, uint32_t skin, float* positions, float* nor
   if (int rc = pies_internal_ensure_ready(s)) return rc;
   const uint32_t first = s->skinFirst[skin], total = s->skin.nVerts;
   float *dPos = s->d_skinOut, *dNrm = s->d_skinOut + 3ull * total;
-  launch_skin_positions(s->stream, s->skin, s->nd.pos, dPos, first, n);
+  launch_skin_positions(s->stream, s->skin, s->dev.nd.pos, dPos, first, n);
   if (normals) launch_skin_normals(s->stream, s->skin, dPos, dNrm, first, n);
   HIP_TRY(s, hipGetLastError());
   float *hPos = s->h_skinStage, *hNrm = s->h_skinStage + 3ull * n;

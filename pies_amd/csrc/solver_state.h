@@ -175,9 +175,43 @@ struct NodeOrder {
   bool active() const { return !order.empty(); }
 };
 
-template <class T> struct DevArray {
-  T* p = nullptr;
-  size_t n = 0;
+// What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
+// its place, so a field added here needs no line of its own there.  Buffers that outlive a finalize (the pinned stages, the export
+// buffers, the skins' records) and the adapted counts (pcgBudget, pairRounds, sortPasses, ncRounds) are members of pies_solver.
+struct DeviceScene {
+  std::vector<void*> allocations;  // every buffer below, in the order it was allocated
+  NodeArrays nd{nullptr, nullptr, nullptr, nullptr, 0};
+  float* d_pack = nullptr;         // n x 3: a node array's x, y, z packed for the read-back
+  uint32_t* d_nodeInv = nullptr;   // HBM copy of nodeOrder.inv (nullptr: identity)
+  // constraint records, in plan order
+  uint32_t* d_pc_id = nullptr;
+  float4* d_pc_tw = nullptr;
+  uint2* d_dc_ids = nullptr;
+  float2* d_dc_rw = nullptr;
+  uint4* d_tc_ids = nullptr;
+  float4 *d_tc_q0 = nullptr, *d_tc_q1 = nullptr, *d_tc_q2 = nullptr;
+  uint4* d_bc_ids = nullptr;
+  float2* d_bc_aw = nullptr;
+  uint2* d_np_ids = nullptr;       // node-pair extension (PD)
+  uint32_t* d_np_bits = nullptr;   // bitmap over the nodes (device numbering): in a listed pair (floor friction after the pairs' friction)
+  uint32_t* d_np_nodes = nullptr;  // those nodes, ascending, once each
+  uint32_t npNodes = 0;
+  uint4* d_vc_ids = nullptr;       // volume constraints (PD only), host order
+  float4 *d_vc_q0 = nullptr, *d_vc_q1 = nullptr, *d_vc_q2 = nullptr;
+  uint32_t* d_waveIndex = nullptr;  // schedule EXACT, PBD: the items of WavePlan's levels
+  LayerDevice d_layer{};            // schedule LAYERED, PBD
+  HashArrays hash{};                // node grid: node-node collisions (PBD), node-node contacts (PD)
+  PairArrays pairs{};               // pair-ordered resolve (PBD)
+  NodeContactArrays nc{};           // node-node contacts of PD (PIES_FLAG_PD_NODE_CONTACTS)
+  bool ncActive = false;            // ... built by the last pies_finalize (a PD scene with nodes)
+  PdArrays pd{};                    // Projective Dynamics
+  uint16_t* d_pairDictIndex = nullptr;  // PD, paired elements: index of the element's set of constants (rest dictionary), or nullptr
+  float4* d_pairDictTable = nullptr;
+  uint32_t pairDictSets = 0;
+  uint32_t pdRowStencils = 0;       // PD: distinct rows of the system matrix in its row dictionary (0: none)
+  // PD: input of a substep, kept until its solves are known to have met the tolerance (pies_tick runs it again otherwise)
+  float4 *snapPos = nullptr, *snapPrev = nullptr, *snapVel = nullptr;
+  double* snapQuat = nullptr;
 };
 
 }  // namespace pies
@@ -203,24 +237,18 @@ struct pies_solver {
   bool releaseHinge = false;
   bool nodeCollisions = true;
   bool collideFast = true;         // every node's cell range spans at most 2 cells per axis: the parallel visiting order may run
-  uint16_t* d_pairDictIndex = nullptr;  // PD, paired elements: index of the element's set of constants (rest dictionary), or nullptr
-  float4* d_pairDictTable = nullptr;
-  uint32_t pairDictSets = 0;
   std::vector<uint16_t> h_pairDictIndex;  // host copy (the tile plan stores it in tile order)
   uint32_t pdTileRecords = 0;            // sum of the tiles' node counts
   uint32_t pdTiles = 0;                  // PD: tiles of the strain + volume local step (0: per-(element, node) records)
   float pdWindowPadding = 0.0f;         // PD: stored / real entries of the windowed matrix (0: not built)
   uint32_t pdWindowEntries = 0;         // its stored entries
   uint32_t pdWindowHalo = 0;            // its halo entries over all chunks
-  uint32_t pdRowStencils = 0;           // PD: distinct rows of the system matrix in its row dictionary (0: none)
   bool tetVolumePaired = false;    // PD: h_volume[k] and h_tet[k] are the same element for every k (fused local step)
   bool triangleCollisions = true;  // PD point-triangle CCD contacts (Solver.cpp:693-797); extension flag to switch off
   bool renumberNodes = false;      // PIES_FLAG_RENUMBER_NODES: pies_finalize may renumber the nodes of a PD scene (node_order.cpp)
   bool pdNodeContacts = false;     // PIES_FLAG_PD_NODE_CONTACTS: PD detects node-node contacts on the device every substep
-  bool ncActive = false;           // ... and the last pies_finalize built its buffers (a PD scene with nodes)
   pies::NodeOrder nodeOrder;       // the numbering the device holds (decided by the last pies_finalize)
   bool internalIds = false;        // the host containers hold the internal numbering (inside an InternalNumbering scope)
-  uint32_t* d_nodeInv = nullptr;   // HBM copy of nodeOrder.inv (nullptr: identity); freed with the device state
   bool simFailed = false;
   int schedule = PIES_SCHEDULE_DEFAULT;
   int collisionOrderFlag = -1;     // PIES_FLAG_COLLISION_ORDER: -1 follows the schedule (EXACT: reference order, otherwise pair order)
@@ -257,37 +285,14 @@ struct pies_solver {
   // ---- plans ----
   pies::Plan plan[5];  // PIES_POSITION .. PIES_BEND
   pies::WavePlan wave;  // schedule EXACT, PBD: levels of the whole-substep DAG
-  uint32_t* d_waveIndex = nullptr;
   pies::LayerPlan layer;  // schedule LAYERED, PBD
-  pies::LayerDevice d_layer;
 
-  // ---- HBM ----
-  pies::NodeArrays nd{nullptr, nullptr, nullptr, nullptr, 0};
-  uint32_t* d_pc_id = nullptr;
-  float4* d_pc_tw = nullptr;
-  uint2* d_dc_ids = nullptr;
-  float2* d_dc_rw = nullptr;
-  uint4* d_tc_ids = nullptr;
-  float4 *d_tc_q0 = nullptr, *d_tc_q1 = nullptr, *d_tc_q2 = nullptr;
-  uint4* d_bc_ids = nullptr;
-  float2* d_bc_aw = nullptr;
-  uint2* d_np_ids = nullptr;  // node-pair extension (PD)
-  uint32_t* d_np_bits = nullptr;   // bitmap over the nodes (device numbering): in a listed pair (floor friction after the pairs' friction)
-  uint32_t* d_np_nodes = nullptr;  // those nodes, ascending, once each
-  uint32_t npNodes = 0;
-  uint4* d_vc_ids = nullptr;  // volume constraints (PD only), host order
-  float4 *d_vc_q0 = nullptr, *d_vc_q1 = nullptr, *d_vc_q2 = nullptr;
-
-  // ---- node-node collisions (PBD) ----
-  pies::HashArrays hash{};
-  pies::PairArrays pairs{};  // pair-ordered resolve
-  // ---- node-node contacts of PD (PIES_FLAG_PD_NODE_CONTACTS; the node grid above is built for them) ----
-  pies::NodeContactArrays nc{};
-  uint32_t ncRounds = 8;     // friction round launches captured per substep (adapt_nc_rounds follows the passes)
+  // ---- HBM: everything the last pies_finalize built (device_scene.cpp) ----
+  pies::DeviceScene dev;
+  uint32_t ncRounds = 8;     // PD node-node contacts: friction round launches captured per substep (adapt_nc_rounds follows the passes)
   uint32_t ncCalm = 0;       // synchronisations in a row at which fewer would have done
 
   // ---- Projective Dynamics ----
-  pies::PdArrays pd{};
   uint32_t slotBase[6] = {0, 0, 0, 0, 0, 0};  // first contribution slot of each container (5: the node-pair extension)
   uint32_t pd_nnz = 0;
   uint32_t goalSlotBase = 0;  // first fp64 contribution slot of the goal constraints
@@ -301,9 +306,7 @@ struct pies_solver {
   bool triFastRows = false;     // PD graph variant: contact rows of the SpMV summed by k_contact_rows (many contacts)
   uint32_t triQuiet = 0;        // synchronisations without a contact while that variant is active
   uint32_t pcgCooldown = 0;   // synchronisations left before the budget may shrink again after a solve ran out
-  std::vector<void*> allocations;
   float4* h_stage = nullptr;  // pinned staging for the per-tick position read-back
-  float* d_pack = nullptr;    // n x 3: a node array's x, y, z packed for the read-back (freed with the device state)
   size_t h_stage_n = 0;
   // ---- render-state export (Solver.h:42-71): frame k is copied out while frame k+1 computes ----
   hipStream_t copyStream = nullptr;
@@ -327,8 +330,6 @@ struct pies_solver {
   size_t skinExport_n = 0;           // vertices the three export buffers hold
   uint32_t frameSkinVerts[2] = {0, 0};  // skin vertices frame (parity) carries
   // ---- PD: a substep whose solve ends above the tolerance is run again with a larger CG budget (pies_tick) ----
-  float4 *snapPos = nullptr, *snapPrev = nullptr, *snapVel = nullptr;
-  double* snapQuat = nullptr;
   bool pcgRetry = true;
   uint32_t pcgRetries = 0;         // substeps run again since the handle was created
   uint64_t pcgShortSolves = 0;     // solves left above the tolerance (budget at its ceiling, or asynchronous ticks)

@@ -84,7 +84,7 @@ void build_layer_program(const pies_solver* s, std::vector<LayerItem>& prog) {
   }
   steps.push_back({LAYER_VELOCITY, -1, -1});
 
-  const uint64_t N = s->nd.n;
+  const uint64_t N = s->dev.nd.n;
   LayerItem cur;
   bool open = false;
   auto flush = [&] { if (open) prog.push_back(cur); open = false; cur = LayerItem{}; };
@@ -135,7 +135,7 @@ void build_layer_program(const pies_solver* s, std::vector<LayerItem>& prog) {
     if (st.container >= 0) {
       const LayerKind& K = L.kind[st.container];
       seg.ncol = K.ncol[q];
-      seg.colOff = s->d_layer.colOff[st.container][q];
+      seg.colOff = s->dev.d_layer.colOff[st.container][q];
       cur.launch.maxClass = std::max(cur.launch.maxClass, K.maxClass);
       const uint64_t count = K.colOff[q].empty() ? 0 : K.colOff[q].back() - K.colOff[q].front();
       const uint64_t perUnit = st.container == PIES_POSITION ? 44 : st.container == PIES_DISTANCE ? 52 : st.container == PIES_TET ? 160 : 136;
@@ -184,8 +184,8 @@ int collision_order(const pies_solver* s) {
 // The reference's order runs by dependency levels of turns (pair_kernels.hip: launch_collide_turns) from 1 024 nodes on; below that -
 // and with PIES_REFERENCE_TURNS=0 - as the single chain of k_collide_reference, which is also the turns' fallback.
 bool reference_by_turns(const pies_solver* s) {
-  if (const char* e = tuning_env("PIES_REFERENCE_TURNS")) return e[0] != '0' && s->pairs.turnCnt != nullptr;
-  return s->nd.n >= 1024u && s->pairs.turnCnt != nullptr;
+  if (const char* e = tuning_env("PIES_REFERENCE_TURNS")) return e[0] != '0' && s->dev.pairs.turnCnt != nullptr;
+  return s->dev.nd.n >= 1024u && s->dev.pairs.turnCnt != nullptr;
 }
 // (the group lists of k_grid_groups: the group order's, and the list kernels' for ranges wider than two cells per axis)
 bool needs_grid_groups(const pies_solver* s) {
@@ -198,12 +198,12 @@ uint32_t enqueue_collide(pies_solver* s, bool rearm) {
   switch (collision_order(s)) {
     case PIES_COLLISION_ORDER_REFERENCE:
       if (reference_by_turns(s))
-        return launch_collide_turns(s->stream, s->hash, s->pairs, s->nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, s->pairRounds);
-      return launch_collide_reference(s->stream, s->hash, s->nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold);
+        return launch_collide_turns(s->stream, s->dev.hash, s->dev.pairs, s->dev.nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, s->pairRounds);
+      return launch_collide_reference(s->stream, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold);
     case PIES_COLLISION_ORDER_GROUPS:
-      return launch_collide(s->stream, s->hash, s->nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, rearm);
+      return launch_collide(s->stream, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, rearm);
     default:
-      return launch_collide_pairs(s->stream, s->hash, s->pairs, s->nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, s->pairRounds);
+      return launch_collide_pairs(s->stream, s->dev.hash, s->dev.pairs, s->dev.nd, s->opt.gridSpacing, s->opt.friction, s->opt.staticFrictionThreshold, s->pairRounds);
   }
 }
 
@@ -211,16 +211,16 @@ void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_
   hipStream_t st = s->stream;
   std::vector<LayerItem> prog;
   build_layer_program(s, prog);
-  const LayerDevice& d = s->d_layer;
+  const LayerDevice& d = s->dev.d_layer;
   LayerData D{};
   D.nodeList = d.nodeList;
   for (int ph = 0; ph < 4; ++ph) D.tiles[ph] = reinterpret_cast<const uint4*>(d.tiles[ph]);
   D.maxGroupNodes = s->layer.maxGroupNodes;
   D.lpos = d.lpos; D.lrad = d.lrad;
-  D.pc_lid = d.pc_lid; D.pc_tw = s->d_pc_tw;
-  D.dc_lid = d.dc_lid; D.dc_rw = s->d_dc_rw;
-  D.tc_lid = d.tc_lid; D.tc_q0 = s->d_tc_q0; D.tc_q1 = s->d_tc_q1; D.tc_q2 = s->d_tc_q2;
-  D.bc_lid = d.bc_lid; D.bc_aw = s->d_bc_aw;
+  D.pc_lid = d.pc_lid; D.pc_tw = s->dev.d_pc_tw;
+  D.dc_lid = d.dc_lid; D.dc_rw = s->dev.d_dc_rw;
+  D.tc_lid = d.tc_lid; D.tc_q0 = s->dev.d_tc_q0; D.tc_q1 = s->dev.d_tc_q1; D.tc_q2 = s->dev.d_tc_q2;
+  D.bc_lid = d.bc_lid; D.bc_aw = s->dev.d_bc_aw;
   const float dt = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
   const LayerParams P = {s->opt.floorHeight, dt, s->opt.gravity, s->opt.damping, s->opt.friction};
   int cur = -1;  // class of the launch being made: with a probe attached only that class's units are tallied
@@ -231,27 +231,27 @@ void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_
     switch (item.type) {
       case ITEM_COLLIDE: {  // Solver.cpp:81-130
         uint32_t nb = 34, nc = 1;
-        if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->hash, s->nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->nd.n); }
+        if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
         probe_mark(s, PIES_KERNEL_HASH);
-        if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->nd.n); }
+        if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
         probe_mark(s, PIES_KERNEL_COLLIDE);
         if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
         break;
       }
       case ITEM_LAYER:
-        if (ON(PIES_KERNEL_LAYER)) { launch_layer(st, s->nd, D, item.launch, P); U(item.bytes); }
+        if (ON(PIES_KERNEL_LAYER)) { launch_layer(st, s->dev.nd, D, item.launch, P); U(item.bytes); }
         C(PIES_KERNEL_LAYER);
         break;
       case ITEM_LPREDICT:
-        if (ON(PIES_KERNEL_PREDICT)) { launch_lpredict(st, s->nd, D, P); U(s->nd.n); }
+        if (ON(PIES_KERNEL_PREDICT)) { launch_lpredict(st, s->dev.nd, D, P); U(s->dev.nd.n); }
         C(PIES_KERNEL_PREDICT);
         break;
       case ITEM_LVELOCITY:
-        if (ON(PIES_KERNEL_VELOCITY)) { launch_lvelocity(st, s->nd, D, P); U(s->nd.n); }
+        if (ON(PIES_KERNEL_VELOCITY)) { launch_lvelocity(st, s->dev.nd, D, P); U(s->dev.nd.n); }
         C(PIES_KERNEL_VELOCITY);
         break;
       case ITEM_LFLOOR:
-        if (ON(PIES_KERNEL_FLOOR)) { launch_lfloor(st, s->nd, D, P); U(s->nd.n); }
+        if (ON(PIES_KERNEL_FLOOR)) { launch_lfloor(st, s->dev.nd, D, P); U(s->dev.nd.n); }
         C(PIES_KERNEL_FLOOR);
         break;
       case ITEM_LPOSITION:
@@ -260,7 +260,7 @@ void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_
         break;
       case ITEM_TO_NODES:
       case ITEM_FROM_NODES:
-        if (only < 0) launch_lcopy(st, s->nd, D, item.type == ITEM_TO_NODES);
+        if (only < 0) launch_lcopy(st, s->dev.nd, D, item.type == ITEM_TO_NODES);
         break;
     }
   }
@@ -277,16 +277,16 @@ void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* u
   auto U = [&](uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; };
 
   if (s->layer.active) { enqueue_layered_substep(s, only, counts, units); return; }
-  if (ON(PIES_KERNEL_PREDICT)) { launch_predict(st, s->nd, dt, s->opt.gravity); U(s->nd.n); }
+  if (ON(PIES_KERNEL_PREDICT)) { launch_predict(st, s->dev.nd, dt, s->opt.gravity); U(s->dev.nd.n); }
   C(PIES_KERNEL_PREDICT);
   if (s->wave.active) {  // schedule EXACT: the levels of the whole-substep DAG, cut by the collision passes
-    const WaveData W = {s->d_pc_id, s->d_pc_tw, s->d_dc_ids, s->d_dc_rw, s->d_tc_ids, s->d_tc_q0, s->d_tc_q1, s->d_tc_q2, s->d_bc_ids, s->d_bc_aw};
+    const WaveData W = {s->dev.d_pc_id, s->dev.d_pc_tw, s->dev.d_dc_ids, s->dev.d_dc_rw, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_bc_ids, s->dev.d_bc_aw};
     size_t barrier = 0;
     auto collide = [&] {
       uint32_t nb = 34, nc = 1;
-      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->hash, s->nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->nd.n); }
+      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
       probe_mark(s, PIES_KERNEL_HASH);
-      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->nd.n); }
+      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
       probe_mark(s, PIES_KERNEL_COLLIDE);
       if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
     };
@@ -294,7 +294,7 @@ void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* u
       for (; barrier < s->wave.barrierAfter.size() && s->wave.barrierAfter[barrier] == l; ++barrier) collide();
       const WaveLevel& L = s->wave.levels[l];
       if (ON(PIES_KERNEL_WAVE)) {
-        launch_wave(st, s->nd, s->opt.floorHeight, s->d_waveIndex, L, W);
+        launch_wave(st, s->dev.nd, s->opt.floorHeight, s->dev.d_waveIndex, L, W);
         U((uint64_t)L.cnt[0] + L.cnt[1] + L.cnt[2] + L.cnt[3] + L.cnt[4]);
       }
       C(PIES_KERNEL_WAVE);
@@ -304,33 +304,33 @@ void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* u
   for (uint32_t it = 0; it < (s->wave.active ? 0u : s->opt.iterations); ++it) {  // one launch per batch, sweep after sweep
     if (!s->releaseHinge)
       for (const Batch& b : s->plan[PIES_POSITION].batches) {
-        if (ON(PIES_KERNEL_POSITION)) { launch_position(st, s->nd.pos, s->d_pc_id, s->d_pc_tw, b.start, b.count); U(b.count); }
+        if (ON(PIES_KERNEL_POSITION)) { launch_position(st, s->dev.nd.pos, s->dev.d_pc_id, s->dev.d_pc_tw, b.start, b.count); U(b.count); }
         C(PIES_KERNEL_POSITION);
       }
     for (const Batch& b : s->plan[PIES_DISTANCE].batches) {
-      if (ON(PIES_KERNEL_DISTANCE)) { launch_distance(st, s->nd.pos, s->d_dc_ids, s->d_dc_rw, b.start, b.count); U(b.count); }
+      if (ON(PIES_KERNEL_DISTANCE)) { launch_distance(st, s->dev.nd.pos, s->dev.d_dc_ids, s->dev.d_dc_rw, b.start, b.count); U(b.count); }
       C(PIES_KERNEL_DISTANCE);
     }
     for (const Batch& b : s->plan[PIES_TET].batches) {
-      if (ON(PIES_KERNEL_TET)) { launch_tet(st, s->nd.pos, s->d_tc_ids, s->d_tc_q0, s->d_tc_q1, s->d_tc_q2, b.start, b.count); U(b.count); }
+      if (ON(PIES_KERNEL_TET)) { launch_tet(st, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, b.start, b.count); U(b.count); }
       C(PIES_KERNEL_TET);
     }
     for (const Batch& b : s->plan[PIES_BEND].batches) {
-      if (ON(PIES_KERNEL_BEND)) { launch_bend(st, s->nd.pos, s->d_bc_ids, s->d_bc_aw, b.start, b.count); U(b.count); }
+      if (ON(PIES_KERNEL_BEND)) { launch_bend(st, s->dev.nd.pos, s->dev.d_bc_ids, s->dev.d_bc_aw, b.start, b.count); U(b.count); }
       C(PIES_KERNEL_BEND);
     }
     if (s->nodeCollisions) {  // Solver.cpp:81-130
       uint32_t nb = 34, nc = 1;
-      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->hash, s->nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->nd.n); }
+      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
       probe_mark(s, PIES_KERNEL_HASH);
-      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->nd.n); }
+      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
       probe_mark(s, PIES_KERNEL_COLLIDE);
       if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
     }
-    if (ON(PIES_KERNEL_FLOOR)) { launch_floor(st, s->nd, s->opt.floorHeight); U(s->nd.n); }
+    if (ON(PIES_KERNEL_FLOOR)) { launch_floor(st, s->dev.nd, s->opt.floorHeight); U(s->dev.nd.n); }
     C(PIES_KERNEL_FLOOR);
   }
-  if (ON(PIES_KERNEL_VELOCITY)) { launch_velocity(st, s->nd, dt, s->opt.damping, s->opt.friction, s->opt.floorHeight); U(s->nd.n); }
+  if (ON(PIES_KERNEL_VELOCITY)) { launch_velocity(st, s->dev.nd, dt, s->opt.damping, s->opt.friction, s->opt.floorHeight); U(s->dev.nd.n); }
   C(PIES_KERNEL_VELOCITY);
 }
 
@@ -339,18 +339,18 @@ void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* u
 bool pd_single_cg(const pies_solver* s) {
   // (the contact-heavy variant: the rows' contact parts are the merged rows k_contact_csr builds every substep - a gather of a
   // handful of distinct columns by the row's lane; PIES_PD_CG_SINGLE_ROWS=0 keeps the two-launch form with its extra workgroups there)
-  return s->pdSingleCg && (!s->pd.cg.useCAp || s->pdSingleCgRows) && s->pd.cg.lanesPerRow == 1u;
+  return s->pdSingleCg && (!s->dev.pd.cg.useCAp || s->pdSingleCgRows) && s->dev.pd.cg.lanesPerRow == 1u;
 }
 
 // PIES_FLAG_PD_NODE_CONTACTS: launches of the node grid's build (launch_hash_build without the group lists)
-static uint32_t nc_hash_launches(const pies_solver* s) { return s->nd.n ? 6u + 3u * s->sortPasses : 0u; }
+static uint32_t nc_hash_launches(const pies_solver* s) { return s->dev.nd.n ? 6u + 3u * s->sortPasses : 0u; }
 // the contacts' friction (Solver.cpp:398-428) in ascending pair key, then their nodes' floor friction; accounted to COLLIDE, one
 // in-situ bracket around the whole pass
 static void enqueue_nc_friction(pies_solver* s, uint32_t* counts) {
   probe_mark(s, PIES_KERNEL_COLLIDE);
-  NodeContactArrays C = s->nc;
+  NodeContactArrays C = s->dev.nc;
   C.rounds = s->ncRounds;
-  const uint32_t k = launch_nc_friction(s->stream, C, s->hash, s->nd, s->pd.nstatic, s->pd.tri.nt ? s->pd.tri.usedBits : nullptr, s->opt.friction,
+  const uint32_t k = launch_nc_friction(s->stream, C, s->dev.hash, s->dev.nd, s->dev.pd.nstatic, s->dev.pd.tri.nt ? s->dev.pd.tri.usedBits : nullptr, s->opt.friction,
                                         s->opt.staticFrictionThreshold);
   probe_mark(s, PIES_KERNEL_COLLIDE);
   if (counts) counts[PIES_KERNEL_COLLIDE] += k;
@@ -361,22 +361,22 @@ static void enqueue_nc_friction(pies_solver* s, uint32_t* counts) {
 void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
   hipStream_t st = s->stream;
   const float h = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
-  const PdArrays& pd = s->pd;
+  const PdArrays& pd = s->dev.pd;
   int cur = -1;
   auto ON = [&](int k) { const bool on = only < 0 || only == k; cur = k; if (on) probe_mark(s, k); return on; };
   auto C = [&](int k, uint32_t n = 1) { if (k != PIES_KERNEL_PD_SPMV && k != PIES_KERNEL_PD_CG_UPDATE) probe_mark(s, k); if (counts) counts[k] += n; };
   auto U = [&](uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; };
   const uint32_t nDist = (uint32_t)s->h_distance.size(), nTet = (uint32_t)s->h_tet.size(), nVol = (uint32_t)s->h_volume.size();
-  if (ON(PIES_KERNEL_PD_PREDICT)) { launch_pd_predict(st, s->nd, pd, h, s->opt.floorHeight + s->opt.collisionThickness, pd.tri.nt != 0 && only < 0); U(s->nd.n); }
+  if (ON(PIES_KERNEL_PD_PREDICT)) { launch_pd_predict(st, s->dev.nd, pd, h, s->opt.floorHeight + s->opt.collisionThickness, pd.tri.nt != 0 && only < 0); U(s->dev.nd.n); }
   C(PIES_KERNEL_PD_PREDICT);
   const bool tri = pd.tri.nt != 0;
   // the statistics of the substep's last solve are closed by an extra workgroup of the floor-snap launch when there is one
-  const bool statsInStabilize = only < 0 && s->opt.collisionStabilizationIterations > 0 && s->opt.iterations > 0 && s->nd.n != 0;
+  const bool statsInStabilize = only < 0 && s->opt.collisionStabilizationIterations > 0 && s->opt.iterations > 0 && s->dev.nd.n != 0;
   if (tri && only < 0) {  // Solver.cpp:240, 245-248: detection, contact list, their blocks of the system matrix
     const char* side = tuning_env("PIES_TRI_SIDE");  // diagnostics: 0 = always in line, 1 = always beside
     s->triLevelsForked = side ? side[0] != '0' : s->triFastRows;
     const bool levelsInLine = !s->triLevelsForked && pd.cg.useCAp == 0;  // the contact-light variant computes them with the list
-    launch_tri_detect(st, pd.tri, s->nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, s->opt.collisionThickness,
+    launch_tri_detect(st, pd.tri, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, s->opt.collisionThickness,
                       pd.cg.useCAp != 0, levelsInLine);
     // The dependency levels of the list (one workgroup, up to 1 ms with tens of thousands of contacts) are only needed by
     // the sequential passes behind the local/global iterations: a second branch of the substep, joined there.
@@ -393,54 +393,54 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
   }
   // PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the predicted positions (where Solver.cpp:240 detects), after the
   // point-triangle detection so that dinv sees both contributions to the diagonal
-  const bool nc = s->ncActive;
+  const bool nc = s->dev.ncActive;
   if (nc) {
     uint32_t nb = nc_hash_launches(s), nd = 1;  // (nd: the detection's launches)
-    if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->hash, s->nd, s->opt.gridSpacing, s->sortPasses, false); U(s->nd.n); }
+    if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, false); U(s->dev.nd.n); }
     probe_mark(s, PIES_KERNEL_HASH);
-    if (ON(PIES_KERNEL_COLLIDE)) { nd = launch_nc_detect(st, s->hash, s->nc, s->nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv); U(s->nd.n); }
+    if (ON(PIES_KERNEL_COLLIDE)) { nd = launch_nc_detect(st, s->dev.hash, s->dev.nc, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv); U(s->dev.nd.n); }
     probe_mark(s, PIES_KERNEL_COLLIDE);
     if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nd; }
   }
   for (uint32_t it = 0; it < s->opt.iterations; ++it) {
     // local step (Solver.cpp:270-308): position constraints project to a constant, uploaded once
     if (nDist && ON(PIES_KERNEL_PD_LOCAL_DISTANCE)) {
-      launch_pd_local_distance(st, s->nd.pos, s->d_dc_ids, s->d_dc_rw, pd.contrib + s->slotBase[PIES_DISTANCE], nDist);
+      launch_pd_local_distance(st, s->dev.nd.pos, s->dev.d_dc_ids, s->dev.d_dc_rw, pd.contrib + s->slotBase[PIES_DISTANCE], nDist);
       U(nDist);
     }
     if (nDist) C(PIES_KERNEL_PD_LOCAL_DISTANCE);
     if (s->tetVolumePaired && pd.tiles.ntiles) {  // tile-resident: one sum per (tile, node) leaves the chip (pd_tiles.cpp)
       if (ON(PIES_KERNEL_PD_LOCAL_TET)) {
-        launch_pd_local_tiles(st, s->nd.pos, pd.tiles, s->d_pairDictTable, tri && only < 0 ? &pd.tri : nullptr, s->opt.collisionThickness);
+        launch_pd_local_tiles(st, s->dev.nd.pos, pd.tiles, s->dev.d_pairDictTable, tri && only < 0 ? &pd.tri : nullptr, s->opt.collisionThickness);
         U(nTet);
       }
       C(PIES_KERNEL_PD_LOCAL_TET);
     } else if (s->tetVolumePaired) {  // both projections in one launch, accounted to the strain class
       if (ON(PIES_KERNEL_PD_LOCAL_TET)) {
-        launch_pd_local_tet_pair(st, s->nd.pos, s->d_tc_ids, s->d_tc_q0, s->d_tc_q1, s->d_tc_q2, s->d_vc_q2,
+        launch_pd_local_tet_pair(st, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_vc_q2,
                                  pd.contrib + s->slotBase[PIES_TET], pd.contrib + s->slotBase[PIES_VOLUME], nTet,
                                  tri && only < 0 ? &pd.tri : nullptr, s->opt.collisionThickness, s->pdLocalPacked,
-                                 s->pdLocalPacked ? s->d_pairDictIndex : nullptr, s->d_pairDictTable);  // + the contacts' local step
+                                 s->pdLocalPacked ? s->dev.d_pairDictIndex : nullptr, s->dev.d_pairDictTable);  // + the contacts' local step
         U(nTet);
       }
       C(PIES_KERNEL_PD_LOCAL_TET);
     } else {
     if (nTet && ON(PIES_KERNEL_PD_LOCAL_TET)) {
-      launch_pd_local_tet(st, false, s->nd.pos, s->d_tc_ids, s->d_tc_q0, s->d_tc_q1, s->d_tc_q2, pd.contrib + s->slotBase[PIES_TET], nTet);
+      launch_pd_local_tet(st, false, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, pd.contrib + s->slotBase[PIES_TET], nTet);
       U(nTet);
     }
     if (nTet) C(PIES_KERNEL_PD_LOCAL_TET);
     if (nVol && ON(PIES_KERNEL_PD_LOCAL_VOLUME)) {
-      launch_pd_local_tet(st, true, s->nd.pos, s->d_vc_ids, s->d_vc_q0, s->d_vc_q1, s->d_vc_q2, pd.contrib + s->slotBase[PIES_VOLUME], nVol);
+      launch_pd_local_tet(st, true, s->dev.nd.pos, s->dev.d_vc_ids, s->dev.d_vc_q0, s->dev.d_vc_q1, s->dev.d_vc_q2, pd.contrib + s->slotBase[PIES_VOLUME], nVol);
       U(nVol);
     }
     if (nVol) C(PIES_KERNEL_PD_LOCAL_VOLUME);
     }
     if (only < 0) {
-      launch_pd_local_bend(st, s->nd.pos, s->d_bc_ids, s->d_bc_aw, pd.contrib + s->slotBase[PIES_BEND], (uint32_t)s->h_bend.size());
-      launch_pd_local_shape(st, s->nd.pos, pd);                        // goal targets are constants between transform updates
-      launch_pd_local_node_pair(st, s->nd.pos, s->nd.radius, s->d_np_ids, pd.contrib + s->slotBase[5], (uint32_t)s->h_nodePair.size());
-      if (tri && !(s->tetVolumePaired && nTet)) launch_pd_local_tri(st, pd.tri, s->nd.pos, s->opt.collisionThickness);  // Solver.cpp:298-300
+      launch_pd_local_bend(st, s->dev.nd.pos, s->dev.d_bc_ids, s->dev.d_bc_aw, pd.contrib + s->slotBase[PIES_BEND], (uint32_t)s->h_bend.size());
+      launch_pd_local_shape(st, s->dev.nd.pos, pd);                        // goal targets are constants between transform updates
+      launch_pd_local_node_pair(st, s->dev.nd.pos, s->dev.nd.radius, s->dev.d_np_ids, pd.contrib + s->slotBase[5], (uint32_t)s->h_nodePair.size());
+      if (tri && !(s->tetVolumePaired && nTet)) launch_pd_local_tri(st, pd.tri, s->dev.nd.pos, s->opt.collisionThickness);  // Solver.cpp:298-300
     }
     // Solver.cpp:266, 310-349.  (When a node's records are a few tile sums, the residual kernel of the one-launch-per-iteration
     // CG evaluates the right-hand side itself.)
@@ -448,13 +448,13 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     // (node-node contacts: their terms are added to the array k_pd_rhs writes, so the residual kernel does not evaluate it)
     const bool single = pd_single_cg(s), fuseRhs = single && only < 0 && pd.rhsLanes == 1 && s->pdFuseRhs && !pd.cg.useCAp && !nc;
     if (!fuseRhs) {
-      if (ON(PIES_KERNEL_PD_RHS)) { launch_pd_rhs(st, s->nd, pd); U(s->nd.n); }
+      if (ON(PIES_KERNEL_PD_RHS)) { launch_pd_rhs(st, s->dev.nd, pd); U(s->dev.nd.n); }
       C(PIES_KERNEL_PD_RHS);
     } else if (counts) {
       counts[PIES_KERNEL_PD_RHS] += 1;  // (the residual kernel that evaluates the right-hand side is counted - and bracketed - as this class)
     }
     if (nc) {  // the contacts' local step (CollisionConstraint.cpp:10-41, 49-65): w * projected, in list order
-      if (ON(PIES_KERNEL_COLLIDE)) { launch_nc_rhs(st, s->nc, s->nd, pd.rhs); U(s->nd.n); }
+      if (ON(PIES_KERNEL_COLLIDE)) { launch_nc_rhs(st, s->dev.nc, s->dev.nd, pd.rhs); U(s->dev.nd.n); }
       C(PIES_KERNEL_COLLIDE);
     }
     const int overflow = s->pcgOverflow ? (int)(s->pcgMaxIters > s->pcgBudget ? s->pcgMaxIters - s->pcgBudget : 0u) : 0;
@@ -467,17 +467,17 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
       const bool neverExitTuning = neverExitEnv && neverExitEnv[0] == '1';
       const bool probed = neverExitTuning || (s->probe && (s->probe->kernel == PIES_KERNEL_PD_SPMV || s->probe->kernel == PIES_KERNEL_PD_CG_UPDATE));
       auto hook = s->probe ? [](void* ctx, int cls) { probe_mark(static_cast<pies_solver*>(ctx), cls); } : (void (*)(void*, int))nullptr;
-      if (fuseRhs && units && s->probe && s->probe->kernel == PIES_KERNEL_PD_RHS) *units += s->nd.n;
-      if (single) launch_pd_solve1(st, s->nd, pd, (int)s->pcgBudget, s->pcgTol, it == 0, lastSolve, fuseRhs, probed, hook, s, overflow);
-      else launch_pd_solve(st, s->nd, pd, (int)s->pcgBudget, s->pcgTol, -1, it == 0, lastSolve, probed, hook, s, overflow);
-      if (probed && s->probe && units) *units += (uint64_t)s->nd.n * s->pcgBudget;
+      if (fuseRhs && units && s->probe && s->probe->kernel == PIES_KERNEL_PD_RHS) *units += s->dev.nd.n;
+      if (single) launch_pd_solve1(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, it == 0, lastSolve, fuseRhs, probed, hook, s, overflow);
+      else launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, -1, it == 0, lastSolve, probed, hook, s, overflow);
+      if (probed && s->probe && units) *units += (uint64_t)s->dev.nd.n * s->pcgBudget;
     }
     else if (only == PIES_KERNEL_PD_SPMV) {
-      if (single) launch_pd_solve1(st, s->nd, pd, (int)s->pcgBudget, s->pcgTol, true, false, false, true);
-      else launch_pd_solve(st, s->nd, pd, (int)s->pcgBudget, 0.f, 1);
-      U((uint64_t)s->nd.n * s->pcgBudget);
+      if (single) launch_pd_solve1(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, true, false, false, true);
+      else launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, 0.f, 1);
+      U((uint64_t)s->dev.nd.n * s->pcgBudget);
     }
-    else if (only == PIES_KERNEL_PD_CG_UPDATE && !single) { launch_pd_solve(st, s->nd, pd, (int)s->pcgBudget, 0.f, 0); U((uint64_t)s->nd.n * s->pcgBudget); }
+    else if (only == PIES_KERNEL_PD_CG_UPDATE && !single) { launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, 0.f, 0); U((uint64_t)s->dev.nd.n * s->pcgBudget); }
     C(PIES_KERNEL_PD_SPMV, s->pcgBudget);
     if (!single) C(PIES_KERNEL_PD_CG_UPDATE, s->pcgBudget);
   }
@@ -485,28 +485,28 @@ void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* un
     if (s->triLevelsForked) (void)hipStreamWaitEvent(st, s->evJoin, 0);
     // all iterations in one launch (the floor snap of the contacts' nodes between the passes), then the snap of everybody else:
     // idempotent, so once is what the reference's `iterations` times come to
-    launch_tri_stabilize(st, pd.tri, s->nd, s->opt.collisionThickness, pd.nstatic, pd.statp, s->opt.collisionStabilizationIterations);
-    if (s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
+    launch_tri_stabilize(st, pd.tri, s->dev.nd, s->opt.collisionThickness, pd.nstatic, pd.statp, s->opt.collisionStabilizationIterations);
+    if (s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->dev.nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
     // velocities, then the contacts' friction (:431-471), then the floor friction (:473-484).  The floor friction of a node that is
     // in no contact does not wait for the contacts: the velocity kernel applies it; the contacts' pass ends with that of its own nodes
     // (the nodes of node-node contacts and of listed node pairs get their floor friction after their pairs' friction as well)
-    launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits,
-                       nc ? s->nc.cnt : nullptr, s->d_np_bits);
-    if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold, s->d_np_nodes, s->npNodes, pd.nstatic, pd.tri.usedBits,
-                                               nc ? s->nc.cnt : nullptr);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
+    launch_pd_velocity(st, s->dev.nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits,
+                       nc ? s->dev.nc.cnt : nullptr, s->dev.d_np_bits);
+    if (only < 0) launch_pd_node_pair_friction(st, s->dev.nd.pos, s->dev.nd.vel, s->dev.nd.radius, s->dev.d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
+                                               s->opt.staticFrictionThreshold, s->dev.d_np_nodes, s->dev.npNodes, pd.nstatic, pd.tri.usedBits,
+                                               nc ? s->dev.nc.cnt : nullptr);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
     if (nc && only < 0) enqueue_nc_friction(s, counts);
-    launch_tri_friction(st, pd.tri, s->nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
+    launch_tri_friction(st, pd.tri, s->dev.nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
   } else {
-    if (only < 0 && s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));  // the floor snap is idempotent
+    if (only < 0 && s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->dev.nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));  // the floor snap is idempotent
     if (ON(PIES_KERNEL_PD_VELOCITY)) {
-      launch_pd_velocity(st, s->nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true, nullptr,
-                         nc ? s->nc.cnt : nullptr, s->d_np_bits);
-      U(s->nd.n);
+      launch_pd_velocity(st, s->dev.nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true, nullptr,
+                         nc ? s->dev.nc.cnt : nullptr, s->dev.d_np_bits);
+      U(s->dev.nd.n);
     }
-    if (only < 0) launch_pd_node_pair_friction(st, s->nd.pos, s->nd.vel, s->nd.radius, s->d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold, s->d_np_nodes, s->npNodes, pd.nstatic, nullptr,
-                                               nc ? s->nc.cnt : nullptr);
+    if (only < 0) launch_pd_node_pair_friction(st, s->dev.nd.pos, s->dev.nd.vel, s->dev.nd.radius, s->dev.d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
+                                               s->opt.staticFrictionThreshold, s->dev.d_np_nodes, s->dev.npNodes, pd.nstatic, nullptr,
+                                               nc ? s->dev.nc.cnt : nullptr);
     if (nc && only < 0) enqueue_nc_friction(s, counts);
   }
   C(PIES_KERNEL_PD_VELOCITY);
@@ -543,7 +543,7 @@ bool uses_ladder(const pies_solver* s) {
 // makes the ladder entry of (pcgBudget, triFastRows) the graph pies_tick launches
 int select_pd_graph(pies_solver* s) {
   s->pcgBudget = ladder_rung(s, s->pcgBudget);
-  s->pd.cg.useCAp = s->triFastRows ? 1 : 0;
+  s->dev.pd.cg.useCAp = s->triFastRows ? 1 : 0;
   auto it = s->pdLadder.find(static_cast<uint64_t>(s->pcgBudget) | (static_cast<uint64_t>(s->triFastRows ? 1 : 0) << 32));
   if (it == s->pdLadder.end()) return fail(s, PIES_ERR_STATE, "no captured graph for this CG budget");
   s->graph = it->second.graph;
@@ -557,7 +557,7 @@ int select_pd_graph(pies_solver* s) {
 int capture_graph(pies_solver* s) {
   destroy_graph(s);
   std::memset(s->launchCounts, 0, sizeof(s->launchCounts));
-  if (s->nd.n == 0) return PIES_OK;
+  if (s->dev.nd.n == 0) return PIES_OK;
   if (const char* e = tuning_env("PIES_NO_GRAPH"); e && e[0] == '1') {
     // count launches without running them: a capture that is thrown away
     HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -573,13 +573,13 @@ int capture_graph(pies_solver* s) {
     const uint32_t wantBudget = s->pcgBudget;
     const bool wantRows = s->triFastRows;
     const std::vector<uint32_t> rungs = ladder_rungs(s);
-    const int variants = s->pd.tri.nt ? 2 : 1;
+    const int variants = s->dev.pd.tri.nt ? 2 : 1;
     for (int v = 0; v < variants; ++v)
       for (uint32_t r : rungs) {
         const bool rows = variants == 2 ? v != 0 : wantRows;
         s->pcgBudget = r;
         s->triFastRows = rows;
-        s->pd.cg.useCAp = rows ? 1 : 0;
+        s->dev.pd.cg.useCAp = rows ? 1 : 0;
         pies_solver::PdGraph g;
         HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
         enqueue_substep(s, g.counts);
@@ -606,10 +606,10 @@ int capture_graph(pies_solver* s) {
 // and quadruples (at least 32, at most pcgMaxIters = 128 by default) when a solve ran out of iterations above the tolerance.
 int adapt_pcg_budget(pies_solver* s) {
   s->asyncSinceSync = 0;  // (called right after a host synchronisation)
-  if (s->opt.solver != PIES_SOLVER_PD || !s->pd.cg.stats || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
+  if (s->opt.solver != PIES_SOLVER_PD || !s->dev.pd.cg.stats || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
   if (s->pcgPinned) return PIES_OK;  // PIES_PCG_BUDGET: tests of the overflow path keep the captured budget where they put it
   float st[4] = {0, 0, 0, 0};
-  HIP_TRY(s, hipMemcpyAsync(st, s->pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (st[2] == 0.0f) return PIES_OK;  // no solve since the statistics were reset
   const uint32_t used = static_cast<uint32_t>(st[1]);
@@ -661,10 +661,10 @@ int adapt_pcg_budget(pies_solver* s) {
   // wavefront per node).  Either variant is correct with any number of contacts; the switch only follows what the last
   // substep saw (on at 512 contacts, off after 120 synchronisations without any).
   bool fastRows = s->triFastRows;
-  if (s->pd.tri.nt && s->pd.tri.counters) {
+  if (s->dev.pd.tri.nt && s->dev.pd.tri.counters) {
     const int force = [] { const char* e = tuning_env("PIES_TRI_FAST_ROWS"); return e ? std::atoi(e) : -1; }();
     uint32_t contacts = 0;
-    HIP_TRY(s, hipMemcpyAsync(&contacts, s->pd.tri.counters + 2, sizeof(contacts), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&contacts, s->dev.pd.tri.counters + 2, sizeof(contacts), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     if (contacts >= 512) { fastRows = true; s->triQuiet = 0; }
     else if (contacts == 0 && fastRows && ++s->triQuiet >= 120) { fastRows = false; s->triQuiet = 0; }
@@ -678,7 +678,7 @@ int adapt_pcg_budget(pies_solver* s) {
   if (budget != s->pcgBudget || fastRows != s->triFastRows) {
     s->pcgBudget = budget;
     s->triFastRows = fastRows;
-    s->pd.cg.useCAp = fastRows ? 1 : 0;
+    s->dev.pd.cg.useCAp = fastRows ? 1 : 0;
     return s->pdLadder.empty() ? capture_graph(s) : select_pd_graph(s);  // (another executable graph of the ladder: no capture)
   }
   return PIES_OK;
@@ -688,13 +688,13 @@ int adapt_pcg_budget(pies_solver* s) {
 // that finds nothing to do costs 2.5 us, and each pass captures the launches twice - once for its repeat).  Deeper orders than
 // captured are finished by the single-workgroup tail kernel, so a short count is slow, never wrong.
 int adapt_pair_rounds(pies_solver* s) {
-  if (!s->pairs.ctl || s->pairRoundsPinned || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
+  if (!s->dev.pairs.ctl || s->pairRoundsPinned || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
   if (s->opt.solver != PIES_SOLVER_PBD || !s->nodeCollisions) return PIES_OK;
   uint32_t deepest = 0;
-  HIP_TRY(s, hipMemcpyAsync(&deepest, s->pairs.ctl + kPairDeepest, sizeof(deepest), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&deepest, s->dev.pairs.ctl + kPairDeepest, sizeof(deepest), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (deepest == 0) return PIES_OK;  // no pass since the last look
-  HIP_TRY(s, hipMemsetAsync(s->pairs.ctl + kPairDeepest, 0, sizeof(uint32_t), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.pairs.ctl + kPairDeepest, 0, sizeof(uint32_t), s->stream));
   uint32_t rounds = s->pairRounds;
   // (the reference's order by turns runs deeper than the pair order: ~850 levels per pass of config 4)
   const uint32_t cap = collision_order(s) == PIES_COLLISION_ORDER_REFERENCE ? 4096u : 1024u;
@@ -716,10 +716,10 @@ int adapt_pair_rounds(pies_solver* s) {
 // times the volume); a build whose key does not fit the captured passes latches a failure (k_grid_box).
 uint32_t sort_passes_for(uint32_t keyBits) { return std::max(1u, std::min(6u, (keyBits + 5u + 10u) / 11u)); }
 int adapt_sort_passes(pies_solver* s) {
-  if (!s->hash.counters || s->sceneDirty || under_profiler()) return PIES_OK;
-  if ((s->opt.solver != PIES_SOLVER_PBD || !s->nodeCollisions) && !s->ncActive) return PIES_OK;
+  if (!s->dev.hash.counters || s->sceneDirty || under_profiler()) return PIES_OK;
+  if ((s->opt.solver != PIES_SOLVER_PBD || !s->nodeCollisions) && !s->dev.ncActive) return PIES_OK;
   int box[6];
-  HIP_TRY(s, hipMemcpyAsync(box, s->hash.counters + kCounterBoxMin, sizeof(box), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(box, s->dev.hash.counters + kCounterBoxMin, sizeof(box), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   uint32_t bits = 0;
   for (int a = 0; a < 3; ++a) {
@@ -743,13 +743,13 @@ int adapt_sort_passes(pies_solver* s) {
 // (two more than it needed; one when no pass had a contact), growing at once and shrinking after 8 calm synchronisations.  A pass
 // deeper than captured is finished by the single-workgroup tail kernel: slow, never wrong.
 int adapt_nc_rounds(pies_solver* s) {
-  if (!s->ncActive || !s->nc.ctl || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
+  if (!s->dev.ncActive || !s->dev.nc.ctl || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
   if (tuning_env("PIES_PD_NODE_CONTACT_ROUNDS")) return PIES_OK;  // pinned at finalize
   uint32_t deepest = 0;
-  HIP_TRY(s, hipMemcpyAsync(&deepest, s->nc.ctl + kNcDeepest, sizeof(deepest), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&deepest, s->dev.nc.ctl + kNcDeepest, sizeof(deepest), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (deepest == 0) return PIES_OK;  // no pass since the last look
-  HIP_TRY(s, hipMemsetAsync(s->nc.ctl + kNcDeepest, 0, sizeof(uint32_t), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.nc.ctl + kNcDeepest, 0, sizeof(uint32_t), s->stream));
   const uint32_t depth = deepest - 1u;
   const uint32_t want = depth == 0 ? 1u : std::min(kNcMaxRounds, depth + 2u);
   uint32_t rounds = s->ncRounds;
@@ -764,14 +764,14 @@ int adapt_nc_rounds(pies_solver* s) {
 }
 
 int poll_failure(pies_solver* s) {
-  uint32_t* flagWord = s->hash.counters ? s->hash.counters + 3 : s->pd.tri.counters ? s->pd.tri.counters + 3 : nullptr;
+  uint32_t* flagWord = s->dev.hash.counters ? s->dev.hash.counters + 3 : s->dev.pd.tri.counters ? s->dev.pd.tri.counters + 3 : nullptr;
   if (s->simFailed || !flagWord || s->device == PIES_DEVICE_NONE) return PIES_OK;
   uint32_t flag = 0;
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipMemcpyAsync(&flag, flagWord, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
-  if (s->ncActive && s->pd.tri.counters) {  // PD with node-node contacts: the point-triangle pipeline's word as well
+  if (s->dev.ncActive && s->dev.pd.tri.counters) {  // PD with node-node contacts: the point-triangle pipeline's word as well
     uint32_t triFlag = 0;
-    HIP_TRY(s, hipMemcpyAsync(&triFlag, s->pd.tri.counters + 3, sizeof(triFlag), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&triFlag, s->dev.pd.tri.counters + 3, sizeof(triFlag), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     flag |= triFlag;
   }
@@ -780,7 +780,7 @@ int poll_failure(pies_solver* s) {
     s->simFailed = true;
     if (flag & kNcOverflowFlag) {
       s->error = "PD node-node contact list overflow: a node has more contact partners than PIES_PD_NODE_CONTACT_PARTNERS (" +
-                 std::to_string(s->nc.cap) + ")";
+                 std::to_string(s->dev.nc.cap) + ")";
       return PIES_OK;
     }
     s->error = flag & 2    ? "node-node collision grid overflow (more cells or entries than reserved)"
