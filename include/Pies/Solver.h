@@ -9,8 +9,10 @@
 //
 // Differences from the reference, all documented in DESIGN.md: tick() runs on the GPU; getters return
 // host mirrors refreshed once per tick (Solver.cpp:157,393 refresh per substep, which nothing can observe);
-// addTriMeshVolume needs tetgen, which is not part of this build (addTetMeshVolume takes tetgen's output arrays, or
-// just elements, and does what addTriMeshVolume does after its tetrahedralize() call); errors surface as std::runtime_error carrying pies_last_error().
+// addTriMeshVolume works without tetgen (not part of this build): the cells of a lattice that lie inside the surface become
+// tetrahedra - a lattice body with a staircase collision surface - and the input mesh is carried along as a skin
+// (lastTriMeshSkin), not as the first nodes of a conforming mesh; addTetMeshVolume takes tetgen's output arrays, or just
+// elements, for hosts that mesh offline; errors surface as std::runtime_error carrying pies_last_error().
 // Shape/goal matching (regions, createShapeMatching*) are Projective-Dynamics constraints, as in the reference.
 #pragma once
 
@@ -75,6 +77,8 @@ public:
   bool renumberNodes = false;       // extension: PD may keep the nodes in a space-filling-curve order on the device
                                     // (PIES_FLAG_RENUMBER_NODES); getVertices() and every id stay the host's
   bool pdNodeContacts = false;      // extension: PD detects node-node contacts every substep (PIES_FLAG_PD_NODE_CONTACTS)
+  uint32_t triMeshResolution = 16;  // extension: lattice cells along the longest axis of an addTriMeshVolume body
+  uint32_t lastTriMeshSkin = 0;     // extension: the skin id of the last addTriMeshVolume body (getSkinVertices / getSkinNormals)
 
   // Like the reference's (Solver.h:54-55: `Solver() = default`, a converting constructor from the options): constructing a
   // Solver touches no device.  The device handle is opened by the first call that needs it (add*/create*/tick), which is
@@ -104,6 +108,8 @@ public:
       triangleCollisions = rhs.triangleCollisions;
       renumberNodes = rhs.renumberNodes;
       pdNodeContacts = rhs.pdNodeContacts;
+      triMeshResolution = rhs.triMeshResolution;
+      lastTriMeshSkin = rhs.lastTriMeshSkin;
     }
     return *this;
   }
@@ -172,10 +178,29 @@ public:
     _ck(pies_add_nodes(_handle(), static_cast<uint32_t>(vertices.size()), p.data(), nullptr));
     _syncRenderState();
   }
-  void addTriMeshVolume(const std::vector<glm::vec3>&, const std::vector<uint32_t>&, const glm::vec3&, float, float, float, float,
-                        float, float, float) {
-    throw std::runtime_error("Pies::Solver::addTriMeshVolume needs tetgen (not part of this build): tetrahedralise offline and "
-                             "call addTetMeshVolume");
+  // PrimitiveUtilities.cpp:164-328 without tetgen (pies_add_tri_mesh_volume in pies_hip.h states the rules): the closed surface
+  // `vertices` / `indices` (three per triangle) is laid over a lattice of `triMeshResolution` cells along its longest axis; the
+  // cells whose centre lies inside (winding numbers, evaluated on the device) or that hold an input vertex become six tetrahedra
+  // each, with mass = density per node and one strain and one volume constraint per element when the respective stiffness is not
+  // 0.  The result is a LATTICE body: getTriangles() gains its staircase boundary, and the input mesh itself is bound to the
+  // elements as a skin - getSkinVertices(lastTriMeshSkin) / getSkinNormals(lastTriMeshSkin) follow the body every tick.  It is
+  // not tetgen's conforming mesh, where the input vertices are the first nodes.
+  void addTriMeshVolume(const std::vector<glm::vec3>& vertices, const std::vector<uint32_t>& indices, const glm::vec3& initialVelocity,
+                        float density, float strainStiffness, float minStrain, float maxStrain, float volumeStiffness, float compression,
+                        float stretching) {
+    std::vector<float> p = _flatten(vertices);
+    const float v[3] = {initialVelocity[0], initialVelocity[1], initialVelocity[2]};
+    uint32_t id = 0;
+    _ck(pies_add_tri_mesh_volume(_handle(), static_cast<uint32_t>(vertices.size()), p.data(), static_cast<uint32_t>(indices.size() / 3),
+                                 indices.data(), v, density, strainStiffness, minStrain, maxStrain, volumeStiffness, compression,
+                                 stretching, triMeshResolution, nullptr, nullptr, nullptr, &id));
+    lastTriMeshSkin = id;
+    _skinVertices.resize(id + 1);
+    _skinNormals.resize(id + 1);
+    _skinVertices[id].resize(vertices.size());
+    _skinNormals[id].resize(vertices.size());
+    _refreshSkin(id);
+    _syncRenderState();
   }
   // addTriMeshVolume after its tetrahedralize() call (PrimitiveUtilities.cpp:243-328), for hosts that mesh offline:
   // `vertices`, `tetIndices` (4 per element), `triFaceIndices` (3 per face) and `face2tet` (2 per face, -1 = no element on

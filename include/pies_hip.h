@@ -256,6 +256,53 @@ int pies_add_skin(pies_solver_t* s, uint32_t n_vertices, const float* positions,
 int pies_get_skin_binding(const pies_solver_t* s, uint32_t skin, uint32_t* tet, uint32_t* node_ids, float* weights, uint32_t capacity,
                           uint32_t* n);
 
+/* EXTENSION: the generalised winding number of a triangle mesh at the CELL CENTRES of a lattice, evaluated on the device; the
+ * diagnostics and the test surface of the kernel pies_add_tri_mesh_volume classifies cells with.  Sample (i, j, k) of the
+ * dims = (nx, ny, nz) lattice is c = origin + ((i, j, k) + 0.5) * cell and has index (i * ny + j) * nz + k (k fastest, the node
+ * order of pies_create_tet_box).  For a triangle (a, b, d), in fp32 without fused multiply-adds: A = a - c, B = b - c, D = d - c
+ * with lengths la, lb, ld; num = det [A, B, D] = A.x (B.y D.z - D.y B.z) - B.x (A.y D.z - D.y A.z) + D.x (A.y B.z - B.y A.z);
+ * den = la lb ld + (A.B) ld + (B.D) la + (D.A) lb, summed left to right; Omega = 2 atan2f(num, den), and 0 when num and den are
+ * both 0 or Omega is not finite.  w(c) = (sum of Omega over the triangles in ascending index, left to right) / (4 pi).  One lane
+ * owns one sample and walks every triangle itself: no atomics, two calls agree bit for bit.  winding (n samples floats) and
+ * inside (n samples bytes: |w| > 0.5) may each be NULL.  Launched on the handle's stream, outside the captured substep; the scene
+ * is neither read nor changed.  PIES_ERR_INVALID: a NULL array, no vertices or triangles, a triangle index >= n_vertices, a
+ * non-finite vertex or origin, cell not finite or <= 0, a zero in dims.  PIES_ERR_UNSUPPORTED: more than 2^26 samples or more
+ * than 2^24 triangles.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first). */
+int pies_voxelize_tri_mesh(pies_solver_t* s, uint32_t n_vertices, const float* positions, uint32_t n_triangles,
+                           const uint32_t* tri_ids, const float origin[3], float cell, const uint32_t dims[3],
+                           float* winding, uint8_t* inside);
+/* Solver::addTriMeshVolume (PrimitiveUtilities.cpp:164-328) without tetgen: a closed triangle mesh becomes a LATTICE body - the
+ * cells of a uniform lattice that lie inside the surface, six tetrahedra each - with a staircase collision surface, and the input
+ * mesh rides on it as a skin (pies_add_skin).  It is not tetgen's conforming mesh: the input vertices are not nodes.  The rules,
+ * all in fp32:
+ *  lattice   lo, hi = bounds of the vertices, extent = hi - lo; cell = (largest extent) / resolution;
+ *            n_a = max(1, ceil(extent_a / cell)) cells per axis; origin_a = lo_a - 0.5 (n_a cell - extent_a).
+ *  cells     cell (i, j, k), index (i ny + j) nz + k, is kept when |w(centre)| > 0.5 (pies_voxelize_tri_mesh on this lattice:
+ *            the winding direction of the input does not matter) OR when it contains an input vertex, the cell of vertex v being
+ *            floor((v_a - origin_a) / cell) clamped to [0, n_a - 1] per axis - so every input vertex lies in an element and a
+ *            feature thinner than a cell becomes cells, not a binding failure.
+ *  nodes     the lattice points origin + (i, j, k) cell that are a corner of a kept cell, numbered in ascending (i, j, k), k
+ *            fastest; velocity = the argument, invMass = 1 / density (the reference's "mass = density", :176),
+ *            radius = min(0.5, 0.95 * 0.5 * cell) (the reference's 0.5, :177, would overlap every neighbour on a fine lattice;
+ *            pies_create_tet_box uses the second expression).
+ *  elements  kept cells in ascending index, each as the six tetrahedra of pies_create_tet_box in its node order and its order of
+ *            the six; one strain (strain_stiffness, min_strain, max_strain) and one volume (volume_stiffness, compression,
+ *            stretching) constraint per element, each kind only when its stiffness is not 0 (:293-315).  No colour hints: the
+ *            schedulers colour the body like any unstructured mesh.
+ *  triangles every element face that belongs to exactly one element, wound so that its normal points away from the element's
+ *            fourth vertex (outward), in the order: elements ascending, faces opposite vertex 0, 1, 2, 3.
+ *  skin      the input vertices and triangles, bound to the new elements by pies_add_skin's rule with
+ *            max_distance = 8 FLT_EPSILON max(cell, largest |coordinate| of the lattice's corners); skin_id receives its id.
+ * first_node, n_nodes, n_tets, skin_id may each be NULL.  PIES_ERR_INVALID: a NULL array, resolution == 0, no vertices or
+ * triangles, a non-finite vertex, a triangle index >= n_vertices, a largest extent of 0, density <= 0, no kept cell.
+ * PIES_ERR_UNSUPPORTED: the limits of pies_voxelize_tri_mesh.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are
+ * checked first).  All or nothing: on any failure the scene holds exactly the nodes, constraints, triangles and skins it held
+ * before.  pies_clear drops the body and its skin like any other scene content. */
+int pies_add_tri_mesh_volume(pies_solver_t* s, uint32_t n_vertices, const float* positions, uint32_t n_triangles,
+                             const uint32_t* tri_ids, const float velocity[3], float density, float strain_stiffness,
+                             float min_strain, float max_strain, float volume_stiffness, float compression, float stretching,
+                             uint32_t resolution, uint32_t* first_node, uint32_t* n_nodes, uint32_t* n_tets, uint32_t* skin_id);
+
 /* ---- configuration -------------------------------------------------------------------------- */
 int pies_set_flag(pies_solver_t* s, int flag, int value);
 /* Solver::tickPBD / Solver::tickPD (Solver.h:62-63) run the named solver whatever SolverOptions::solver says: this switches

@@ -58,6 +58,7 @@ SYMBOLS = [
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
+    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume",
 ]
 
 
@@ -168,6 +169,8 @@ def load():
     sig["pies_get_skin_binding"] = [vp, u32, pu, pu, pf, u32, pu]
     sig["pies_read_skin"] = [vp, u32, pf, pf, u32]
     sig["pies_export_acquire_skin"] = [vp, C.c_uint64, u32, C.POINTER(pf), C.POINTER(pf), pu]
+    sig["pies_voxelize_tri_mesh"] = [vp, u32, pf, u32, pu, pf, f32, pu, pf, C.POINTER(C.c_uint8)]
+    sig["pies_add_tri_mesh_volume"] = [vp, u32, pf, u32, pu, pf, f32, f32, f32, f32, f32, f32, f32, u32, pu, pu, pu, pu]
     sig["pies_get_pd_tile_plan"] = [vp, pu, pu, pu, pu, pu, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), u32]
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -376,6 +379,31 @@ class Solver:
         p, q, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_uint32()
         self._ck(self._L.pies_export_acquire_skin(self._h, frame, skin, C.byref(p), C.byref(q), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value, 3)), np.ctypeslib.as_array(q, shape=(n.value, 3))
+
+    def voxelize_tri_mesh(self, vertices, triangles, origin, cell, dims):
+        """pies_voxelize_tri_mesh: (winding numbers float32, inside mask bool) of the cell centres origin + ((i, j, k) + 0.5) cell
+        of the dims = (nx, ny, nz) lattice, both shaped dims (k fastest), evaluated on the device."""
+        v = _f32(vertices).reshape(-1, 3)
+        tri = _u32(triangles).reshape(-1, 3)
+        o, d = _f32(origin).reshape(3), _u32(dims).reshape(3)
+        w = np.empty(tuple(int(x) for x in d), np.float32)
+        inside = np.empty(w.shape, np.uint8)
+        self._ck(self._L.pies_voxelize_tri_mesh(self._h, len(v), _pf(v), len(tri), _pu(tri), _pf(o), cell, _pu(d), _pf(w),
+                                                inside.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return w, inside.astype(bool)
+
+    def add_tri_mesh_volume(self, vertices, triangles, resolution, velocity=(0, 0, 0), density=1.0, strain_stiffness=1.0,
+                            min_strain=0.8, max_strain=1.0, volume_stiffness=1.0, compression=1.0, stretching=1.0):
+        """pies_add_tri_mesh_volume: a closed triangle mesh as a lattice body (the cells inside the surface, six tetrahedra each)
+        with the mesh bound to it as a skin.  Returns (first node, nodes, elements, skin id)."""
+        v = _f32(vertices).reshape(-1, 3)
+        tri = _u32(triangles).reshape(-1, 3)
+        vel = _f32(velocity).reshape(3)
+        out = [C.c_uint32() for _ in range(4)]
+        self._ck(self._L.pies_add_tri_mesh_volume(self._h, len(v), _pf(v), len(tri), _pu(tri), _pf(vel), density, strain_stiffness,
+                                                  min_strain, max_strain, volume_stiffness, compression, stretching, resolution,
+                                                  *[C.byref(x) for x in out]))
+        return tuple(x.value for x in out)
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))
