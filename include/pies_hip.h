@@ -88,7 +88,13 @@ enum {
   PIES_NODE_CONTACTS = 20,     /* pies_count only: node-node contacts of the last PD substep (PIES_FLAG_PD_NODE_CONTACTS; synchronises),
                                   0 before the first tick and without the flag */
   PIES_SKINS = 21,             /* pies_count only: embedded surface meshes (pies_add_skin), an EXTENSION */
-  PIES_SKIN_VERTICES = 22      /* pies_count only: their vertices, over all skins */
+  PIES_SKIN_VERTICES = 22,     /* pies_count only: their vertices, over all skins */
+  PIES_LAYER_REST_SETS = 23,   /* pies_count only: distinct sets of rest constants (Qinv, strain limits, w) in the rest dictionary of
+                                  schedule LAYERED's tetrahedral container (PBD), 0: the per-element arrays are read (after
+                                  pies_finalize; tuning switch PIES_LAYER_REST_DICT=0 forces 0) */
+  PIES_LAYER_MAX_TILES = 24    /* pies_count only: tiles (= workgroups of a launch) of the phase of schedule LAYERED's plan that has
+                                  most, 0 when the plan is not active (after pies_finalize); more than the device's 256 compute
+                                  units select the four-wavefronts-per-SIMD kernel variants */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.
@@ -392,7 +398,8 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
 /* Tuning and diagnostic switches, process wide, by name (value NULL or "" unsets): graph variants and sizes that tests and
  * profiling scripts pin - PIES_PCG_BUDGET, PIES_PCG_OVERFLOW, PIES_TRI_FAST_ROWS, PIES_TRI_LDS, PIES_ROW_MAX_UNIQUE, PIES_TRI_SIDE, PIES_TRI_TEAM,
  * PIES_NO_GRAPH, PIES_NO_WAVEFRONT, PIES_NO_TET_PAIRS, PIES_PD_LOCAL_PACKED (0: one element per lane in the PD strain + volume step),
- * PIES_PD_REST_DICT (0: per-element constants instead of the rest dictionary), PIES_PD_ROW_DICT (0: the PD system matrix as SELL
+ * PIES_PD_REST_DICT (0: per-element constants instead of the rest dictionary), PIES_LAYER_REST_DICT (0: the same for the tetrahedral
+ * container of schedule LAYERED, PBD), PIES_PD_ROW_DICT (0: the PD system matrix as SELL
  * arrays only, no row dictionary), PIES_LAYER_PLAN (0: schedule LAYERED's original plan only, 1: + single-level constraints dealt to either group, 2: + slabs by position; default 2) / _PLAN_FORCE (candidate index) / _SLAB / _SLAB_OFFSET, PIES_LAYER_ONE_STRIP_MAX / _TILE_NODES / _STRIPS_MIN_NODES / PIES_LAYER_BLOCK,
  * PIES_PD_TILE_ELEMS (0: per-(element, node) records instead of the tile-resident local step), PIES_PD_CG_SINGLE / _SINGLE_ROWS (0: the
  * two-launch CG everywhere / in the contact-heavy variant), PIES_PD_FUSE_RHS (0: k_pd_rhs), PIES_PD_RHS_LANES,
@@ -488,6 +495,14 @@ int pies_profile_in_situ(pies_solver_t* s, int kernel, uint32_t substeps, uint32
  * corner).  Any array pointer but info may be NULL. */
 int pies_get_pd_tile_plan(pies_solver_t* s, uint32_t* n_tiles, uint32_t* info, uint32_t* node, uint32_t* elem, uint32_t* local, uint16_t* nptr,
                           uint16_t* inc, uint32_t tile_capacity);
+/* The tetrahedral rest dictionary of schedule LAYERED (PIES_LAYER_REST_SETS), for inspection and tests; no handle is needed.
+ * pack: four tile-local node ids (13 bits each, <= 8191) and a set index (12 bits) into the element's two record words;
+ * PIES_ERR_INVALID when one does not fit.  unpack: the inverse.  usable: 1 when a scene of `count` elements with `sets` distinct sets
+ * of rest constants and tiles of up to max_group_nodes nodes takes the dictionary on a device whose workgroups have lds_bytes of
+ * LDS (0: gfx950's 160 KB, what a PIES_DEVICE_NONE handle decides with), else 0 (the rule is all or nothing per scene). */
+int pies_layer_rest_pack(const uint32_t* ids, uint32_t set, uint32_t* words);
+int pies_layer_rest_unpack(const uint32_t* words, uint32_t* ids, uint32_t* set);
+int pies_layer_rest_usable(uint32_t sets, uint32_t count, uint32_t max_group_nodes, uint32_t lds_bytes);
 /* launches per substep of the captured graph, per kernel class (PIES_KERNEL_COUNT entries) */
 int pies_launch_counts(pies_solver_t* s, uint32_t* out);
 

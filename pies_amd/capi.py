@@ -39,6 +39,9 @@ NODE_PAIRS = 18  # the node-node CollisionConstraint extension container (PD)
 NODES_RENUMBERED = 19  # pies_count: 1 when the device holds the nodes in another numbering (FLAG_RENUMBER_NODES)
 NODE_CONTACTS = 20  # pies_count: node-node contacts of the last PD substep (FLAG_PD_NODE_CONTACTS)
 SKINS, SKIN_VERTICES = 21, 22  # pies_count: embedded surface meshes (pies_add_skin) and their vertices over all skins
+LAYER_REST_SETS = 23  # pies_count: sets in the rest dictionary of schedule LAYERED's tetrahedral container (0: per-element arrays)
+LAYER_MAX_TILES = 24  # pies_count: tiles of the phase of schedule LAYERED's plan that has most (0: not active)
+LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
 SYMBOLS = [
@@ -59,11 +62,31 @@ SYMBOLS = [
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume",
+    "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
 
 class PiesError(RuntimeError):
     pass
+
+
+def layer_rest_pack(ids, set_index):
+    """pies_layer_rest_pack: the two record words of an element (13-bit tile-local ids, 12-bit set index), None when one does not fit"""
+    i, w = (C.c_uint32 * 4)(*ids), (C.c_uint32 * 2)()
+    return (w[0], w[1]) if load().pies_layer_rest_pack(i, set_index, w) == OK else None
+
+
+def layer_rest_unpack(words):
+    """pies_layer_rest_unpack: (ids, set index) of an element's two record words"""
+    w, i, s = (C.c_uint32 * 2)(*words), (C.c_uint32 * 4)(), C.c_uint32()
+    load().pies_layer_rest_unpack(w, i, C.byref(s))
+    return list(i), s.value
+
+
+def layer_rest_usable(sets, count, max_group_nodes, lds_bytes=0):
+    """pies_layer_rest_usable: whether such a scene takes the rest dictionary (all or nothing); lds_bytes 0: the library's figure for
+    gfx950, the one host-only handles decide with"""
+    return load().pies_layer_rest_usable(sets, count, max_group_nodes, lds_bytes) == 1
 
 
 def set_tuning(name, value):
@@ -171,6 +194,9 @@ def load():
     sig["pies_export_acquire_skin"] = [vp, C.c_uint64, u32, C.POINTER(pf), C.POINTER(pf), pu]
     sig["pies_voxelize_tri_mesh"] = [vp, u32, pf, u32, pu, pf, f32, pu, pf, C.POINTER(C.c_uint8)]
     sig["pies_add_tri_mesh_volume"] = [vp, u32, pf, u32, pu, pf, f32, f32, f32, f32, f32, f32, f32, u32, pu, pu, pu, pu]
+    sig["pies_layer_rest_pack"] = [pu, u32, pu]
+    sig["pies_layer_rest_unpack"] = [pu, pu, pu]
+    sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
     sig["pies_get_pd_tile_plan"] = [vp, pu, pu, pu, pu, pu, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), u32]
     for name, args in sig.items():
         fn = getattr(L, name)

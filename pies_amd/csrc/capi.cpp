@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "capi_internal.h"
+#include "layer_rest.h"
 
 #include <numeric>
 
@@ -310,6 +311,7 @@ int pies_finalize(pies_solver_t* s) {
     if (s->sceneDirty) {
       decide_node_order(s);
       build_plans(s, s->opt.solver == PIES_SOLVER_PD ? -1 : s->schedule);
+      if (s->layer.active && s->opt.solver != PIES_SOLVER_PD) layer_rest_dictionary(s, kLayerLdsBytes, nullptr, nullptr);
     }
     s->sceneDirty = false;
     return PIES_OK;
@@ -737,6 +739,23 @@ int pies_collision_stats(pies_solver_t* s, uint64_t* pairs, uint64_t* candidates
   return PIES_OK;
 }
 
+int pies_layer_rest_pack(const uint32_t* ids, uint32_t set, uint32_t* words) {
+  if (!ids || !words || set >= 4096u) return PIES_ERR_INVALID;
+  for (int k = 0; k < 4; ++k)
+    if (ids[k] > kLayerRestIdMask) return PIES_ERR_INVALID;
+  layer_rest_pack(ids, set, words);
+  return PIES_OK;
+}
+int pies_layer_rest_unpack(const uint32_t* words, uint32_t* ids, uint32_t* set) {
+  if (!words || !ids || !set) return PIES_ERR_INVALID;
+  layer_rest_unpack(words, ids, set);
+  return PIES_OK;
+}
+int pies_layer_rest_usable(uint32_t sets, uint32_t count, uint32_t max_group_nodes, uint32_t lds_bytes) {
+  if (lds_bytes == 0) lds_bytes = kLayerLdsBytes;
+  return layer_rest_usable(sets, count, max_group_nodes, layer_lds_bytes(max_group_nodes, 0), layer_lds_bytes(max_group_nodes, sets), lds_bytes) ? 1 : 0;
+}
+
 int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
   if (!s || !out) return PIES_ERR_INVALID;
   switch (what) {
@@ -760,6 +779,13 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_PD_WINDOW_ENTRIES: *out = s->dev.pd.cg.wRows ? s->pdWindowEntries : 0u; break;
     case PIES_PD_WINDOW_HALO: *out = s->dev.pd.cg.wRows ? s->pdWindowHalo : 0u; break;
     case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
+    case PIES_LAYER_REST_SETS: *out = s->layer.active ? s->layer.restSets : 0u; break;
+    case PIES_LAYER_MAX_TILES: {
+      *out = 0;
+      if (s->layer.active)
+        for (int ph = 0; ph < 4; ++ph) *out = std::max<uint32_t>(*out, (uint32_t)s->layer.tiles[ph].size());
+      break;
+    }
     case PIES_SKINS: *out = (uint32_t)s->h_skins.size(); break;
     case PIES_SKIN_VERTICES: {
       *out = 0;

@@ -45,6 +45,8 @@ int alloc_nodes(pies_solver* s);          // node arrays, the read-back stage, t
 int upload_constraints(pies_solver* s);   // position, distance, strain and bend records in plan order
 int upload_node_pairs(pies_solver* s);    // the node-pair extension: ids, bitmap, node list
 int upload_layer_tables(pies_solver* s);  // schedule LAYERED
+// schedule LAYERED: decides the tetrahedral rest dictionary (s->layer.restSets) for a device whose workgroups have maxLds bytes of LDS
+void layer_rest_dictionary(pies_solver* s, size_t maxLds, std::vector<uint16_t>* index, std::vector<float4>* table);
 int upload_wave_index(pies_solver* s);    // schedule EXACT
 int alloc_node_grid(pies_solver* s, bool collide);  // ... and, with `collide`, the pair-order lists
 int nc_build(pies_solver* s);             // PIES_FLAG_PD_NODE_CONTACTS

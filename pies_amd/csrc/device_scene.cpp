@@ -8,8 +8,29 @@
 #include <map>
 
 #include "capi_internal.h"
+#include "layer_rest.h"
 
 namespace pies {
+
+// Distinct sets of N rest constants, compared by bytes (-0.0 and +0.0 are two sets) and numbered in order of first appearance:
+// the rest dictionaries of the PD local step and of schedule LAYERED's tetrahedral container.
+template <int N>
+struct RestSets {
+  static_assert(N % 4 == 0, "a set is stored as float4");
+  struct Set { float v[N]; bool operator<(const Set& o) const { return std::memcmp(v, o.v, sizeof(v)) < 0; } };
+  std::map<Set, uint32_t> ids;
+  std::vector<float4> table;  // N / 4 per set
+  // the number of `key`'s set, a new one if need be; -1 when that would be set number `cap`
+  int find_or_add(const Set& key, size_t cap) {
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      if (ids.size() >= cap) return -1;
+      it = ids.emplace(key, static_cast<uint32_t>(ids.size())).first;
+      for (int q = 0; q < N; q += 4) table.push_back(make_float4(key.v[q], key.v[q + 1], key.v[q + 2], key.v[q + 3]));
+    }
+    return static_cast<int>(it->second);
+  }
+};
 
 void free_device(pies_solver* s) {
   destroy_graph(s);
@@ -214,15 +235,50 @@ int upload_node_pairs(pies_solver* s) {
   return PIES_OK;
 }
 
+// schedule LAYERED: the rest dictionary of the tetrahedral container (layer_rest.h).  On a createTetBox lattice the 48 bytes of
+// rest constants are the same for every element of one orientation, and k_layer reads them from a table in LDS instead of
+// streaming them from HBM colour after colour.  All or nothing per scene: sets L.restSets and fills index (per slot) and table, or
+// leaves L.restSets 0 (PIES_LAYER_REST_DICT=0, too many sets, no compression, no room in LDS: the per-element arrays are read).
+void layer_rest_dictionary(pies_solver* s, size_t maxLds, std::vector<uint16_t>* index, std::vector<float4>* table) {
+  LayerPlan& L = s->layer;
+  L.restSets = 0;
+  const std::vector<uint32_t>& order = s->plan[PIES_TET].order;
+  const size_t count = L.kind[PIES_TET].local.size() / 4;
+  const char* de = tuning_env("PIES_LAYER_REST_DICT");
+  if (!L.active || count == 0 || order.size() != count || (de && de[0] == '0')) return;
+  RestSets<12> sets;
+  std::vector<uint16_t> idx(count);
+  const size_t cap = std::min<size_t>(kLayerRestMaxSets, count / 16);  // (more sets than that are no real compression)
+  for (size_t k = 0; k < count; ++k) {
+    const HostTet& a = s->h_tet[order[k]];
+    RestSets<12>::Set key;
+    std::memcpy(key.v, a.qinv, 9 * sizeof(float));
+    key.v[9] = a.lo; key.v[10] = a.hi; key.v[11] = a.w;
+    const int set = sets.find_or_add(key, cap);
+    if (set < 0) return;
+    idx[k] = static_cast<uint16_t>(set);
+  }
+  const uint32_t n = static_cast<uint32_t>(sets.ids.size());
+  if (!layer_rest_usable(n, count, L.maxGroupNodes, layer_lds_bytes(L.maxGroupNodes, 0), layer_lds_bytes(L.maxGroupNodes, n), maxLds)) return;
+  L.restSets = n;
+  if (index) index->swap(idx);
+  if (table) table->swap(sets.table);
+}
+
 // schedule LAYERED: the level-ordered node list, the tiles and the tile-local ids of every container
 int upload_layer_tables(pies_solver* s) {
-  const LayerPlan& L = s->layer;
+  LayerPlan& L = s->layer;
   LayerDevice& d = s->dev.d_layer;
   int maxLds = 0;
   HIP_TRY(s, hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
   if (static_cast<size_t>(L.maxGroupNodes) * 20 + 4096 > static_cast<size_t>(maxLds))
     return fail(s, PIES_ERR_UNSUPPORTED, "schedule LAYERED: the device's LDS is smaller than this build assumes");
-  HIP_TRY(s, layer_prepare(L.maxGroupNodes));
+  std::vector<uint16_t> restIndex;
+  std::vector<float4> restTable;
+  layer_rest_dictionary(s, static_cast<size_t>(maxLds), &restIndex, &restTable);
+  HIP_TRY(s, layer_prepare(L.maxGroupNodes, L.restSets));
+  if (L.restSets)
+    if (int rc = upload(s, restTable, &d.restTable)) return rc;
   if (int rc = upload(s, L.nodeList, &d.nodeList)) return rc;
   if (int rc = dev_alloc(s, L.nodeList.size(), &d.lpos, true)) return rc;
   {
@@ -246,6 +302,12 @@ int upload_layer_tables(pies_solver* s) {
     const std::vector<uint32_t>& l = L.kind[k].local;
     std::vector<uint2> packed(l.size() / 4);
     for (size_t c = 0; c < packed.size(); ++c) packed[c] = make_uint2(l[4 * c] | (l[4 * c + 1] << 16), l[4 * c + 2] | (l[4 * c + 3] << 16));
+    if (k == PIES_TET && L.restSets)  // 13-bit ids, the set index in their spare bits
+      for (size_t c = 0; c < packed.size(); ++c) {
+        uint32_t w[2];
+        layer_rest_pack(&l[4 * c], restIndex[c], w);
+        packed[c] = make_uint2(w[0], w[1]);
+      }
     if (int rc = upload(s, packed, k == PIES_TET ? &d.tc_lid : &d.bc_lid)) return rc;
   }
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -436,29 +498,24 @@ int pd_rest_dictionary(pies_solver* s) {
   s->h_pairDictIndex.clear();
   const char* de = tuning_env("PIES_PD_REST_DICT");
   if (!s->tetVolumePaired || (de && de[0] == '0')) return PIES_OK;
-  struct Set { float v[16]; bool operator<(const Set& o) const { return std::memcmp(v, o.v, sizeof(v)) < 0; } };
-  std::map<Set, uint16_t> sets;
+  RestSets<16> sets;
   std::vector<uint16_t> index(count);
-  std::vector<float4> table;
+  const size_t cap = std::min<size_t>(4096, count / 16);  // more sets than that are no real compression: per-element arrays
   for (size_t k = 0; k < count; ++k) {
     const HostTet &a = s->h_tet[s->plan[PIES_TET].order[k]], &b = s->h_volume[k];
-    Set key;
+    RestSets<16>::Set key;
     std::memcpy(key.v, a.qinv, 9 * sizeof(float));
     key.v[9] = a.lo; key.v[10] = a.hi; key.v[11] = a.w;
     key.v[12] = b.qinv[8]; key.v[13] = b.lo; key.v[14] = b.hi; key.v[15] = b.w;
-    auto it = sets.find(key);
-    if (it == sets.end()) {
-      if (sets.size() >= 4096 || (sets.size() + 1) * 16 > count) return PIES_OK;  // no real compression: per-element arrays
-      it = sets.emplace(key, static_cast<uint16_t>(sets.size())).first;
-      for (int q = 0; q < 16; q += 4) table.push_back(make_float4(key.v[q], key.v[q + 1], key.v[q + 2], key.v[q + 3]));
-    }
-    index[k] = it->second;
+    const int set = sets.find_or_add(key, cap);
+    if (set < 0) return PIES_OK;
+    index[k] = static_cast<uint16_t>(set);
   }
   if (index.empty()) return PIES_OK;
   s->h_pairDictIndex = index;
   if (int rc = upload(s, index, &d.d_pairDictIndex)) return rc;
-  if (int rc = upload(s, table, &d.d_pairDictTable)) return rc;
-  d.pairDictSets = static_cast<uint32_t>(sets.size());
+  if (int rc = upload(s, sets.table, &d.d_pairDictTable)) return rc;
+  d.pairDictSets = static_cast<uint32_t>(sets.ids.size());
   return PIES_OK;
 }
 

@@ -71,6 +71,8 @@ struct LayerData {
   const float2* dc_rw;
   const uint2* tc_lid;
   const float4 *tc_q0, *tc_q1, *tc_q2;
+  const float4* tc_rest;  // the rest dictionary (layer_rest.h): 3 float4 per set, tc_lid carries the set index; nullptr: tc_q0..2 per element
+  uint32_t restSets;      // its sets (0 without)
   const uint2* bc_lid;
   const float2* bc_aw;
 };
@@ -78,7 +80,9 @@ struct LayerParams {  // scalars of the per-node steps
   float floorHeight, dt, gravity, damping, friction;
 };
 // Returns hipSuccess or the error of the attribute call that raises the kernel's LDS limit.
-hipError_t layer_prepare(uint32_t maxGroupNodes);
+hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets);
+// LDS a launch asks for: the node records and radii of the largest tile, the colour offsets, the rest dictionary
+size_t layer_lds_bytes(uint32_t maxGroupNodes, uint32_t restSets);
 void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, const LayerLaunch& L, const LayerParams& P);
 // Per-node steps on the level-ordered copy, for bodies whose levels are cut into strips (no tile partition covers every
 // node exactly once there): predict reads the node array and fills the copy, velocity writes the node array back.

@@ -7,7 +7,8 @@
 // per-node steps of the substep (predict, floor clamp, velocity) - and writes the records back once.  Between two colours stands a workgroup barrier (~0.1 us) where
 // the batch-per-launch schedules pay a kernel boundary plus two dependent HBM round trips (~3.8 us); constraint
 // records (local ids 4-8 B, rest data) stream from HBM and the next colour's are requested before the current
-// colour is computed, so their latency hides behind the arithmetic.
+// colour is computed, so their latency hides behind the arithmetic.  A scene whose tetrahedra share a few sets of rest constants
+// (a lattice: one per orientation) keeps those in LDS as well (layer_rest.h): an element's record is then its 8 bytes of ids.
 //
 // Arithmetic per constraint is pbd_project.h's, the same as the global-memory kernels'.  No MFMA: 3x3 algebra per
 // lane.  Algorithmic bytes are those of the projections executed; HBM traffic is lower because a node
@@ -16,6 +17,7 @@
 
 #include "dev_math.h"
 #include "kernels.h"
+#include "layer_rest.h"
 #include "pbd_project.h"
 
 namespace pies {
@@ -48,13 +50,18 @@ PIES_DEV uint32_t hi16(uint32_t v) { return v >> 16; }
 // than compute units (config 2: 125) lasts as long as one wavefront's instruction stream and takes all the registers that shorten
 // it (1: up to 256 at 256 / 512 threads); a launch with several tiles per compute unit (1M particles: 400, the unstructured beam) is
 // bound by throughput and wants two 512-thread workgroups resident per compute unit: 4 wavefronts per SIMD, 128 registers.
-template <int BLOCK, int TETV, int WPE = 1>
+// DICT: the tetrahedral segments take Qinv, the strain limits and w from the rest dictionary in LDS (the set index rides in the spare
+// bits of tc_lid) instead of three float4 per element from HBM.  A template parameter: neither path pays the other's registers.
+template <int BLOCK, int TETV, int WPE = 1, bool DICT = false>
 __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D, LayerLaunch L, LayerParams P) {
+  static_assert(3 * kLayerRestMaxSets <= BLOCK, "the prologue requests the rest dictionary with one load per lane");
   constexpr int kDistPreload = (WPE > 1 || BLOCK > 512) ? 6 : kDistPreloadMax;
   constexpr int kDistAhead = 3;  // colours of a distance segment whose records are in flight
   extern __shared__ float4 lds[];
   float4* __restrict__ sp = lds;                                                  // node records of the group
-  float* __restrict__ srad = reinterpret_cast<float*>(sp + D.maxGroupNodes);      // their radii
+  float4* __restrict__ stab = sp + D.maxGroupNodes;                               // the rest dictionary: 3 per set (DICT)
+  const uint32_t tabLen = DICT ? 3u * D.restSets : 0u;
+  float* __restrict__ srad = reinterpret_cast<float*>(stab + tabLen);             // the node records' radii
   uint32_t* __restrict__ soff = reinterpret_cast<uint32_t*>(srad + D.maxGroupNodes);  // colour offsets, per segment
   const uint32_t tid = threadIdx.x;
   // (the grid size and the phase's tile list come with the launch record: the kernel's first loads are then ONE line of its
@@ -84,6 +91,7 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
   for (int s = 0; s < kLayerMaxSegs; ++s) { segCols[s] = L.seg[s].ncol; segOff[s] = L.seg[s].colOff; }
   uint32_t offReg[kLayerMaxSegs];
   float radReg[kBatch];
+  float4 tabReg = make_float4(0.f, 0.f, 0.f, 0.f);
   auto request_early = [&]() {  // (called inside both branches of the node load below: a branch waits for every load in flight)
 #pragma unroll
     for (int s = 0; s < kLayerMaxSegs; ++s) {
@@ -93,6 +101,7 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
     }
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) radReg[k] = needRadius ? D.lrad[lp(min(k * BLOCK + tid, m - 1))] : 0.0f;
+    if (DICT) tabReg = D.tc_rest[min(tid, tabLen - 1u)];  // (DICT: at least one set)
   };
   // Node records in: from the level-ordered copy (the tile's two runs are contiguous: coalesced) or, with one strip, in
   // the first launch of a substep / after a collision pass, gathered from the node array.  Four requests per lane are in flight before
@@ -151,8 +160,20 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
       for (uint32_t c = tid + BLOCK; c <= nc + 1; c += BLOCK) soff[s * kOffStride + c] = (segOff[s] + static_cast<size_t>(g) * (nc + 1))[min(c, nc)];
     }
   }
+  if (DICT && tid < tabLen) stab[tid] = tabReg;
   __syncthreads();
   PIES_STAMP();
+
+  // an element's tile-local node ids and, with the dictionary, its rest constants (LDS reads; a lattice's lanes mostly share a row)
+  auto tet_ids = [&](const uint2& w, uint32_t& i1, uint32_t& i2, uint32_t& i3, uint32_t& i4) {
+    if (DICT) { i1 = w.x & kLayerRestIdMask; i2 = (w.x >> 16) & kLayerRestIdMask; i3 = w.y & kLayerRestIdMask; i4 = (w.y >> 16) & kLayerRestIdMask; }
+    else { i1 = lo16(w.x); i2 = hi16(w.x); i3 = lo16(w.y); i4 = hi16(w.y); }
+  };
+  auto rest_ok = [&](const uint2& w) { return !DICT || PIES_IN_BOUNDS(layer_rest_set(w.x, w.y) < D.restSets, 14u); };
+  auto rest_read = [&](const uint2& w, float4& q0, float4& q1, float4& q2) {
+    const float4* __restrict__ row = stab + 3u * layer_rest_set(w.x, w.y);
+    q0 = row[0]; q1 = row[1]; q2 = row[2];
+  };
 
   for (uint32_t s = 0; s < L.nseg; ++s) {
     const uint32_t kind = L.seg[s].kind, ncol = L.seg[s].ncol;
@@ -163,9 +184,14 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
       for (uint32_t c = 0; c < ncol; ++c) {
         for (uint32_t t = off[c] + tid; t < off[c + 1]; t += BLOCK) {
           const uint2 jd = D.tc_lid[t];
-          const uint32_t i1 = lo16(jd.x), i2 = hi16(jd.x), i3 = lo16(jd.y), i4 = hi16(jd.y);
+          uint32_t i1, i2, i3, i4;
+          tet_ids(jd, i1, i2, i3, i4);
+          if (!rest_ok(jd)) continue;
+          float4 q0, q1, q2;
+          if (DICT) rest_read(jd, q0, q1, q2);
+          else { q0 = D.tc_q0[t]; q1 = D.tc_q1[t]; q2 = D.tc_q2[t]; }
           float4 x1 = sp[i1], x2 = sp[i2], x3 = sp[i3], x4 = sp[i4];
-          tet_core<TETV>(x1, x2, x3, x4, D.tc_q0[t], D.tc_q1[t], D.tc_q2[t]);
+          tet_core<TETV>(x1, x2, x3, x4, q0, q1, q2);
           sp[i1] = x1; sp[i2] = x2; sp[i3] = x3; sp[i4] = x4;
         }
         lds_barrier();
@@ -177,16 +203,22 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
       uint32_t lo = off[0], hi = off[1];
       bool have = lo + tid < hi;
       uint32_t t0 = min(lo + tid, last);
+      // (with the dictionary the look-ahead is the 8 bytes of ids alone, and the constants are read from LDS together with the node
+      // records, nothing held across the projection: reading the next colour's before the barrier instead, 12 registers held,
+      // measured slower - 882 against 905 substeps/s on config 2, 876 streamed)
       uint2 id = D.tc_lid[t0];
-      float4 a0 = D.tc_q0[t0], a1 = D.tc_q1[t0], a2 = D.tc_q2[t0];
+      float4 a0, a1, a2, b0, b1, b2;
+      if (!DICT) { a0 = D.tc_q0[t0]; a1 = D.tc_q1[t0]; a2 = D.tc_q2[t0]; }
       for (uint32_t c = 0; c < ncol; ++c) {
         const uint32_t nlo = hi, nhi = off[c + 2];
         const bool nhave = nlo + tid < nhi;
         t0 = min(nlo + tid, last);
         const uint2 nid = D.tc_lid[t0];
-        const float4 b0 = D.tc_q0[t0], b1 = D.tc_q1[t0], b2 = D.tc_q2[t0];
-        if (have && PIES_IN_BOUNDS(max(max(lo16(id.x), hi16(id.x)), max(lo16(id.y), hi16(id.y))) < m, 11u)) {
-          const uint32_t i1 = lo16(id.x), i2 = hi16(id.x), i3 = lo16(id.y), i4 = hi16(id.y);
+        if (!DICT) { b0 = D.tc_q0[t0]; b1 = D.tc_q1[t0]; b2 = D.tc_q2[t0]; }
+        uint32_t i1, i2, i3, i4;
+        tet_ids(id, i1, i2, i3, i4);
+        if (have && PIES_IN_BOUNDS(max(max(i1, i2), max(i3, i4)) < m, 11u) && rest_ok(id)) {
+          if (DICT) rest_read(id, a0, a1, a2);
           float4 x1 = sp[i1], x2 = sp[i2], x3 = sp[i3], x4 = sp[i4];
 #ifdef PIES_EXPERIMENTS
           if (stampBase) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); PIES_STAMP(); }  // the gather has landed
@@ -199,14 +231,20 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
         }
         for (uint32_t t = lo + tid + BLOCK; t < hi; t += BLOCK) {  // classes larger than the workgroup
           const uint2 jd = D.tc_lid[t];
-          const uint32_t i1 = lo16(jd.x), i2 = hi16(jd.x), i3 = lo16(jd.y), i4 = hi16(jd.y);
-          float4 x1 = sp[i1], x2 = sp[i2], x3 = sp[i3], x4 = sp[i4];
-          tet_core<TETV>(x1, x2, x3, x4, D.tc_q0[t], D.tc_q1[t], D.tc_q2[t]);
-          sp[i1] = x1; sp[i2] = x2; sp[i3] = x3; sp[i4] = x4;
+          uint32_t j1, j2, j3, j4;
+          tet_ids(jd, j1, j2, j3, j4);
+          if (!rest_ok(jd)) continue;
+          float4 q0, q1, q2;
+          if (DICT) rest_read(jd, q0, q1, q2);
+          else { q0 = D.tc_q0[t]; q1 = D.tc_q1[t]; q2 = D.tc_q2[t]; }
+          float4 x1 = sp[j1], x2 = sp[j2], x3 = sp[j3], x4 = sp[j4];
+          tet_core<TETV>(x1, x2, x3, x4, q0, q1, q2);
+          sp[j1] = x1; sp[j2] = x2; sp[j3] = x3; sp[j4] = x4;
         }
         lds_barrier();
         PIES_STAMP();
-        lo = nlo; hi = nhi; have = nhave; id = nid; a0 = b0; a1 = b1; a2 = b2;
+        lo = nlo; hi = nhi; have = nhave; id = nid;
+        if (!DICT) { a0 = b0; a1 = b1; a2 = b2; }
       }
     } else if (kind == LAYER_DISTANCE) {
       // a projection is ~40 instructions, far shorter than a record's way from HBM: every lane keeps the records of kDistAhead
@@ -409,19 +447,34 @@ extern "C" int pies_exp_layer_stamps(unsigned long long* deviceBuffer) {  // 64 
 }
 #endif
 PIES_BOUNDS_REPORT(layer)
-static size_t layer_lds_bytes(uint32_t maxGroupNodes) {
-  return static_cast<size_t>(maxGroupNodes) * (sizeof(float4) + sizeof(float)) + kLayerMaxSegs * kOffStride * sizeof(uint32_t);
+size_t layer_lds_bytes(uint32_t maxGroupNodes, uint32_t restSets) {
+  return static_cast<size_t>(maxGroupNodes) * (sizeof(float4) + sizeof(float)) + kLayerMaxSegs * kOffStride * sizeof(uint32_t) +
+         static_cast<size_t>(restSets) * 3u * sizeof(float4);
 }
 
-hipError_t layer_prepare(uint32_t maxGroupNodes) {
-  const int bytes = static_cast<int>(layer_lds_bytes(maxGroupNodes));
-  if (bytes <= 64 * 1024) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<1024, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+template <bool DICT>
+static hipError_t layer_prepare_variants(int bytes) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 1, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 1, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 4, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 4, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<1024, 0, 1, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   return e;
+}
+hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets) {
+  const int bytes = static_cast<int>(layer_lds_bytes(maxGroupNodes, restSets));
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return restSets ? layer_prepare_variants<true>(bytes) : layer_prepare_variants<false>(bytes);
+}
+
+template <bool DICT>
+static void launch_layer_variant(hipStream_t st, uint32_t want, bool throughput, size_t lds, const NodeArrays& nd, const LayerData& D,
+                                 const LayerLaunch& L, const LayerParams& P) {
+  if (want <= 256 && throughput) hipLaunchKernelGGL((k_layer<256, 0, 4, DICT>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+  else if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0, 1, DICT>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+  else if (want <= 512 && throughput) hipLaunchKernelGGL((k_layer<512, 0, 4, DICT>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
+  else if (want <= 512) hipLaunchKernelGGL((k_layer<512, 0, 1, DICT>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
+  else hipLaunchKernelGGL((k_layer<1024, 0, 1, DICT>), dim3(L.groups), dim3(1024), lds, st, nd, D, L, P);
 }
 
 void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, const LayerLaunch& L0, const LayerParams& P) {
@@ -431,7 +484,9 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
   for (uint32_t s = L.nseg; s < static_cast<uint32_t>(kLayerMaxSegs); ++s) L.seg[s] = LayerSeg{};  // (the kernel reads all six)
   L.needRadius = 0u;
   for (uint32_t s = 0; s < L.nseg; ++s) L.needRadius |= (L.seg[s].kind == LAYER_FLOOR || L.seg[s].kind == LAYER_VELOCITY) ? 1u : 0u;
-  const size_t lds = layer_lds_bytes(D.maxGroupNodes);
+  // the scene has a rest dictionary: tc_lid carries set indices, and every launch runs the instantiations that read the table
+  const bool restDict = D.tc_rest && D.restSets && D.restSets <= kLayerRestMaxSets;
+  const size_t lds = layer_lds_bytes(D.maxGroupNodes, restDict ? D.restSets : 0u);
 #ifdef PIES_EXPERIMENTS  // timing experiments that change the work done: never part of the product build (build.py)
   const int skipMask = [] { const char* e = getenv("PIES_EXP_LAYER_SKIP"); return e ? atoi(e) : 0; }();
   if (skipMask) {
@@ -444,7 +499,11 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
     L.stampSlot = slot++ & 63u;
   }
   const int variant = [] { const char* e = getenv("PIES_EXP_TET"); return e ? atoi(e) : 0; }();
-  if (variant == 1) { hipLaunchKernelGGL((k_layer<256, 1>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P); return; }  // no SVD
+  if (variant == 1) {  // no SVD (with a dictionary tc_lid holds 13-bit ids: the instantiation that unpacks them)
+    if (restDict) hipLaunchKernelGGL((k_layer<256, 1, 1, true>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+    else hipLaunchKernelGGL((k_layer<256, 1>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+    return;
+  }
 #endif
   const uint32_t forceBlock = [] { const char* e = tuning_env("PIES_LAYER_BLOCK"); return e ? (uint32_t)atoi(e) : 0u; }();  // speed only
   // A workgroup as wide as the launch's largest colour class runs every colour in one round - what counts while the launch has
@@ -454,11 +513,8 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
   uint32_t want = forceBlock ? forceBlock : L.maxClass;
   if (!forceBlock && L.groups > 256u) want = std::min<uint32_t>(want, 512u);  // (256 compute units)
   const bool throughput = L.groups > 256u;  // several tiles per compute unit
-  if (want <= 256 && throughput) hipLaunchKernelGGL((k_layer<256, 0, 4>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
-  else if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
-  else if (want <= 512 && throughput) hipLaunchKernelGGL((k_layer<512, 0, 4>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
-  else if (want <= 512) hipLaunchKernelGGL((k_layer<512, 0>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
-  else hipLaunchKernelGGL((k_layer<1024, 0>), dim3(L.groups), dim3(1024), lds, st, nd, D, L, P);
+  if (restDict) launch_layer_variant<true>(st, want, throughput, lds, nd, D, L, P);
+  else launch_layer_variant<false>(st, want, throughput, lds, nd, D, L, P);
 }
 
 }  // namespace pies

@@ -125,6 +125,7 @@ struct LayerPlan {
   std::vector<uint32_t> nodeList;     // node ids sorted by (level, second level, id)
   std::vector<LayerTile> tiles[4];    // per phase
   LayerKind kind[5];                  // indexed by PIES_POSITION .. PIES_BEND (PIES_VOLUME unused)
+  uint32_t restSets = 0;              // sets of the tetrahedral rest dictionary (layer_rest_dictionary), 0: per-element arrays
 };
 struct LayerDevice {
   uint32_t* nodeList = nullptr;
@@ -134,7 +135,8 @@ struct LayerDevice {
   uint32_t* colOff[5][4] = {};
   uint32_t* pc_lid = nullptr;  // 1 x 16 bit in a word
   uint32_t* dc_lid = nullptr;  // a | b << 16
-  uint2* tc_lid = nullptr;     // (n1 | n2 << 16, n3 | n4 << 16)
+  uint2* tc_lid = nullptr;     // (n1 | n2 << 16, n3 | n4 << 16); with a rest dictionary 13-bit ids + the set index (layer_rest.h)
+  float4* restTable = nullptr;  // the rest dictionary: 3 float4 per set (Qinv, min strain, max strain, w), nullptr without
   uint2* bc_lid = nullptr;
 };
 

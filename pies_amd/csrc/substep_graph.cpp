@@ -220,6 +220,7 @@ void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_
   D.pc_lid = d.pc_lid; D.pc_tw = s->dev.d_pc_tw;
   D.dc_lid = d.dc_lid; D.dc_rw = s->dev.d_dc_rw;
   D.tc_lid = d.tc_lid; D.tc_q0 = s->dev.d_tc_q0; D.tc_q1 = s->dev.d_tc_q1; D.tc_q2 = s->dev.d_tc_q2;
+  D.tc_rest = s->layer.restSets ? d.restTable : nullptr; D.restSets = D.tc_rest ? s->layer.restSets : 0u;
   D.bc_lid = d.bc_lid; D.bc_aw = s->dev.d_bc_aw;
   const float dt = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
   const LayerParams P = {s->opt.floorHeight, dt, s->opt.gravity, s->opt.damping, s->opt.friction};

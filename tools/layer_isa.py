@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Static VALU / scalar / memory instruction counts per basic block of k_layer<256>'s tetrahedral colour loop, in the gfx950 ISA
 hipcc emits for the product build (cross-compilation only: runs without a GPU).
-usage: python tools/layer_isa.py > profiles/r06_layer_isa.txt"""
+usage: python tools/layer_isa.py [--streamed] > profiles/r07_layer_isa.txt"""
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
+DICT = 0 if "--streamed" in sys.argv else 1  # the instantiation with the rest dictionary (the headline's), or the streamed one
+sys.argv = [a for a in sys.argv if a != "--streamed"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 with tempfile.TemporaryDirectory() as tmp:
     out = os.path.join(tmp, "layer.s")
@@ -15,10 +17,10 @@ with tempfile.TemporaryDirectory() as tmp:
                            "-ffp-contract=off", "-fno-fast-math"] + sys.argv[1:] + ["--offload-arch=gfx950", "--cuda-device-only", "-I", os.path.join(ROOT, "include")],
                           stderr=subprocess.DEVNULL)
     txt = open(out).read()
-m = re.search(r"^_ZN4pies7k_layerILi256ELi0ELi1EEE.*?s_endpgm", txt, re.S | re.M)
+m = re.search(r"^_ZN4pies7k_layerILi256ELi0ELi1ELb%dEEE.*?s_endpgm" % DICT, txt, re.S | re.M)
 lines = m.group(0).splitlines()
-meta = re.search(r"_ZN4pies7k_layerILi256ELi0ELi1EEE.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)", txt, re.S)
-print("k_layer<256, 0, 1>: %d lines of ISA, %s VGPRs, scratch %s bytes, occupancy %s" % (len(lines), meta.group(1), meta.group(2), meta.group(3)))
+meta = re.search(r"_ZN4pies7k_layerILi256ELi0ELi1ELb%dEEE.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)" % DICT, txt, re.S)
+print("k_layer<256, 0, 1, " + ("true" if DICT else "false") + ">: %d lines of ISA, %s VGPRs, scratch %s bytes, occupancy %s" % (len(lines), meta.group(1), meta.group(2), meta.group(3)))
 # the tetrahedral colour loop: the first loop whose body holds four 12/16-byte LDS reads followed (later) by four LDS writes and a barrier
 blocks, cur = [], None
 for l in lines:
@@ -40,7 +42,7 @@ for l in lines:
         if op.startswith(("s_cbranch", "s_branch")):
             cur["br"].append(t.replace("\t", " "))
 start = next(i for i, b in enumerate(blocks) if sum(o in ("ds_read_b96", "ds_read_b128") for o in b["ops"]) >= 4 and
-             sum(o == "global_load_dwordx4" for o in b["ops"]) >= 3)  # (the next colour's records are requested at the head of the body)
+             sum(o == "global_load_dwordx4" for o in b["ops"]) >= (0 if DICT else 3) and any(o == "global_load_dwordx2" for o in b["ops"]))  # (the next colour's records are requested at the head of the body)
 end = next(i for i in range(start, len(blocks)) if "s_barrier" in blocks[i]["ops"] or (i > start and sum(o.startswith("ds_write_b") for o in blocks[i]["ops"]) >= 4))
 print("tetrahedral colour loop: blocks %s .. %s" % (blocks[start]["name"], blocks[end]["name"]))
 tot = 0
