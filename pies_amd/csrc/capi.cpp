@@ -429,11 +429,7 @@ int pies_synchronize(pies_solver_t* s) {
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   s->asyncSinceSync = 0;
-  if (int rc = poll_failure(s)) return rc;  // a loop of pies_tick_async learns here that the simulation failed
-  if (int rc = adapt_pair_rounds(s)) return rc;
-  if (int rc = adapt_sort_passes(s)) return rc;
-  if (int rc = adapt_nc_rounds(s)) return rc;
-  return adapt_pcg_budget(s);
+  return after_synchronize(s);
 }
 
 // Projective Dynamics, synchronous tick: the reference's global step is a direct solve (Solver.cpp:258-262, 356), the
@@ -468,10 +464,7 @@ static int pd_tick_checked(pies_solver* s) {
         HIP_TRY(s, hipMemcpyAsync(s->dev.pd.shape.quat, s->dev.snapQuat, 4ull * s->dev.pd.shape.count * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
       HIP_TRY(s, hipMemcpyAsync(s->dev.pd.cg.stats, before, sizeof(before), hipMemcpyHostToDevice, s->stream));
       HIP_TRY(s, hipStreamSynchronize(s->stream));
-      s->pcgBudget = std::min(s->pcgMaxIters, std::max(32u, 4u * s->pcgBudget));
-      s->pcgCalm = 0;
-      s->pcgWindowMax = 0;
-      s->pcgCooldown = 24;
+      s->pcgBudget = pcg_ran_short(s, s->pcgBudget);
       ++s->pcgRetries;
       if (const char* e = std::getenv("PIES_PCG_DEBUG"); e && e[0] == '1')
         std::fprintf(stderr, "[pies] pcg: substep ran short (residual^2 %.3g): again with budget %u\n", after[0], s->pcgBudget);
@@ -499,11 +492,7 @@ int pies_tick(pies_solver_t* s) {
   // Solver.cpp:157 : _vertices[i].position = position -- one D2H copy per tick; the host mirror's positions are
   // current afterwards (pies_read_nodes / pies_read_positions_strided copy from it without touching the device)
   if (int rc = download_nodes(s, 1u)) return rc;
-  if (int rc = poll_failure(s)) return rc;
-  if (int rc = adapt_pair_rounds(s)) return rc;
-  if (int rc = adapt_sort_passes(s)) return rc;
-  if (int rc = adapt_nc_rounds(s)) return rc;
-  return adapt_pcg_budget(s);
+  return after_synchronize(s);
 }
 
 // ---- render-state export: frame k leaves through a copy stream while frame k+1 computes -----------------------

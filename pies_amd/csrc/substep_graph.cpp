@@ -2,16 +2,14 @@
 // launches -, its capture into hipGraphs (one per CG budget and contact-row variant for PD), and the adaptations that follow
 // the scene at host synchronisations: captured CG iterations, level launches of the pair order, radix passes of the node grid.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
+#include <type_traits>
 
 #include "capi_internal.h"
+#include "follow_rule.h"
 
 using namespace pies;
 
@@ -169,12 +167,12 @@ void collision_grid_bound(const pies_solver* s, uint64_t& entries, bool& fast) {
     if (!(twoR <= 1.0f)) fast = false;
   }
 }
-void probe_mark(pies_solver* s, int k) {
+static void probe_mark(pies_solver* s, int k) {
   if (s->probe && s->probe->kernel == k) s->probe->mark();
 }
 // PIES_COLLISION_ORDER_*: the reference's loop for ranges wider than two cells per axis (the parallel orders need 2R <= 1),
 // under schedule EXACT, or when asked for; otherwise the pair order (or, when asked for, the group order of rounds 1-2)
-int collision_order(const pies_solver* s) {
+static int collision_order(const pies_solver* s) {
   int order = s->collisionOrderFlag >= 0 ? s->collisionOrderFlag
                                           : (s->schedule == PIES_SCHEDULE_EXACT ? PIES_COLLISION_ORDER_REFERENCE : PIES_COLLISION_ORDER_PAIRS);
   // the group order needs ranges of at most two cells per axis (2R <= 1); the pair order lists node by node beyond that
@@ -183,18 +181,18 @@ int collision_order(const pies_solver* s) {
 }
 // The reference's order runs by dependency levels of turns (pair_kernels.hip: launch_collide_turns) from 1 024 nodes on; below that -
 // and with PIES_REFERENCE_TURNS=0 - as the single chain of k_collide_reference, which is also the turns' fallback.
-bool reference_by_turns(const pies_solver* s) {
+static bool reference_by_turns(const pies_solver* s) {
   if (const char* e = tuning_env("PIES_REFERENCE_TURNS")) return e[0] != '0' && s->dev.pairs.turnCnt != nullptr;
   return s->dev.nd.n >= 1024u && s->dev.pairs.turnCnt != nullptr;
 }
 // (the group lists of k_grid_groups: the group order's, and the list kernels' for ranges wider than two cells per axis)
-bool needs_grid_groups(const pies_solver* s) {
+static bool needs_grid_groups(const pies_solver* s) {
   const int order = collision_order(s);
   if (order == PIES_COLLISION_ORDER_GROUPS) return true;
   if (order == PIES_COLLISION_ORDER_REFERENCE && !reference_by_turns(s)) return false;
   return !s->collideFast;
 }
-uint32_t enqueue_collide(pies_solver* s, bool rearm) {
+static uint32_t enqueue_collide(pies_solver* s, bool rearm) {
   switch (collision_order(s)) {
     case PIES_COLLISION_ORDER_REFERENCE:
       if (reference_by_turns(s))
@@ -207,7 +205,52 @@ uint32_t enqueue_collide(pies_solver* s, bool rearm) {
   }
 }
 
-void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
+// The launches of one kernel class inside a substep.  The enqueue_* functions make every launch through run(): the class's launch
+// or launches if the class is selected (only < 0: every class; otherwise the one class of a profile pass), the in-situ probe's
+// bracket around them, n added to the class's count and u to the units (tallied for the selected class; with a probe attached,
+// for the probed one).
+struct Bracket {
+  pies_solver* s;
+  int only;
+  uint32_t* counts;
+  uint64_t* units;
+  int cur = -1;  // class of the launch being made
+  bool all() const { return only < 0; }
+  // PD: the solve brackets the launches of these two classes one by one through its own hook; its caller only counts them
+  static bool bracketed_by_solve(int k) { return k == PIES_KERNEL_PD_SPMV || k == PIES_KERNEL_PD_CG_UPDATE; }
+  bool open(int k) { cur = k; const bool on = only < 0 || only == k; if (on) probe_mark(s, k); return on; }
+  void tally(uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; }
+  void close(int k, uint32_t n = 1) { if (!bracketed_by_solve(k)) probe_mark(s, k); if (counts) counts[k] += n; }
+  // `launch` returns nothing (one launch) or the number of launches it made; a class that is not selected counts `unselected`
+  template <class F> void run(int k, uint64_t u, F&& launch, uint32_t unselected = 1) {
+    uint32_t n = unselected;
+    if (open(k)) {
+      if constexpr (std::is_void_v<decltype(launch())>) { launch(); n = 1; } else n = launch();
+      tally(u);
+    }
+    close(k, n);
+  }
+};
+
+// Launches of the node grid's build (launch_hash_build), counted for a build that is not selected.  Counts are only taken with every
+// class selected, so neither figure is ever read; the PBD literal predates the radix passes that follow the scene's box (it is
+// not 6 + 3 sortPasses + the group lists' launch) and is kept as it was.
+constexpr uint32_t kPbdGridBuildLaunchesUnselected = 34;
+static uint32_t nc_hash_launches(const pies_solver* s) { return s->dev.nd.n ? 6u + 3u * s->sortPasses : 0u; }  // (without the group lists)
+
+// A pass over the node grid: its build, then the launches that work on it, each class in its bracket with the count it returns
+template <class F> static void grid_pass(Bracket& b, bool groups, uint32_t buildUnselected, F&& work) {
+  pies_solver* s = b.s;
+  b.run(PIES_KERNEL_HASH, s->dev.nd.n, [&] { return launch_hash_build(s->stream, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, groups); }, buildUnselected);
+  b.run(PIES_KERNEL_COLLIDE, s->dev.nd.n, work);
+}
+// the node-node collision pass of PBD (Solver.cpp:81-130)
+static void collide_pass(Bracket& b) {
+  grid_pass(b, needs_grid_groups(b.s), kPbdGridBuildLaunchesUnselected, [&] { return enqueue_collide(b.s, b.only == PIES_KERNEL_COLLIDE); });
+}
+
+static void enqueue_layered_substep(Bracket& b) {
+  pies_solver* s = b.s;
   hipStream_t st = s->stream;
   std::vector<LayerItem> prog;
   build_layer_program(s, prog);
@@ -224,115 +267,67 @@ void enqueue_layered_substep(pies_solver* s, int only, uint32_t* counts, uint64_
   D.bc_lid = d.bc_lid; D.bc_aw = s->dev.d_bc_aw;
   const float dt = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
   const LayerParams P = {s->opt.floorHeight, dt, s->opt.gravity, s->opt.damping, s->opt.friction};
-  int cur = -1;  // class of the launch being made: with a probe attached only that class's units are tallied
-  auto ON = [&](int k) { const bool on = only < 0 || only == k; cur = k; if (on) probe_mark(s, k); return on; };
-  auto C = [&](int k) { probe_mark(s, k); if (counts) ++counts[k]; };
-  auto U = [&](uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; };
+  const uint64_t n = s->dev.nd.n;
   for (const LayerItem& item : prog) {
     switch (item.type) {
-      case ITEM_COLLIDE: {  // Solver.cpp:81-130
-        uint32_t nb = 34, nc = 1;
-        if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
-        probe_mark(s, PIES_KERNEL_HASH);
-        if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
-        probe_mark(s, PIES_KERNEL_COLLIDE);
-        if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
-        break;
-      }
-      case ITEM_LAYER:
-        if (ON(PIES_KERNEL_LAYER)) { launch_layer(st, s->dev.nd, D, item.launch, P); U(item.bytes); }
-        C(PIES_KERNEL_LAYER);
-        break;
-      case ITEM_LPREDICT:
-        if (ON(PIES_KERNEL_PREDICT)) { launch_lpredict(st, s->dev.nd, D, P); U(s->dev.nd.n); }
-        C(PIES_KERNEL_PREDICT);
-        break;
-      case ITEM_LVELOCITY:
-        if (ON(PIES_KERNEL_VELOCITY)) { launch_lvelocity(st, s->dev.nd, D, P); U(s->dev.nd.n); }
-        C(PIES_KERNEL_VELOCITY);
-        break;
-      case ITEM_LFLOOR:
-        if (ON(PIES_KERNEL_FLOOR)) { launch_lfloor(st, s->dev.nd, D, P); U(s->dev.nd.n); }
-        C(PIES_KERNEL_FLOOR);
-        break;
-      case ITEM_LPOSITION:
-        if (ON(PIES_KERNEL_POSITION)) { launch_lposition(st, D, item.batch.start, item.batch.count); U(item.batch.count); }
-        C(PIES_KERNEL_POSITION);
-        break;
+      case ITEM_COLLIDE: collide_pass(b); break;
+      case ITEM_LAYER: b.run(PIES_KERNEL_LAYER, item.bytes, [&] { launch_layer(st, s->dev.nd, D, item.launch, P); }); break;
+      case ITEM_LPREDICT: b.run(PIES_KERNEL_PREDICT, n, [&] { launch_lpredict(st, s->dev.nd, D, P); }); break;
+      case ITEM_LVELOCITY: b.run(PIES_KERNEL_VELOCITY, n, [&] { launch_lvelocity(st, s->dev.nd, D, P); }); break;
+      case ITEM_LFLOOR: b.run(PIES_KERNEL_FLOOR, n, [&] { launch_lfloor(st, s->dev.nd, D, P); }); break;
+      case ITEM_LPOSITION: b.run(PIES_KERNEL_POSITION, item.batch.count, [&] { launch_lposition(st, D, item.batch.start, item.batch.count); }); break;
       case ITEM_TO_NODES:
       case ITEM_FROM_NODES:
-        if (only < 0) launch_lcopy(st, s->dev.nd, D, item.type == ITEM_TO_NODES);
+        if (b.all()) launch_lcopy(st, s->dev.nd, D, item.type == ITEM_TO_NODES);
         break;
     }
   }
 }
 
-// One PBD substep as a launch sequence (Solver.cpp:45-159).  `timer`/`timedKernel` select one kernel
-// class for per-dispatch timing (profile pass); counts (optional) tallies launches per class.
-void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
-  hipStream_t st = s->stream;
-  const float dt = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
-  int cur = -1;
-  auto C = [&](int k) { probe_mark(s, k); if (counts) ++counts[k]; };
-  auto ON = [&](int k) { const bool on = only < 0 || only == k; cur = k; if (on) probe_mark(s, k); return on; };  // profile pass: one kernel class only
-  auto U = [&](uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; };
+// Schedule EXACT: the levels of the whole-substep DAG, cut by the collision passes
+static void pbd_wavefront_levels(Bracket& b) {
+  pies_solver* s = b.s;
+  const WaveData W = {s->dev.d_pc_id, s->dev.d_pc_tw, s->dev.d_dc_ids, s->dev.d_dc_rw, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_bc_ids, s->dev.d_bc_aw};
+  size_t barrier = 0;
+  for (size_t l = 0; l < s->wave.levels.size(); ++l) {
+    for (; barrier < s->wave.barrierAfter.size() && s->wave.barrierAfter[barrier] == l; ++barrier) collide_pass(b);
+    const WaveLevel& L = s->wave.levels[l];
+    b.run(PIES_KERNEL_WAVE, (uint64_t)L.cnt[0] + L.cnt[1] + L.cnt[2] + L.cnt[3] + L.cnt[4],
+          [&] { launch_wave(s->stream, s->dev.nd, s->opt.floorHeight, s->dev.d_waveIndex, L, W); });
+  }
+  for (; barrier < s->wave.barrierAfter.size(); ++barrier) collide_pass(b);
+}
 
-  if (s->layer.active) { enqueue_layered_substep(s, only, counts, units); return; }
-  if (ON(PIES_KERNEL_PREDICT)) { launch_predict(st, s->dev.nd, dt, s->opt.gravity); U(s->dev.nd.n); }
-  C(PIES_KERNEL_PREDICT);
-  if (s->wave.active) {  // schedule EXACT: the levels of the whole-substep DAG, cut by the collision passes
-    const WaveData W = {s->dev.d_pc_id, s->dev.d_pc_tw, s->dev.d_dc_ids, s->dev.d_dc_rw, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_bc_ids, s->dev.d_bc_aw};
-    size_t barrier = 0;
-    auto collide = [&] {
-      uint32_t nb = 34, nc = 1;
-      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
-      probe_mark(s, PIES_KERNEL_HASH);
-      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
-      probe_mark(s, PIES_KERNEL_COLLIDE);
-      if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
-    };
-    for (size_t l = 0; l < s->wave.levels.size(); ++l) {
-      for (; barrier < s->wave.barrierAfter.size() && s->wave.barrierAfter[barrier] == l; ++barrier) collide();
-      const WaveLevel& L = s->wave.levels[l];
-      if (ON(PIES_KERNEL_WAVE)) {
-        launch_wave(st, s->dev.nd, s->opt.floorHeight, s->dev.d_waveIndex, L, W);
-        U((uint64_t)L.cnt[0] + L.cnt[1] + L.cnt[2] + L.cnt[3] + L.cnt[4]);
-      }
-      C(PIES_KERNEL_WAVE);
-    }
-    for (; barrier < s->wave.barrierAfter.size(); ++barrier) collide();
-  }
-  for (uint32_t it = 0; it < (s->wave.active ? 0u : s->opt.iterations); ++it) {  // one launch per batch, sweep after sweep
+// Schedule COLOURED (and EXACT without the wavefront levels): one launch per batch, sweep after sweep
+static void pbd_batch_sweeps(Bracket& b) {
+  pies_solver* s = b.s;
+  hipStream_t st = s->stream;
+  float4* pos = s->dev.nd.pos;
+  for (uint32_t it = 0; it < s->opt.iterations; ++it) {
     if (!s->releaseHinge)
-      for (const Batch& b : s->plan[PIES_POSITION].batches) {
-        if (ON(PIES_KERNEL_POSITION)) { launch_position(st, s->dev.nd.pos, s->dev.d_pc_id, s->dev.d_pc_tw, b.start, b.count); U(b.count); }
-        C(PIES_KERNEL_POSITION);
-      }
-    for (const Batch& b : s->plan[PIES_DISTANCE].batches) {
-      if (ON(PIES_KERNEL_DISTANCE)) { launch_distance(st, s->dev.nd.pos, s->dev.d_dc_ids, s->dev.d_dc_rw, b.start, b.count); U(b.count); }
-      C(PIES_KERNEL_DISTANCE);
-    }
-    for (const Batch& b : s->plan[PIES_TET].batches) {
-      if (ON(PIES_KERNEL_TET)) { launch_tet(st, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, b.start, b.count); U(b.count); }
-      C(PIES_KERNEL_TET);
-    }
-    for (const Batch& b : s->plan[PIES_BEND].batches) {
-      if (ON(PIES_KERNEL_BEND)) { launch_bend(st, s->dev.nd.pos, s->dev.d_bc_ids, s->dev.d_bc_aw, b.start, b.count); U(b.count); }
-      C(PIES_KERNEL_BEND);
-    }
-    if (s->nodeCollisions) {  // Solver.cpp:81-130
-      uint32_t nb = 34, nc = 1;
-      if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, needs_grid_groups(s)); U(s->dev.nd.n); }
-      probe_mark(s, PIES_KERNEL_HASH);
-      if (ON(PIES_KERNEL_COLLIDE)) { nc = enqueue_collide(s, only == PIES_KERNEL_COLLIDE); U(s->dev.nd.n); }
-      probe_mark(s, PIES_KERNEL_COLLIDE);
-      if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nc; }
-    }
-    if (ON(PIES_KERNEL_FLOOR)) { launch_floor(st, s->dev.nd, s->opt.floorHeight); U(s->dev.nd.n); }
-    C(PIES_KERNEL_FLOOR);
+      for (const Batch& c : s->plan[PIES_POSITION].batches)
+        b.run(PIES_KERNEL_POSITION, c.count, [&] { launch_position(st, pos, s->dev.d_pc_id, s->dev.d_pc_tw, c.start, c.count); });
+    for (const Batch& c : s->plan[PIES_DISTANCE].batches)
+      b.run(PIES_KERNEL_DISTANCE, c.count, [&] { launch_distance(st, pos, s->dev.d_dc_ids, s->dev.d_dc_rw, c.start, c.count); });
+    for (const Batch& c : s->plan[PIES_TET].batches)
+      b.run(PIES_KERNEL_TET, c.count, [&] { launch_tet(st, pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, c.start, c.count); });
+    for (const Batch& c : s->plan[PIES_BEND].batches)
+      b.run(PIES_KERNEL_BEND, c.count, [&] { launch_bend(st, pos, s->dev.d_bc_ids, s->dev.d_bc_aw, c.start, c.count); });
+    if (s->nodeCollisions) collide_pass(b);
+    b.run(PIES_KERNEL_FLOOR, s->dev.nd.n, [&] { launch_floor(st, s->dev.nd, s->opt.floorHeight); });
   }
-  if (ON(PIES_KERNEL_VELOCITY)) { launch_velocity(st, s->dev.nd, dt, s->opt.damping, s->opt.friction, s->opt.floorHeight); U(s->dev.nd.n); }
-  C(PIES_KERNEL_VELOCITY);
+}
+
+// One PBD substep as a launch sequence (Solver.cpp:45-159).  only >= 0 (profile pass) launches one kernel class; counts
+// (optional) tallies launches per class, units the work items of the launches made.
+void enqueue_pbd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
+  Bracket b{s, only, counts, units};
+  if (s->layer.active) { enqueue_layered_substep(b); return; }
+  const float dt = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
+  b.run(PIES_KERNEL_PREDICT, s->dev.nd.n, [&] { launch_predict(s->stream, s->dev.nd, dt, s->opt.gravity); });
+  if (s->wave.active) pbd_wavefront_levels(b);
+  else pbd_batch_sweeps(b);
+  b.run(PIES_KERNEL_VELOCITY, s->dev.nd.n, [&] { launch_velocity(s->stream, s->dev.nd, dt, s->opt.damping, s->opt.friction, s->opt.floorHeight); });
 }
 
 // The global step's CG with one launch per iteration (pd_cg1_kernels.hip): the contact-light graph variant with one lane per
@@ -343,174 +338,191 @@ bool pd_single_cg(const pies_solver* s) {
   return s->pdSingleCg && (!s->dev.pd.cg.useCAp || s->pdSingleCgRows) && s->dev.pd.cg.lanesPerRow == 1u;
 }
 
-// PIES_FLAG_PD_NODE_CONTACTS: launches of the node grid's build (launch_hash_build without the group lists)
-static uint32_t nc_hash_launches(const pies_solver* s) { return s->dev.nd.n ? 6u + 3u * s->sortPasses : 0u; }
-// the contacts' friction (Solver.cpp:398-428) in ascending pair key, then their nodes' floor friction; accounted to COLLIDE, one
-// in-situ bracket around the whole pass
-static void enqueue_nc_friction(pies_solver* s, uint32_t* counts) {
-  probe_mark(s, PIES_KERNEL_COLLIDE);
-  NodeContactArrays C = s->dev.nc;
-  C.rounds = s->ncRounds;
-  const uint32_t k = launch_nc_friction(s->stream, C, s->dev.hash, s->dev.nd, s->dev.pd.nstatic, s->dev.pd.tri.nt ? s->dev.pd.tri.usedBits : nullptr, s->opt.friction,
-                                        s->opt.staticFrictionThreshold);
-  probe_mark(s, PIES_KERNEL_COLLIDE);
-  if (counts) counts[PIES_KERNEL_COLLIDE] += k;
+// PIES_TRI_SIDE (diagnostics: 0 = always in line, 1 = always beside): whether the dependency levels of the contact list run on the
+// side stream.  Decided by the switch and the contact-row variant alone, so a graph selected from the ladder answers as it was captured.
+static bool tri_levels_forked(const pies_solver* s) {
+  const char* side = tuning_env("PIES_TRI_SIDE");
+  return side ? side[0] != '0' : s->triFastRows;
 }
 
-// One PD substep as a launch sequence (Solver.cpp:228-485).  `only` >= 0 (profile pass) launches one kernel
-// class of the tetrahedral pipeline; units tallies the work items of the launches made.
-void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
+// ---- the steps of a PD substep, in order (Solver.cpp:228-485) ----
+static float pd_h(const pies_solver* s) { return s->opt.fixedTimestepSize / s->opt.timeSubsteps; }
+static bool pd_tri(const Bracket& b) { return b.s->dev.pd.tri.nt != 0; }
+// the statistics of the substep's last solve are closed by an extra workgroup of the floor-snap launch when there is one
+static bool pd_stats_in_stabilize(const Bracket& b) {
+  return b.all() && b.s->opt.collisionStabilizationIterations > 0 && b.s->opt.iterations > 0 && b.s->dev.nd.n != 0;
+}
+
+static void pd_predict(Bracket& b) {
+  pies_solver* s = b.s;
+  b.run(PIES_KERNEL_PD_PREDICT, s->dev.nd.n,
+        [&] { launch_pd_predict(s->stream, s->dev.nd, s->dev.pd, pd_h(s), s->opt.floorHeight + s->opt.collisionThickness, pd_tri(b) && b.all()); });
+}
+
+// Solver.cpp:240, 245-248: point-triangle detection, contact list, their blocks of the system matrix
+static void pd_detect_triangles(Bracket& b) {
+  pies_solver* s = b.s;
   hipStream_t st = s->stream;
-  const float h = s->opt.fixedTimestepSize / s->opt.timeSubsteps;
   const PdArrays& pd = s->dev.pd;
-  int cur = -1;
-  auto ON = [&](int k) { const bool on = only < 0 || only == k; cur = k; if (on) probe_mark(s, k); return on; };
-  auto C = [&](int k, uint32_t n = 1) { if (k != PIES_KERNEL_PD_SPMV && k != PIES_KERNEL_PD_CG_UPDATE) probe_mark(s, k); if (counts) counts[k] += n; };
-  auto U = [&](uint64_t u) { if (units && (only >= 0 || (s->probe && s->probe->kernel == cur))) *units += u; };
+  s->triLevelsForked = tri_levels_forked(s);
+  const bool levelsInLine = !s->triLevelsForked && pd.cg.useCAp == 0;  // the contact-light variant computes them with the list
+  launch_tri_detect(st, pd.tri, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, s->opt.collisionThickness,
+                    pd.cg.useCAp != 0, levelsInLine);
+  // The dependency levels of the list (one workgroup, up to 1 ms with tens of thousands of contacts) are only needed by
+  // the sequential passes behind the local/global iterations: a second branch of the substep, joined there.
+  // Only in the contact-heavy graph variant: a fork and join inside a hipGraph costs about 100 us per replay (measured:
+  // config 3, no contact, 1 257 -> 1 120 substeps/s with the branch; 29k contacts, 197 -> 234 with it).
+  if (s->triLevelsForked) {
+    (void)hipEventRecord(s->evFork, st);
+    (void)hipStreamWaitEvent(s->sideStream, s->evFork, 0);
+    launch_tri_levels(s->sideStream, pd.tri);
+    (void)hipEventRecord(s->evJoin, s->sideStream);
+  } else if (!levelsInLine) {
+    launch_tri_levels(st, pd.tri);
+  }
+}
+
+// PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the predicted positions (where Solver.cpp:240 detects), after the
+// point-triangle detection so that dinv sees both contributions to the diagonal
+static void pd_detect_node_contacts(Bracket& b) {
+  pies_solver* s = b.s;
+  const PdArrays& pd = s->dev.pd;
+  grid_pass(b, false, nc_hash_launches(s), [&] { return launch_nc_detect(s->stream, s->dev.hash, s->dev.nc, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv); });
+}
+
+// local step (Solver.cpp:270-308): position constraints project to a constant, uploaded once
+static void pd_local_steps(Bracket& b) {
+  pies_solver* s = b.s;
+  hipStream_t st = s->stream;
+  const PdArrays& pd = s->dev.pd;
+  float4* pos = s->dev.nd.pos;
   const uint32_t nDist = (uint32_t)s->h_distance.size(), nTet = (uint32_t)s->h_tet.size(), nVol = (uint32_t)s->h_volume.size();
-  if (ON(PIES_KERNEL_PD_PREDICT)) { launch_pd_predict(st, s->dev.nd, pd, h, s->opt.floorHeight + s->opt.collisionThickness, pd.tri.nt != 0 && only < 0); U(s->dev.nd.n); }
-  C(PIES_KERNEL_PD_PREDICT);
-  const bool tri = pd.tri.nt != 0;
-  // the statistics of the substep's last solve are closed by an extra workgroup of the floor-snap launch when there is one
-  const bool statsInStabilize = only < 0 && s->opt.collisionStabilizationIterations > 0 && s->opt.iterations > 0 && s->dev.nd.n != 0;
-  if (tri && only < 0) {  // Solver.cpp:240, 245-248: detection, contact list, their blocks of the system matrix
-    const char* side = tuning_env("PIES_TRI_SIDE");  // diagnostics: 0 = always in line, 1 = always beside
-    s->triLevelsForked = side ? side[0] != '0' : s->triFastRows;
-    const bool levelsInLine = !s->triLevelsForked && pd.cg.useCAp == 0;  // the contact-light variant computes them with the list
-    launch_tri_detect(st, pd.tri, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, s->opt.collisionThickness,
-                      pd.cg.useCAp != 0, levelsInLine);
-    // The dependency levels of the list (one workgroup, up to 1 ms with tens of thousands of contacts) are only needed by
-    // the sequential passes behind the local/global iterations: a second branch of the substep, joined there.
-    // Only in the contact-heavy graph variant: a fork and join inside a hipGraph costs about 100 us per replay (measured:
-    // config 3, no contact, 1 257 -> 1 120 substeps/s with the branch; 29k contacts, 197 -> 234 with it).
-    if (s->triLevelsForked) {
-      (void)hipEventRecord(s->evFork, st);
-      (void)hipStreamWaitEvent(s->sideStream, s->evFork, 0);
-      launch_tri_levels(s->sideStream, pd.tri);
-      (void)hipEventRecord(s->evJoin, s->sideStream);
-    } else if (!levelsInLine) {
-      launch_tri_levels(st, pd.tri);
-    }
+  const TriArrays* contacts = pd_tri(b) && b.all() ? &pd.tri : nullptr;  // the paired launches take the contacts' local step along
+  if (nDist)
+    b.run(PIES_KERNEL_PD_LOCAL_DISTANCE, nDist, [&] { launch_pd_local_distance(st, pos, s->dev.d_dc_ids, s->dev.d_dc_rw, pd.contrib + s->slotBase[PIES_DISTANCE], nDist); });
+  if (s->tetVolumePaired && pd.tiles.ntiles) {  // tile-resident: one sum per (tile, node) leaves the chip (pd_tiles.cpp)
+    b.run(PIES_KERNEL_PD_LOCAL_TET, nTet, [&] { launch_pd_local_tiles(st, pos, pd.tiles, s->dev.d_pairDictTable, contacts, s->opt.collisionThickness); });
+  } else if (s->tetVolumePaired) {  // both projections in one launch, accounted to the strain class
+    b.run(PIES_KERNEL_PD_LOCAL_TET, nTet, [&] {
+      launch_pd_local_tet_pair(st, pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_vc_q2, pd.contrib + s->slotBase[PIES_TET],
+                               pd.contrib + s->slotBase[PIES_VOLUME], nTet, contacts, s->opt.collisionThickness, s->pdLocalPacked,
+                               s->pdLocalPacked ? s->dev.d_pairDictIndex : nullptr, s->dev.d_pairDictTable);
+    });
+  } else {
+    if (nTet)
+      b.run(PIES_KERNEL_PD_LOCAL_TET, nTet, [&] { launch_pd_local_tet(st, false, pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, pd.contrib + s->slotBase[PIES_TET], nTet); });
+    if (nVol)
+      b.run(PIES_KERNEL_PD_LOCAL_VOLUME, nVol, [&] { launch_pd_local_tet(st, true, pos, s->dev.d_vc_ids, s->dev.d_vc_q0, s->dev.d_vc_q1, s->dev.d_vc_q2, pd.contrib + s->slotBase[PIES_VOLUME], nVol); });
   }
-  // PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the predicted positions (where Solver.cpp:240 detects), after the
-  // point-triangle detection so that dinv sees both contributions to the diagonal
-  const bool nc = s->dev.ncActive;
-  if (nc) {
-    uint32_t nb = nc_hash_launches(s), nd = 1;  // (nd: the detection's launches)
-    if (ON(PIES_KERNEL_HASH)) { nb = launch_hash_build(st, s->dev.hash, s->dev.nd, s->opt.gridSpacing, s->sortPasses, false); U(s->dev.nd.n); }
-    probe_mark(s, PIES_KERNEL_HASH);
-    if (ON(PIES_KERNEL_COLLIDE)) { nd = launch_nc_detect(st, s->dev.hash, s->dev.nc, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv); U(s->dev.nd.n); }
-    probe_mark(s, PIES_KERNEL_COLLIDE);
-    if (counts) { counts[PIES_KERNEL_HASH] += nb; counts[PIES_KERNEL_COLLIDE] += nd; }
+  if (b.all()) {
+    launch_pd_local_bend(st, pos, s->dev.d_bc_ids, s->dev.d_bc_aw, pd.contrib + s->slotBase[PIES_BEND], (uint32_t)s->h_bend.size());
+    launch_pd_local_shape(st, pos, pd);  // goal targets are constants between transform updates
+    launch_pd_local_node_pair(st, pos, s->dev.nd.radius, s->dev.d_np_ids, pd.contrib + s->slotBase[5], (uint32_t)s->h_nodePair.size());
+    if (pd_tri(b) && !(s->tetVolumePaired && nTet)) launch_pd_local_tri(st, pd.tri, pos, s->opt.collisionThickness);  // Solver.cpp:298-300
   }
-  for (uint32_t it = 0; it < s->opt.iterations; ++it) {
-    // local step (Solver.cpp:270-308): position constraints project to a constant, uploaded once
-    if (nDist && ON(PIES_KERNEL_PD_LOCAL_DISTANCE)) {
-      launch_pd_local_distance(st, s->dev.nd.pos, s->dev.d_dc_ids, s->dev.d_dc_rw, pd.contrib + s->slotBase[PIES_DISTANCE], nDist);
-      U(nDist);
-    }
-    if (nDist) C(PIES_KERNEL_PD_LOCAL_DISTANCE);
-    if (s->tetVolumePaired && pd.tiles.ntiles) {  // tile-resident: one sum per (tile, node) leaves the chip (pd_tiles.cpp)
-      if (ON(PIES_KERNEL_PD_LOCAL_TET)) {
-        launch_pd_local_tiles(st, s->dev.nd.pos, pd.tiles, s->dev.d_pairDictTable, tri && only < 0 ? &pd.tri : nullptr, s->opt.collisionThickness);
-        U(nTet);
-      }
-      C(PIES_KERNEL_PD_LOCAL_TET);
-    } else if (s->tetVolumePaired) {  // both projections in one launch, accounted to the strain class
-      if (ON(PIES_KERNEL_PD_LOCAL_TET)) {
-        launch_pd_local_tet_pair(st, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, s->dev.d_vc_q2,
-                                 pd.contrib + s->slotBase[PIES_TET], pd.contrib + s->slotBase[PIES_VOLUME], nTet,
-                                 tri && only < 0 ? &pd.tri : nullptr, s->opt.collisionThickness, s->pdLocalPacked,
-                                 s->pdLocalPacked ? s->dev.d_pairDictIndex : nullptr, s->dev.d_pairDictTable);  // + the contacts' local step
-        U(nTet);
-      }
-      C(PIES_KERNEL_PD_LOCAL_TET);
-    } else {
-    if (nTet && ON(PIES_KERNEL_PD_LOCAL_TET)) {
-      launch_pd_local_tet(st, false, s->dev.nd.pos, s->dev.d_tc_ids, s->dev.d_tc_q0, s->dev.d_tc_q1, s->dev.d_tc_q2, pd.contrib + s->slotBase[PIES_TET], nTet);
-      U(nTet);
-    }
-    if (nTet) C(PIES_KERNEL_PD_LOCAL_TET);
-    if (nVol && ON(PIES_KERNEL_PD_LOCAL_VOLUME)) {
-      launch_pd_local_tet(st, true, s->dev.nd.pos, s->dev.d_vc_ids, s->dev.d_vc_q0, s->dev.d_vc_q1, s->dev.d_vc_q2, pd.contrib + s->slotBase[PIES_VOLUME], nVol);
-      U(nVol);
-    }
-    if (nVol) C(PIES_KERNEL_PD_LOCAL_VOLUME);
-    }
-    if (only < 0) {
-      launch_pd_local_bend(st, s->dev.nd.pos, s->dev.d_bc_ids, s->dev.d_bc_aw, pd.contrib + s->slotBase[PIES_BEND], (uint32_t)s->h_bend.size());
-      launch_pd_local_shape(st, s->dev.nd.pos, pd);                        // goal targets are constants between transform updates
-      launch_pd_local_node_pair(st, s->dev.nd.pos, s->dev.nd.radius, s->dev.d_np_ids, pd.contrib + s->slotBase[5], (uint32_t)s->h_nodePair.size());
-      if (tri && !(s->tetVolumePaired && nTet)) launch_pd_local_tri(st, pd.tri, s->dev.nd.pos, s->opt.collisionThickness);  // Solver.cpp:298-300
-    }
-    // Solver.cpp:266, 310-349.  (When a node's records are a few tile sums, the residual kernel of the one-launch-per-iteration
-    // CG evaluates the right-hand side itself.)
-    // (contact-heavy variant: a node's contact records are gathered by four lanes in k_pd_rhs, not by the residual kernel's one)
-    // (node-node contacts: their terms are added to the array k_pd_rhs writes, so the residual kernel does not evaluate it)
-    const bool single = pd_single_cg(s), fuseRhs = single && only < 0 && pd.rhsLanes == 1 && s->pdFuseRhs && !pd.cg.useCAp && !nc;
-    if (!fuseRhs) {
-      if (ON(PIES_KERNEL_PD_RHS)) { launch_pd_rhs(st, s->dev.nd, pd); U(s->dev.nd.n); }
-      C(PIES_KERNEL_PD_RHS);
-    } else if (counts) {
-      counts[PIES_KERNEL_PD_RHS] += 1;  // (the residual kernel that evaluates the right-hand side is counted - and bracketed - as this class)
-    }
-    if (nc) {  // the contacts' local step (CollisionConstraint.cpp:10-41, 49-65): w * projected, in list order
-      if (ON(PIES_KERNEL_COLLIDE)) { launch_nc_rhs(st, s->dev.nc, s->dev.nd, pd.rhs); U(s->dev.nd.n); }
-      C(PIES_KERNEL_COLLIDE);
-    }
-    const int overflow = s->pcgOverflow ? (int)(s->pcgMaxIters > s->pcgBudget ? s->pcgMaxIters - s->pcgBudget : 0u) : 0;
-    const bool lastSolve = it + 1 == s->opt.iterations && !statsInStabilize;
-    if (only < 0) {  // Solver.cpp:356-364
-      // a probed solve never takes the converged early exit: every bracketed launch does a full SpMV / vector update
-      // (PIES_PCG_NEVER_EXIT=1: the same for every solve of a captured substep - a diagnostics switch for profiler passes, so that a
-      // trace of a body at rest holds working CG launches instead of early exits; a converged column stands still, cg1_scalars)
-      const char* neverExitEnv = tuning_env("PIES_PCG_NEVER_EXIT");  // (read when the substep is captured)
-      const bool neverExitTuning = neverExitEnv && neverExitEnv[0] == '1';
-      const bool probed = neverExitTuning || (s->probe && (s->probe->kernel == PIES_KERNEL_PD_SPMV || s->probe->kernel == PIES_KERNEL_PD_CG_UPDATE));
-      auto hook = s->probe ? [](void* ctx, int cls) { probe_mark(static_cast<pies_solver*>(ctx), cls); } : (void (*)(void*, int))nullptr;
-      if (fuseRhs && units && s->probe && s->probe->kernel == PIES_KERNEL_PD_RHS) *units += s->dev.nd.n;
-      if (single) launch_pd_solve1(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, it == 0, lastSolve, fuseRhs, probed, hook, s, overflow);
-      else launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, -1, it == 0, lastSolve, probed, hook, s, overflow);
-      if (probed && s->probe && units) *units += (uint64_t)s->dev.nd.n * s->pcgBudget;
-    }
-    else if (only == PIES_KERNEL_PD_SPMV) {
-      if (single) launch_pd_solve1(st, s->dev.nd, pd, (int)s->pcgBudget, s->pcgTol, true, false, false, true);
-      else launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, 0.f, 1);
-      U((uint64_t)s->dev.nd.n * s->pcgBudget);
-    }
-    else if (only == PIES_KERNEL_PD_CG_UPDATE && !single) { launch_pd_solve(st, s->dev.nd, pd, (int)s->pcgBudget, 0.f, 0); U((uint64_t)s->dev.nd.n * s->pcgBudget); }
-    C(PIES_KERNEL_PD_SPMV, s->pcgBudget);
-    if (!single) C(PIES_KERNEL_PD_CG_UPDATE, s->pcgBudget);
+}
+
+// Solver.cpp:266, 310-349.  When a node's records are a few tile sums, the residual kernel of the one-launch-per-iteration CG
+// evaluates the right-hand side itself - not in the contact-heavy variant (a node's contact records are gathered by four lanes in
+// k_pd_rhs, not by the residual kernel's one) and not with node-node contacts (their terms are added to the array k_pd_rhs writes).
+static bool pd_fuse_rhs(const Bracket& b) {
+  const pies_solver* s = b.s;
+  return pd_single_cg(s) && b.all() && s->dev.pd.rhsLanes == 1 && s->pdFuseRhs && !s->dev.pd.cg.useCAp && !s->dev.ncActive;
+}
+static void pd_right_hand_side(Bracket& b) {
+  pies_solver* s = b.s;
+  if (!pd_fuse_rhs(b)) b.run(PIES_KERNEL_PD_RHS, s->dev.nd.n, [&] { launch_pd_rhs(s->stream, s->dev.nd, s->dev.pd); });
+  else if (b.counts) b.counts[PIES_KERNEL_PD_RHS] += 1;  // (the residual kernel that evaluates it is counted - and bracketed - as this class)
+  if (s->dev.ncActive)  // the contacts' local step (CollisionConstraint.cpp:10-41, 49-65): w * projected, in list order
+    b.run(PIES_KERNEL_COLLIDE, s->dev.nd.n, [&] { launch_nc_rhs(s->stream, s->dev.nc, s->dev.nd, s->dev.pd.rhs); });
+}
+
+// global step (Solver.cpp:356-364)
+static void pd_solve(Bracket& b, bool first, bool last) {
+  pies_solver* s = b.s;
+  hipStream_t st = s->stream;
+  const PdArrays& pd = s->dev.pd;
+  const bool single = pd_single_cg(s), fuseRhs = pd_fuse_rhs(b);
+  const int budget = (int)s->pcgBudget;
+  const uint64_t solveUnits = (uint64_t)s->dev.nd.n * s->pcgBudget;
+  const int overflow = s->pcgOverflow ? (int)(s->pcgMaxIters > s->pcgBudget ? s->pcgMaxIters - s->pcgBudget : 0u) : 0;
+  if (b.all()) {
+    // a probed solve never takes the converged early exit: every bracketed launch does a full SpMV / vector update
+    // (PIES_PCG_NEVER_EXIT=1: the same for every solve of a captured substep - a diagnostics switch for profiler passes, so that a
+    // trace of a body at rest holds working CG launches instead of early exits; a converged column stands still, cg1_scalars)
+    const char* neverExitEnv = tuning_env("PIES_PCG_NEVER_EXIT");  // (read when the substep is captured)
+    const bool neverExitTuning = neverExitEnv && neverExitEnv[0] == '1';
+    const bool probed = neverExitTuning || (s->probe && Bracket::bracketed_by_solve(s->probe->kernel));
+    auto hook = s->probe ? [](void* ctx, int cls) { probe_mark(static_cast<pies_solver*>(ctx), cls); } : (void (*)(void*, int))nullptr;
+    if (fuseRhs) { b.cur = PIES_KERNEL_PD_RHS; b.tally(s->dev.nd.n); }
+    if (single) launch_pd_solve1(st, s->dev.nd, pd, budget, s->pcgTol, first, last, fuseRhs, probed, hook, s, overflow);
+    else launch_pd_solve(st, s->dev.nd, pd, budget, s->pcgTol, -1, first, last, probed, hook, s, overflow);
+    if (probed && s->probe && b.units) *b.units += solveUnits;
+  } else if (b.only == PIES_KERNEL_PD_SPMV) {
+    if (single) launch_pd_solve1(st, s->dev.nd, pd, budget, s->pcgTol, true, false, false, true);
+    else launch_pd_solve(st, s->dev.nd, pd, budget, 0.f, 1);
+    b.tally(solveUnits);
+  } else if (b.only == PIES_KERNEL_PD_CG_UPDATE && !single) {
+    launch_pd_solve(st, s->dev.nd, pd, budget, 0.f, 0);
+    b.tally(solveUnits);
   }
-  if (tri && only < 0) {  // :367-383: every stabilisation iteration is a sequential pass over the contacts, then the floor snap
+  b.close(PIES_KERNEL_PD_SPMV, s->pcgBudget);
+  if (!single) b.close(PIES_KERNEL_PD_CG_UPDATE, s->pcgBudget);
+}
+
+// Solver.cpp:367-484: the stabilisation passes over the contacts and the floor snap, the velocities, then friction: listed node
+// pairs (:398-428), node-node contacts, triangles (:431-471), floor (:473-484).  PD_VELOCITY's bracket closes behind all of it.
+static void pd_stabilize_velocity_friction(Bracket& b) {
+  pies_solver* s = b.s;
+  hipStream_t st = s->stream;
+  const PdArrays& pd = s->dev.pd;
+  const float h = pd_h(s);
+  const bool tri = pd_tri(b) && b.all();
+  const uint32_t* ncCount = s->dev.ncActive ? s->dev.nc.cnt : nullptr;
+  const uint32_t* triUsed = tri ? pd.tri.usedBits : nullptr;
+  if (tri) {  // every stabilisation iteration is a sequential pass over the contacts, then the floor snap
     if (s->triLevelsForked) (void)hipStreamWaitEvent(st, s->evJoin, 0);
     // all iterations in one launch (the floor snap of the contacts' nodes between the passes), then the snap of everybody else:
     // idempotent, so once is what the reference's `iterations` times come to
     launch_tri_stabilize(st, pd.tri, s->dev.nd, s->opt.collisionThickness, pd.nstatic, pd.statp, s->opt.collisionStabilizationIterations);
-    if (s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->dev.nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
-    // velocities, then the contacts' friction (:431-471), then the floor friction (:473-484).  The floor friction of a node that is
-    // in no contact does not wait for the contacts: the velocity kernel applies it; the contacts' pass ends with that of its own nodes
-    // (the nodes of node-node contacts and of listed node pairs get their floor friction after their pairs' friction as well)
-    launch_pd_velocity(st, s->dev.nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, false, pd.tri.usedBits,
-                       nc ? s->dev.nc.cnt : nullptr, s->dev.d_np_bits);
-    if (only < 0) launch_pd_node_pair_friction(st, s->dev.nd.pos, s->dev.nd.vel, s->dev.nd.radius, s->dev.d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold, s->dev.d_np_nodes, s->dev.npNodes, pd.nstatic, pd.tri.usedBits,
-                                               nc ? s->dev.nc.cnt : nullptr);  // Solver.cpp:398-428 comes before the triangles' (:431-471)
-    if (nc && only < 0) enqueue_nc_friction(s, counts);
-    launch_tri_friction(st, pd.tri, s->dev.nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
-  } else {
-    if (only < 0 && s->opt.collisionStabilizationIterations > 0) launch_pd_stabilize(st, s->dev.nd, pd, statsInStabilize, (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));  // the floor snap is idempotent
-    if (ON(PIES_KERNEL_PD_VELOCITY)) {
-      launch_pd_velocity(st, s->dev.nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, true, nullptr,
-                         nc ? s->dev.nc.cnt : nullptr, s->dev.d_np_bits);
-      U(s->dev.nd.n);
-    }
-    if (only < 0) launch_pd_node_pair_friction(st, s->dev.nd.pos, s->dev.nd.vel, s->dev.nd.radius, s->dev.d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
-                                               s->opt.staticFrictionThreshold, s->dev.d_np_nodes, s->dev.npNodes, pd.nstatic, nullptr,
-                                               nc ? s->dev.nc.cnt : nullptr);
-    if (nc && only < 0) enqueue_nc_friction(s, counts);
   }
-  C(PIES_KERNEL_PD_VELOCITY);
+  if (b.all() && s->opt.collisionStabilizationIterations > 0)
+    launch_pd_stabilize(st, s->dev.nd, pd, pd_stats_in_stabilize(b), (int)s->pcgBudget, s->pcgTol, pd_single_cg(s));
+  // The floor friction of a node that is in no contact does not wait for the contacts: the velocity kernel applies it; the contacts'
+  // pass ends with that of its own nodes (the nodes of node-node contacts and of listed node pairs get theirs after their pairs' friction)
+  auto velocity = [&] {
+    launch_pd_velocity(st, s->dev.nd, pd, h, s->opt.damping, s->opt.gravity, s->opt.friction, s->opt.staticFrictionThreshold, !tri, triUsed, ncCount, s->dev.d_np_bits);
+  };
+  if (tri) velocity();
+  else if (b.open(PIES_KERNEL_PD_VELOCITY)) { velocity(); b.tally(s->dev.nd.n); }
+  if (b.all()) {
+    launch_pd_node_pair_friction(st, s->dev.nd.pos, s->dev.nd.vel, s->dev.nd.radius, s->dev.d_np_ids, (uint32_t)s->h_nodePair.size(), s->opt.friction,
+                                 s->opt.staticFrictionThreshold, s->dev.d_np_nodes, s->dev.npNodes, pd.nstatic, triUsed, ncCount);
+    if (s->dev.ncActive) {  // the contacts' friction in ascending pair key, then their nodes' floor friction; accounted to COLLIDE
+      NodeContactArrays C = s->dev.nc;
+      C.rounds = s->ncRounds;
+      b.run(PIES_KERNEL_COLLIDE, 0, [&] {
+        return launch_nc_friction(st, C, s->dev.hash, s->dev.nd, pd.nstatic, pd.tri.nt ? pd.tri.usedBits : nullptr, s->opt.friction, s->opt.staticFrictionThreshold);
+      });
+    }
+  }
+  if (tri) launch_tri_friction(st, pd.tri, s->dev.nd, s->opt.friction, s->opt.staticFrictionThreshold, pd.nstatic);
+  b.close(PIES_KERNEL_PD_VELOCITY);
+}
+
+// One PD substep as a launch sequence (Solver.cpp:228-485).  only >= 0 (profile pass) launches one kernel class of the
+// tetrahedral pipeline; units tallies the work items of the launches made.
+void enqueue_pd_substep(pies_solver* s, int only, uint32_t* counts, uint64_t* units) {
+  Bracket b{s, only, counts, units};
+  pd_predict(b);
+  if (pd_tri(b) && b.all()) pd_detect_triangles(b);
+  if (s->dev.ncActive) pd_detect_node_contacts(b);
+  for (uint32_t it = 0; it < s->opt.iterations; ++it) {
+    pd_local_steps(b);
+    pd_right_hand_side(b);
+    pd_solve(b, it == 0, it + 1 == s->opt.iterations && !pd_stats_in_stabilize(b));
+  }
+  pd_stabilize_velocity_friction(b);
 }
 
 void enqueue_substep(pies_solver* s, uint32_t* counts) {
@@ -521,7 +533,7 @@ void enqueue_substep(pies_solver* s, uint32_t* counts) {
 // The budget ladder: captured CG iterations per solve of the graphs instantiated together - 1, 2, 3, 4, 6, 8, 12, 16, ... up to
 // the ceiling of pies_set_pcg (the one-launch-per-iteration form pays one launch per unused iteration, so the low rungs are
 // close together); ladder_rung = the rung that holds `budget` iterations
-std::vector<uint32_t> ladder_rungs(const pies_solver* s) {
+static std::vector<uint32_t> ladder_rungs(const pies_solver* s) {
   std::vector<uint32_t> r;
   if (s->pcgMaxIters > 1) r.push_back(1);  // (a body at rest: the solves end at their first look at the residual)
   for (uint32_t b = 2; b < s->pcgMaxIters; b *= 2) {
@@ -531,27 +543,38 @@ std::vector<uint32_t> ladder_rungs(const pies_solver* s) {
   r.push_back(s->pcgMaxIters);
   return r;
 }
-uint32_t ladder_rung(const pies_solver* s, uint32_t budget) {
+static uint32_t ladder_rung(const pies_solver* s, uint32_t budget) {
   for (uint32_t r : ladder_rungs(s))
     if (r >= budget) return r;
   return s->pcgMaxIters;
 }
-bool uses_ladder(const pies_solver* s) {
+static bool uses_ladder(const pies_solver* s) {
   if (s->opt.solver != PIES_SOLVER_PD || s->pcgPinned || under_profiler()) return false;
   const char* e = tuning_env("PIES_NO_GRAPH");
   return !(e && e[0] == '1');
 }
+static uint64_t ladder_key(uint32_t budget, bool rows) { return static_cast<uint64_t>(budget) | (static_cast<uint64_t>(rows ? 1 : 0) << 32); }
 // makes the ladder entry of (pcgBudget, triFastRows) the graph pies_tick launches
 int select_pd_graph(pies_solver* s) {
   s->pcgBudget = ladder_rung(s, s->pcgBudget);
   s->dev.pd.cg.useCAp = s->triFastRows ? 1 : 0;
-  auto it = s->pdLadder.find(static_cast<uint64_t>(s->pcgBudget) | (static_cast<uint64_t>(s->triFastRows ? 1 : 0) << 32));
+  auto it = s->pdLadder.find(ladder_key(s->pcgBudget, s->triFastRows));
   if (it == s->pdLadder.end()) return fail(s, PIES_ERR_STATE, "no captured graph for this CG budget");
   s->graph = it->second.graph;
   s->graphExec = it->second.exec;
   s->graphFromLadder = true;
-  { const char* e = tuning_env("PIES_TRI_SIDE"); s->triLevelsForked = e ? e[0] != '0' : s->triFastRows; }  // (as the entry was captured)
+  s->triLevelsForked = tri_levels_forked(s);  // (as the entry was captured)
   std::memcpy(s->launchCounts, it->second.counts, sizeof(s->launchCounts));
+  return PIES_OK;
+}
+
+// Captures one substep into *graph, its launches per class into counts, and instantiates it as *exec.  Without exec the capture only counts.
+static int capture_substep(pies_solver* s, uint32_t* counts, hipGraph_t* graph, hipGraphExec_t* exec) {
+  HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+  enqueue_substep(s, counts);
+  hipError_t e = hipStreamEndCapture(s->stream, graph);
+  if (e != hipSuccess) return fail(s, PIES_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+  if (exec) HIP_TRY(s, hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
   return PIES_OK;
 }
 
@@ -561,44 +584,38 @@ int capture_graph(pies_solver* s) {
   if (s->dev.nd.n == 0) return PIES_OK;
   if (const char* e = tuning_env("PIES_NO_GRAPH"); e && e[0] == '1') {
     // count launches without running them: a capture that is thrown away
-    HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_substep(s, s->launchCounts);
     hipGraph_t tmp = nullptr;
-    HIP_TRY(s, hipStreamEndCapture(s->stream, &tmp));
+    const int rc = capture_substep(s, s->launchCounts, &tmp, nullptr);
     if (tmp) (void)hipGraphDestroy(tmp);
-    return PIES_OK;
+    return rc;
   }
-  if (uses_ladder(s)) {
-    // every rung, both contact-row variants when the scene has surface triangles: captured and instantiated now, so that
-    // following the solves later never instantiates a graph in the middle of a frame
-    const uint32_t wantBudget = s->pcgBudget;
-    const bool wantRows = s->triFastRows;
-    const std::vector<uint32_t> rungs = ladder_rungs(s);
-    const int variants = s->dev.pd.tri.nt ? 2 : 1;
-    for (int v = 0; v < variants; ++v)
-      for (uint32_t r : rungs) {
-        const bool rows = variants == 2 ? v != 0 : wantRows;
-        s->pcgBudget = r;
-        s->triFastRows = rows;
-        s->dev.pd.cg.useCAp = rows ? 1 : 0;
-        pies_solver::PdGraph g;
-        HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-        enqueue_substep(s, g.counts);
-        hipError_t e = hipStreamEndCapture(s->stream, &g.graph);
-        if (e != hipSuccess) return fail(s, PIES_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        HIP_TRY(s, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-        s->pdLadder[static_cast<uint64_t>(r) | (static_cast<uint64_t>(rows ? 1 : 0) << 32)] = g;
-      }
-    s->pcgBudget = wantBudget;
-    s->triFastRows = wantRows;
-    return select_pd_graph(s);
-  }
-  HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-  enqueue_substep(s, s->launchCounts);
-  hipError_t e = hipStreamEndCapture(s->stream, &s->graph);
-  if (e != hipSuccess) return fail(s, PIES_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  HIP_TRY(s, hipGraphInstantiate(&s->graphExec, s->graph, nullptr, nullptr, 0));
-  return PIES_OK;
+  if (!uses_ladder(s)) return capture_substep(s, s->launchCounts, &s->graph, &s->graphExec);
+  // every rung, both contact-row variants when the scene has surface triangles: captured and instantiated now, so that
+  // following the solves later never instantiates a graph in the middle of a frame
+  const uint32_t wantBudget = s->pcgBudget;
+  const bool wantRows = s->triFastRows;
+  const int variants = s->dev.pd.tri.nt ? 2 : 1;
+  for (int v = 0; v < variants; ++v)
+    for (uint32_t r : ladder_rungs(s)) {
+      const bool rows = variants == 2 ? v != 0 : wantRows;
+      s->pcgBudget = r;
+      s->triFastRows = rows;
+      s->dev.pd.cg.useCAp = rows ? 1 : 0;
+      pies_solver::PdGraph g;
+      if (int rc = capture_substep(s, g.counts, &g.graph, &g.exec)) return rc;
+      s->pdLadder[ladder_key(r, rows)] = g;
+    }
+  s->pcgBudget = wantBudget;
+  s->triFastRows = wantRows;
+  return select_pd_graph(s);
+}
+
+// A solve ran out of iterations above the tolerance: the budget to go on with, and no shrinking for the next 24 synchronisations
+uint32_t pcg_ran_short(pies_solver* s, uint32_t budget) {
+  s->pcgCalm = 0;
+  s->pcgWindowMax = 0;
+  s->pcgCooldown = 24;
+  return std::min(s->pcgMaxIters, std::max(32u, 4u * budget));  // 2..8 -> 32 -> 128: at most two short substeps
 }
 
 // The graph holds a fixed number of CG iterations per solve (converged solves early-exit the rest).  At
@@ -620,10 +637,7 @@ int adapt_pcg_budget(pies_solver* s) {
     // a solve ran out of iterations above the tolerance (new contacts stiffen the system at once): back to the full
     // budget now - the reference's solve is a direct one - and no shrinking for the next 24 synchronisations (a converged
     // solve's unused captured iterations return on one flag word: a generous budget costs 2.5 us per unused launch)
-    budget = std::min(s->pcgMaxIters, std::max(32u, 4u * budget));  // 2..8 -> 32 -> 128: at most two short substeps
-    s->pcgCalm = 0;
-    s->pcgWindowMax = 0;
-    s->pcgCooldown = 24;
+    budget = pcg_ran_short(s, budget);
   } else if (used > budget || (pd_single_cg(s) && used == budget && budget < s->pcgMaxIters)) {
     // converged, but only because the last launch went on by itself (k_cg_update's continuation): capture what it needed
     budget = std::min(s->pcgMaxIters, used + std::max(pd_single_cg(s) ? 1u : 2u, (used + 2u) / 3u));
@@ -696,20 +710,12 @@ int adapt_pair_rounds(pies_solver* s) {
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (deepest == 0) return PIES_OK;  // no pass since the last look
   HIP_TRY(s, hipMemsetAsync(s->dev.pairs.ctl + kPairDeepest, 0, sizeof(uint32_t), s->stream));
-  uint32_t rounds = s->pairRounds;
   // (the reference's order by turns runs deeper than the pair order: ~850 levels per pass of config 4)
   const uint32_t cap = collision_order(s) == PIES_COLLISION_ORDER_REFERENCE ? 4096u : 1024u;
   // (round 5: eight more than the deepest pass seen, in steps of 8 - a quarter more on top of that were 24 launches per settled pass of
   // config 4 that found nothing to do, 40 with the repeat's half again: VERDICT r4 item 6)
   const uint32_t want = std::min(cap, ((deepest + 8u + 7u) / 8u) * 8u);
-  if (deepest > rounds) { rounds = want; s->pairCalm = 0; }
-  else if (want < rounds) { if (++s->pairCalm >= 3) { rounds = want; s->pairCalm = 0; } }
-  else s->pairCalm = 0;
-  if (rounds != s->pairRounds) {
-    s->pairRounds = rounds;
-    return capture_graph(s);
-  }
-  return PIES_OK;
+  return follow(deepest > s->pairRounds, want, s->pairRounds, s->pairCalm, 3) ? capture_graph(s) : PIES_OK;
 }
 
 // Radix passes of the node grid's sort: a pass takes up to 11 bits of the cell key, whose width follows the cell box of the
@@ -729,15 +735,8 @@ int adapt_sort_passes(pies_solver* s) {
     while (ext) { ++bits; ext >>= 1; }
   }
   const uint32_t want = sort_passes_for(bits);
-  uint32_t passes = s->sortPasses;
-  if (want > passes) { passes = want; s->sortCalm = 0; }
-  else if (want < passes) { if (++s->sortCalm >= 8) { passes = want; s->sortCalm = 0; } }
-  else s->sortCalm = 0;
-  if (passes != s->sortPasses) {
-    s->sortPasses = passes;
-    if (s->graphExec) return capture_graph(s);  // (without a captured graph the next tick's launches take the new count)
-  }
-  return PIES_OK;
+  if (follow(want > s->sortPasses, want, s->sortPasses, s->sortCalm, 8) && s->graphExec) return capture_graph(s);
+  return PIES_OK;  // (without a captured graph the next tick's launches take the new count)
 }
 
 // PIES_FLAG_PD_NODE_CONTACTS: friction rounds captured per substep.  At host synchronisations they follow the deepest pass seen
@@ -753,15 +752,7 @@ int adapt_nc_rounds(pies_solver* s) {
   HIP_TRY(s, hipMemsetAsync(s->dev.nc.ctl + kNcDeepest, 0, sizeof(uint32_t), s->stream));
   const uint32_t depth = deepest - 1u;
   const uint32_t want = depth == 0 ? 1u : std::min(kNcMaxRounds, depth + 2u);
-  uint32_t rounds = s->ncRounds;
-  if (depth > rounds) { rounds = want; s->ncCalm = 0; }
-  else if (want < rounds) { if (++s->ncCalm >= 8) { rounds = want; s->ncCalm = 0; } }
-  else s->ncCalm = 0;
-  if (rounds != s->ncRounds) {
-    s->ncRounds = rounds;
-    return capture_graph(s);
-  }
-  return PIES_OK;
+  return follow(depth > s->ncRounds, want, s->ncRounds, s->ncCalm, 8) ? capture_graph(s) : PIES_OK;
 }
 
 int poll_failure(pies_solver* s) {
@@ -796,6 +787,15 @@ int poll_failure(pies_solver* s) {
                           : "a node left the supported cell range (non-finite position)";
   }
   return PIES_OK;
+}
+
+// what every host synchronisation is followed by: the failure latch, then the adaptations
+int after_synchronize(pies_solver* s) {
+  if (int rc = poll_failure(s)) return rc;  // a loop of pies_tick_async learns here that the simulation failed
+  if (int rc = adapt_pair_rounds(s)) return rc;
+  if (int rc = adapt_sort_passes(s)) return rc;
+  if (int rc = adapt_nc_rounds(s)) return rc;
+  return adapt_pcg_budget(s);
 }
 
 }  // namespace pies
