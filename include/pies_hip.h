@@ -92,9 +92,12 @@ enum {
   PIES_LAYER_REST_SETS = 23,   /* pies_count only: distinct sets of rest constants (Qinv, strain limits, w) in the rest dictionary of
                                   schedule LAYERED's tetrahedral container (PBD), 0: the per-element arrays are read (after
                                   pies_finalize; tuning switch PIES_LAYER_REST_DICT=0 forces 0) */
-  PIES_LAYER_MAX_TILES = 24    /* pies_count only: tiles (= workgroups of a launch) of the phase of schedule LAYERED's plan that has
+  PIES_LAYER_MAX_TILES = 24,   /* pies_count only: tiles (= workgroups of a launch) of the phase of schedule LAYERED's plan that has
                                   most, 0 when the plan is not active (after pies_finalize); more than the device's 256 compute
                                   units select the four-wavefronts-per-SIMD kernel variants */
+  PIES_LAYER_MAX_CLASS = 25    /* pies_count only: constraints of the largest colour class of any tile and container of schedule
+                                  LAYERED's plan, 0 when the plan is not active (after pies_finalize); with at most 256 tiles it
+                                  selects the workgroup of the layer kernel: 256 threads up to 256, 512 up to 512, else 1 024 */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.

@@ -41,6 +41,7 @@ NODE_CONTACTS = 20  # pies_count: node-node contacts of the last PD substep (FLA
 SKINS, SKIN_VERTICES = 21, 22  # pies_count: embedded surface meshes (pies_add_skin) and their vertices over all skins
 LAYER_REST_SETS = 23  # pies_count: sets in the rest dictionary of schedule LAYERED's tetrahedral container (0: per-element arrays)
 LAYER_MAX_TILES = 24  # pies_count: tiles of the phase of schedule LAYERED's plan that has most (0: not active)
+LAYER_MAX_CLASS = 25  # pies_count: the largest colour class of any tile and container of schedule LAYERED's plan (0: not active)
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)

@@ -775,6 +775,12 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
         for (int ph = 0; ph < 4; ++ph) *out = std::max<uint32_t>(*out, (uint32_t)s->layer.tiles[ph].size());
       break;
     }
+    case PIES_LAYER_MAX_CLASS: {
+      *out = 0;
+      if (s->layer.active)
+        for (const LayerKind& K : s->layer.kind) *out = std::max<uint32_t>(*out, K.maxClass);
+      break;
+    }
     case PIES_SKINS: *out = (uint32_t)s->h_skins.size(); break;
     case PIES_SKIN_VERTICES: {
       *out = 0;

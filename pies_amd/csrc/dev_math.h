@@ -39,6 +39,16 @@ PIES_DEV bool pies_bounds_note(bool ok, unsigned int site) {
 #define PIES_BOUNDS_REPORT(name)
 #endif
 
+// tools/layer_isa.py compiles with -DPIES_PATH_NOTES: the rare paths of the tetrahedral projection then carry a comment in the ISA, by
+// which the tool tells them from the path every element takes.  Nothing in the product build.
+#ifdef PIES_PATH_NOTES
+#define PIES_RARE_PATH() asm volatile("; pies-rare-path")
+#define PIES_MAIN_TET_PATH() asm volatile("; pies-main-tet-path")  // the main tetrahedral colour loop of k_layer, at its gather
+#else
+#define PIES_RARE_PATH()
+#define PIES_MAIN_TET_PATH()
+#endif
+
 // Workgroups are dealt round-robin over the 8 XCDs (observed, MI355X_MICROARCH.md "Workgroup dispatch"), each
 // with a private 4 MiB L2.  Gather kernels whose work items are stored in mesh order use this bijective
 // relabelling so that one XCD processes one contiguous eighth of the items and neighbouring items' node
@@ -262,6 +272,7 @@ PIES_DEV void svd3(const float a[3][3], Svd3& d) {
     (void)jacobi_pair<0, 1>(d);
     jacobi_polish(d);
   } else {
+    PIES_RARE_PATH();
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -285,6 +296,7 @@ PIES_DEV void svd3(const float a[3][3], Svd3& d) {
       const bool t02 = pair_needs(n0, n2, g02), t12 = pair_needs(n1, n2, g12), t01 = pair_needs(n0, n1, g01);
       clean = !(int(t02) | int(t12) | int(t01));  // (no short circuit: one branch)
       if (clean) break;
+      PIES_RARE_PATH();
       (void)jacobi_pair<0, 2>(d);
       (void)jacobi_pair<1, 2>(d);
       (void)jacobi_pair<0, 1>(d);
@@ -332,6 +344,7 @@ PIES_DEV void svd3_recompose(const Svd3& d, const float snew[3], float out[3][3]
   }
   const int nbad = (ok0 ? 0 : 1) + (ok1 ? 0 : 1) + (ok2 ? 0 : 1);
   if (nbad == 1) {  // a flattened element
+    PIES_RARE_PATH();
     if (!ok0) complete_t<0, 1, 2>(d, t, snew[0]);
     else if (!ok1) complete_t<1, 2, 0>(d, t, snew[1]);
     else complete_t<2, 0, 1>(d, t, snew[2]);

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "layer_rest.h"
 #include "pbd_project.h"
+#include "tet_rows.h"
 
 namespace pies {
 
@@ -52,7 +53,9 @@ PIES_DEV uint32_t hi16(uint32_t v) { return v >> 16; }
 // bound by throughput and wants two 512-thread workgroups resident per compute unit: 4 wavefronts per SIMD, 128 registers.
 // DICT: the tetrahedral segments take Qinv, the strain limits and w from the rest dictionary in LDS (the set index rides in the spare
 // bits of tc_lid) instead of three float4 per element from HBM.  A template parameter: neither path pays the other's registers.
-template <int BLOCK, int TETV, int WPE = 1, bool DICT = false>
+// FORM: 1 = the tetrahedral projection on row pairs with its rare paths behind wave-uniform tests (tet_rows.h), 0 = tet_core; the
+// same bits either way.  The 256-register instantiations have both (launch_layer: PIES_LAYER_TET_FORM); the 128-register ones keep tet_core.
+template <int BLOCK, int TETV, int WPE = 1, bool DICT = false, int FORM = 0>
 __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D, LayerLaunch L, LayerParams P) {
   static_assert(3 * kLayerRestMaxSets <= BLOCK, "the prologue requests the rest dictionary with one load per lane");
   constexpr int kDistPreload = (WPE > 1 || BLOCK > 512) ? 6 : kDistPreloadMax;
@@ -174,6 +177,16 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
     const float4* __restrict__ row = stab + 3u * layer_rest_set(w.x, w.y);
     q0 = row[0]; q1 = row[1]; q2 = row[2];
   };
+  // one element's projection in the instantiation's form (FORM 1 with the dictionary reads the table's row as pairs itself)
+  auto project = [&](const uint2& w, float4& x1, float4& x2, float4& x3, float4& x4, float4& q0, float4& q1, float4& q2) {
+    if (FORM == 1 && TETV == 0) {
+      if (DICT) rows::tet_rows(x1, x2, x3, x4, rows::rest_of(reinterpret_cast<const float*>(stab + 3u * layer_rest_set(w.x, w.y))));
+      else rows::tet_rows(x1, x2, x3, x4, rows::rest_of(q0, q1, q2));
+    } else {
+      if (DICT) rest_read(w, q0, q1, q2);
+      tet_core<TETV>(x1, x2, x3, x4, q0, q1, q2);
+    }
+  };
 
   for (uint32_t s = 0; s < L.nseg; ++s) {
     const uint32_t kind = L.seg[s].kind, ncol = L.seg[s].ncol;
@@ -218,27 +231,27 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
         uint32_t i1, i2, i3, i4;
         tet_ids(id, i1, i2, i3, i4);
         if (have && PIES_IN_BOUNDS(max(max(i1, i2), max(i3, i4)) < m, 11u) && rest_ok(id)) {
-          if (DICT) rest_read(id, a0, a1, a2);
+          PIES_MAIN_TET_PATH();
           float4 x1 = sp[i1], x2 = sp[i2], x3 = sp[i3], x4 = sp[i4];
 #ifdef PIES_EXPERIMENTS
           if (stampBase) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); PIES_STAMP(); }  // the gather has landed
 #endif
-          tet_core<TETV>(x1, x2, x3, x4, a0, a1, a2);
+          project(id, x1, x2, x3, x4, a0, a1, a2);
 #ifdef PIES_EXPERIMENTS
           if (stampBase) { asm volatile("" : "+v"(x1.x), "+v"(x2.x), "+v"(x3.x), "+v"(x4.x)); PIES_STAMP(); }  // the projection is done
 #endif
           sp[i1] = x1; sp[i2] = x2; sp[i3] = x3; sp[i4] = x4;
         }
         for (uint32_t t = lo + tid + BLOCK; t < hi; t += BLOCK) {  // classes larger than the workgroup
+          PIES_RARE_PATH();
           const uint2 jd = D.tc_lid[t];
           uint32_t j1, j2, j3, j4;
           tet_ids(jd, j1, j2, j3, j4);
           if (!rest_ok(jd)) continue;
           float4 q0, q1, q2;
-          if (DICT) rest_read(jd, q0, q1, q2);
-          else { q0 = D.tc_q0[t]; q1 = D.tc_q1[t]; q2 = D.tc_q2[t]; }
+          if (!DICT) { q0 = D.tc_q0[t]; q1 = D.tc_q1[t]; q2 = D.tc_q2[t]; }
           float4 x1 = sp[j1], x2 = sp[j2], x3 = sp[j3], x4 = sp[j4];
-          tet_core<TETV>(x1, x2, x3, x4, q0, q1, q2);
+          project(jd, x1, x2, x3, x4, q0, q1, q2);
           sp[j1] = x1; sp[j2] = x2; sp[j3] = x3; sp[j4] = x4;
         }
         lds_barrier();
@@ -459,6 +472,8 @@ static hipError_t layer_prepare_variants(int bytes) {
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 4, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 4, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<1024, 0, 1, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 1, DICT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 1, DICT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   return e;
 }
 hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets) {
@@ -468,8 +483,13 @@ hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets) {
 }
 
 template <bool DICT>
-static void launch_layer_variant(hipStream_t st, uint32_t want, bool throughput, size_t lds, const NodeArrays& nd, const LayerData& D,
-                                 const LayerLaunch& L, const LayerParams& P) {
+static void launch_layer_variant(hipStream_t st, uint32_t want, bool throughput, bool rowForm, size_t lds, const NodeArrays& nd,
+                                 const LayerData& D, const LayerLaunch& L, const LayerParams& P) {
+  if (rowForm && !throughput && want <= 512) {  // the 256-register instantiations with the projection on row pairs (tet_rows.h)
+    if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0, 1, DICT, 1>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+    else hipLaunchKernelGGL((k_layer<512, 0, 1, DICT, 1>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
+    return;
+  }
   if (want <= 256 && throughput) hipLaunchKernelGGL((k_layer<256, 0, 4, DICT>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
   else if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0, 1, DICT>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
   else if (want <= 512 && throughput) hipLaunchKernelGGL((k_layer<512, 0, 4, DICT>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
@@ -513,8 +533,10 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
   uint32_t want = forceBlock ? forceBlock : L.maxClass;
   if (!forceBlock && L.groups > 256u) want = std::min<uint32_t>(want, 512u);  // (256 compute units)
   const bool throughput = L.groups > 256u;  // several tiles per compute unit
-  if (restDict) launch_layer_variant<true>(st, want, throughput, lds, nd, D, L, P);
-  else launch_layer_variant<false>(st, want, throughput, lds, nd, D, L, P);
+  // PIES_LAYER_TET_FORM=0 (tuning switch; tests and A/B): tet_core in every instantiation.  The same bits either way.
+  const bool rowForm = [] { const char* e = tuning_env("PIES_LAYER_TET_FORM"); return !e || e[0] != '0'; }();
+  if (restDict) launch_layer_variant<true>(st, want, throughput, rowForm, lds, nd, D, L, P);
+  else launch_layer_variant<false>(st, want, throughput, rowForm, lds, nd, D, L, P);
 }
 
 }  // namespace pies

@@ -1,52 +1,219 @@
 #!/usr/bin/env python3
-"""Static VALU / scalar / memory instruction counts per basic block of k_layer<256>'s tetrahedral colour loop, in the gfx950 ISA
-hipcc emits for the product build (cross-compilation only: runs without a GPU).
-usage: python tools/layer_isa.py [--streamed] > profiles/r07_layer_isa.txt"""
+"""Static instruction counts of k_layer's MAIN tetrahedral colour loop in the gfx950 ISA hipcc emits for the product flags
+(cross-compilation only: runs without a GPU), per basic block and summed along the path every element of BASELINE config 2 takes:
+from the block after the barrier through the closed form, one rotation, the polish and one clean certifying snapshot to the
+scatter and the barrier.
+
+The main loop's gather and the rare paths (the start of an element with fewer than two pairs out of tolerance, the rotating sweeps, the completion
+of a collapsed direction, the loop for classes larger than the workgroup) are told from the common one by a comment the
+sources emit under -DPIES_PATH_NOTES (dev_math.h: PIES_MAIN_TET_PATH, PIES_RARE_PATH); the tool compiles once with and once without it and reports
+both kernels' lengths, so that a difference made by the notes shows.
+
+usage: python tools/layer_isa.py [--block 512] [--streamed] [--json profiles/rNN_layer_critical_path.json] [extra compiler flags]
+       > profiles/rNN_layer_isa.txt"""
+import json
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-DICT = 0 if "--streamed" in sys.argv else 1  # the instantiation with the rest dictionary (the headline's), or the streamed one
-sys.argv = [a for a in sys.argv if a != "--streamed"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-with tempfile.TemporaryDirectory() as tmp:
-    out = os.path.join(tmp, "layer.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-S", os.path.join(ROOT, "pies_amd/csrc/layer_kernels.hip"), "-o", out, "-O3", "-std=c++17",
-                           "-ffp-contract=off", "-fno-fast-math"] + sys.argv[1:] + ["--offload-arch=gfx950", "--cuda-device-only", "-I", os.path.join(ROOT, "include")],
+MOVES = ("v_mov_b32", "v_mov_b64", "v_pk_mov_b32", "v_accvgpr")
+MEMORY = ("ds_", "global_", "buffer_", "flat_", "scratch_")
+
+
+def take(argv, flag, default=None):
+    if flag in argv:
+        i = argv.index(flag)
+        v = argv[i + 1]
+        del argv[i:i + 2]
+        return v
+    return default
+
+
+def compile_isa(tmp, name, flags):
+    out = os.path.join(tmp, name)
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    subprocess.check_call([hipcc, "-S", os.path.join(ROOT, "pies_amd/csrc/layer_kernels.hip"), "-o", out, "-O3", "-std=c++17", "-ffp-contract=off",
+                           "-fno-fast-math"] + flags + ["--offload-arch=gfx950", "--cuda-device-only", "-I", os.path.join(ROOT, "include")],
                           stderr=subprocess.DEVNULL)
-    txt = open(out).read()
-m = re.search(r"^_ZN4pies7k_layerILi256ELi0ELi1ELb%dEEE.*?s_endpgm" % DICT, txt, re.S | re.M)
-lines = m.group(0).splitlines()
-meta = re.search(r"_ZN4pies7k_layerILi256ELi0ELi1ELb%dEEE.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)" % DICT, txt, re.S)
-print("k_layer<256, 0, 1, " + ("true" if DICT else "false") + ">: %d lines of ISA, %s VGPRs, scratch %s bytes, occupancy %s" % (len(lines), meta.group(1), meta.group(2), meta.group(3)))
-# the tetrahedral colour loop: the first loop whose body holds four 12/16-byte LDS reads followed (later) by four LDS writes and a barrier
-blocks, cur = [], None
-for l in lines:
-    t = l.strip()
-    if re.match(r"^\.LBB\d+_\d+:", t) or re.match(r"^; %bb\.\d+:", t):
-        cur = {"name": t.split(":")[0].replace("; %", ""), "valu": 0, "salu": 0, "mem": 0, "ops": [], "br": []}
-        blocks.append(cur)
-        continue
-    if cur is None or not t or t.startswith((";", ".")):
-        continue
-    op = t.split()[0]
-    cur["ops"].append(op)
-    if op.startswith("v_"):
-        cur["valu"] += 1
-    elif op.startswith(("ds_", "global_", "buffer_", "flat_")):
-        cur["mem"] += 1
-    elif op.startswith("s_"):
-        cur["salu"] += 1
+    with open(out) as f:
+        return f.read()
+
+
+def kernel_text(txt, sym):
+    m = re.search(r"^%s\S*:.*?s_endpgm" % sym, txt, re.S | re.M)
+    meta = re.search(r"%s.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)" % sym, txt, re.S)
+    return m.group(0).splitlines(), meta.groups()
+
+
+def basic_blocks(lines):
+    """true basic blocks: split at labels and after every branch.  name = the label, or label+k for the k-th piece after it"""
+    blocks, cur, label, piece = [], None, "entry", 0
+
+    def start(name):
+        b = {"name": name, "ops": [], "rare": False, "main": False, "branch": None}
+        blocks.append(b)
+        return b
+    cur = start(label)
+    for raw in lines:
+        t = raw.strip()
+        m = re.match(r"^(\.LBB\d+_\d+):", t)
+        if m:
+            label, piece = m.group(1), 0
+            cur = start(label)
+            continue
+        if "pies-rare-path" in t:
+            cur["rare"] = True
+        if "pies-main-tet-path" in t:
+            cur["main"] = True
+        if not t or t.startswith((";", ".")):
+            continue
+        op = t.split()[0]
+        cur["ops"].append(op)
         if op.startswith(("s_cbranch", "s_branch")):
-            cur["br"].append(t.replace("\t", " "))
-start = next(i for i, b in enumerate(blocks) if sum(o in ("ds_read_b96", "ds_read_b128") for o in b["ops"]) >= 4 and
-             sum(o == "global_load_dwordx4" for o in b["ops"]) >= (0 if DICT else 3) and any(o == "global_load_dwordx2" for o in b["ops"]))  # (the next colour's records are requested at the head of the body)
-end = next(i for i in range(start, len(blocks)) if "s_barrier" in blocks[i]["ops"] or (i > start and sum(o.startswith("ds_write_b") for o in blocks[i]["ops"]) >= 4))
-print("tetrahedral colour loop: blocks %s .. %s" % (blocks[start]["name"], blocks[end]["name"]))
-tot = 0
-for b in blocks[start:end + 1]:
-    tot += b["valu"]
-    print("  %-12s VALU %4d  scalar %3d  memory %2d   %s" % (b["name"], b["valu"], b["salu"], b["mem"], "; ".join(b["br"])))
-print("VALU instructions in the loop body (all paths): %d" % tot)
+            cur["branch"] = (op, t.split()[1])
+            piece += 1
+            cur = start("%s+%d" % (label, piece))
+    return blocks
+
+
+def counts(b):
+    ops = b["ops"]
+    valu = [o for o in ops if o.startswith("v_")]
+    return {"all": len(ops), "valu": len(valu), "moves": sum(o.startswith(MOVES) for o in valu),
+            "packed": sum(o.startswith("v_pk_") and not o.startswith("v_pk_mov") for o in valu),
+            "waits": sum(o.startswith("s_waitcnt") for o in ops),
+            "scalar": sum(o.startswith("s_") and not o.startswith("s_waitcnt") for o in ops),
+            "memory": sum(o.startswith(MEMORY) for o in ops)}
+
+
+def main_loop_path(blocks):
+    index = {b["name"]: i for i, b in enumerate(blocks)}
+    marked = [i for i, b in enumerate(blocks) if b["main"]]
+    if len(marked) != 1:
+        raise SystemExit("the main tetrahedral colour loop's note was found %d times" % len(marked))
+    header = back = marked[0]
+
+    def rare(i, depth=0):
+        b = blocks[i]
+        if b["rare"]:
+            return True
+        only_jump = all(o.startswith(("s_branch", "s_or_b64", "s_mov_b64", "s_nop")) for o in b["ops"])
+        if only_jump and depth < 4:
+            if b["branch"] and b["branch"][0] == "s_branch":
+                return rare(index[b["branch"][1]], depth + 1)
+        return False
+    def succ(i):
+        b = blocks[i]
+        if not b["branch"]:
+            return [i + 1] if i + 1 < len(blocks) else []
+        op, target = b["branch"]
+        return [index[target]] if op == "s_branch" else [index[target], i + 1]
+
+    def distance_home(i):  # blocks from i back to the loop's gather, not through a rare path
+        seen, front, d = {i}, [i], 0
+        while front and d < 200:
+            if header in front:
+                return d
+            front = [j for k in front for j in succ(k) if j not in seen and not rare(j) and not seen.add(j)]
+            d += 1
+        return 1 << 30
+    path, i, notes = [], header, []
+    while True:
+        b = blocks[i]
+        if i == header and path:
+            break
+        path.append(i)
+        if len(path) > 400:
+            raise SystemExit("the walk does not come back to the loop's gather: " + " ".join(blocks[k]["name"] for k in path[:60]))
+        if not b["branch"]:
+            i += 1
+            continue
+        op, target = b["branch"]
+        t, f = index[target], i + 1
+        if op == "s_branch":
+            i = t
+        elif rare(f) and not rare(t):
+            i = t
+        elif rare(t):
+            i = f
+        elif op == "s_cbranch_execz":
+            i = f  # (lanes are active: the guarded region runs)
+        elif op == "s_cbranch_execnz":
+            i = t
+        else:  # a scalar condition (the loop's own tests): the way that stays in the loop
+            i = t if distance_home(t) < distance_home(f) else f
+        other = t if i == f else f
+        if i in path and i != header and other not in path and not rare(other):  # an inner loop (the sweeps) is left after its first, clean pass
+            i = other
+    return header, back, path, notes
+
+
+def report(txt, sym, title):
+    lines, (vgprs, scratch, occupancy) = kernel_text(txt, sym)
+    blocks = basic_blocks(lines)
+    header, back, path, notes = main_loop_path(blocks)
+    print("%s: %d lines of ISA, %s VGPRs, scratch %s bytes, occupancy %s" % (title, len(lines), vgprs, scratch, occupancy))
+    print("main tetrahedral colour loop (gather in block %s); * = on the path of a config-2 element" % blocks[header]["name"])
+    total = dict.fromkeys(("all", "valu", "moves", "packed", "scalar", "waits", "memory"), 0)
+    lo, hi = min(path), max(path)
+    for i in range(lo, hi + 1):
+        c = counts(blocks[i])
+        if not c["all"]:
+            continue
+        on = i in path
+        if on:
+            for k in total:
+                total[k] += c[k]
+        print(" %s %-16s all %4d  VALU %4d (moves %3d, packed %3d)  scalar %3d  waits %2d  memory %2d%s" %
+              ("*" if on else " ", blocks[i]["name"], c["all"], c["valu"], c["moves"], c["packed"], c["scalar"], c["waits"], c["memory"],
+               "  [rare]" if blocks[i]["rare"] else ""))
+    for n in notes:
+        print("  note: " + n)
+    print("per colour step along the path: all %(all)d, VALU %(valu)d (moves %(moves)d, packed %(packed)d), scalar %(scalar)d, waits %(waits)d, memory %(memory)d"
+          % total)
+    print()
+    return total, len(lines), (vgprs, scratch)
+
+
+def main():
+    argv = sys.argv[1:]
+    block = int(take(argv, "--block", "512"))
+    json_out = take(argv, "--json")
+    dict_ = 0 if "--streamed" in argv else 1
+    argv = [a for a in argv if a != "--streamed"]
+    with tempfile.TemporaryDirectory() as tmp:
+        noted = compile_isa(tmp, "noted.s", ["-DPIES_PATH_NOTES"] + argv)
+        plain = compile_isa(tmp, "plain.s", argv)
+    out = {}
+    for form, what in ((0, "tet_core (the form before tet_rows.h)"), (1, "tet_rows.h")):
+        sym = "_ZN4pies7k_layerILi%dELi0ELi1ELb%dELi%dEEE" % (block, dict_, form)
+        title = "k_layer<%d, 0, 1, %s, %d>, %s" % (block, "true" if dict_ else "false", form, what)
+        total, n_noted, regs = report(noted, sym, title)
+        n_plain = len(kernel_text(plain, sym)[0])
+        vg, sc = kernel_text(plain, sym)[1][:2]
+        print("  (the product build of this kernel, without the notes: %d lines of ISA against %d with them; %s VGPRs, scratch %s)\n" % (n_plain, n_noted, vg, sc))
+        out[form] = total
+    print("registers of every instantiation (product flags):")
+    for m in re.finditer(r"^(_ZN4pies7k_layerI\S+):.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", plain, re.S | re.M):
+        print("  %-48s VGPRs %3s  scratch %s" % (m.group(1), m.group(2), m.group(3)))
+    if json_out:
+        with open(os.path.join(ROOT, "profiles", "r06_layer_critical_path.json")) as f:
+            base = json.load(f)
+        base["what"] = ("VALU instructions the busiest wavefront of a k_layer tile executes in one launch of BASELINE config 2, as in "
+                        "r06_layer_critical_path.json; tet_colour_valu recounted by tools/layer_isa.py along the config-2 path of the main loop of "
+                        "k_layer<%d, 0, 1, true, 1> (tet_rows.h); the distance and load/store figures are r06's." % block)
+        base["tet_colour_valu"] = out[1]["valu"]
+        base["tet_colour_all_instructions"] = out[1]["all"]
+        base["tet_colour_valu_tet_core_form"] = out[0]["valu"]
+        base["tet_colour_all_instructions_tet_core_form"] = out[0]["all"]
+        base.pop("cross_check", None)
+        with open(json_out, "w") as f:
+            json.dump(base, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -2,8 +2,9 @@
 """Where does a k_layer launch spend its time?  In-kernel time stamps (s_memtime) of the diagnostic build
 (python -m pies_amd.build --exp; PIES_LIB selects it), BASELINE config 2 in the state bench.py times (after 25 ticks).
 One stamp after the tile's node records are in LDS, one after every colour's barrier, one at the end; lane 0 of wavefront 0
-of every tile; the table is printed with the tetrahedral rest dictionary off and on, twice each.
-usage: python tools/layer_timeline.py [ticks_before] > profiles/r07_layer_timeline.txt"""
+of every tile, and around every tetrahedral projection of that lane; the table is printed with the projection on row pairs
+(tet_rows.h) off (PIES_LAYER_TET_FORM=0: tet_core) and on, twice each.
+usage: python tools/layer_timeline.py [ticks_before] > profiles/r08_layer_timeline.txt"""
 import ctypes
 import os
 import sys
@@ -24,9 +25,9 @@ L = capi.load()
 L.pies_exp_layer_stamps.argtypes = [ctypes.c_void_p]
 
 
-def timeline(rest_dict):
-    """one table; rest_dict False: PIES_LAYER_REST_DICT=0, the tetrahedra's rest constants streamed per element"""
-    capi.set_tuning("PIES_LAYER_REST_DICT", None if rest_dict else "0")
+def timeline(rows):
+    """one table; rows False: PIES_LAYER_TET_FORM=0, the tetrahedral projection as tet_core"""
+    capi.set_tuning("PIES_LAYER_TET_FORM", None if rows else "0")
     g = bench.build_scene(capi, scenes.L100K, 1234, schedule=capi.SCHEDULE_LAYERED, device=0)
     g.finalize()
     sets = g.count(capi.LAYER_REST_SETS)
@@ -38,8 +39,8 @@ def timeline(rest_dict):
     st = buf.cpu().numpy().reshape(SLOTS, TILES, NST)
     assert L.pies_exp_layer_stamps(None) == 0
     used = [s for s in range(SLOTS) if st[s, :, 1].any()]
-    print("== tetrahedral rest dictionary %s (%d sets): launch slots with stamps: %d; config 2 after %d ticks; 20 x 20 x 250 beam, LAYERED" % (
-        "ON" if rest_dict else "OFF (PIES_LAYER_REST_DICT=0)", sets, len(used), ticks))
+    print("== tetrahedral projection %s (rest dictionary: %d sets): launch slots with stamps: %d; config 2 after %d ticks; 20 x 20 x 250 beam, LAYERED" % (
+        "on row pairs (tet_rows.h)" if rows else "as tet_core (PIES_LAYER_TET_FORM=0)", sets, len(used), ticks))
     for s in used[:6] + used[-2:]:
         tiles = np.nonzero(st[s, :, 1])[0]
         rows = st[s, tiles]
