@@ -277,8 +277,13 @@ int upload_layer_tables(pies_solver* s) {
   std::vector<float4> restTable;
   layer_rest_dictionary(s, static_cast<size_t>(maxLds), &restIndex, &restTable);
   HIP_TRY(s, layer_prepare(L.maxGroupNodes, L.restSets));
-  if (L.restSets)
+  if (L.restSets) {  // the table, then the table once more with every row in the row-pair form's order (layer_rest.h)
+    const size_t n = restTable.size();
+    restTable.resize(2 * n);
+    for (uint32_t k = 0; k < L.restSets; ++k)
+      layer_rest_row_permute(reinterpret_cast<const float*>(&restTable[3 * k]), reinterpret_cast<float*>(&restTable[n + 3 * k]));
     if (int rc = upload(s, restTable, &d.restTable)) return rc;
+  }
   if (int rc = upload(s, L.nodeList, &d.nodeList)) return rc;
   if (int rc = dev_alloc(s, L.nodeList.size(), &d.lpos, true)) return rc;
   {

@@ -71,7 +71,7 @@ struct LayerData {
   const float2* dc_rw;
   const uint2* tc_lid;
   const float4 *tc_q0, *tc_q1, *tc_q2;
-  const float4* tc_rest;  // the rest dictionary (layer_rest.h): 3 float4 per set, tc_lid carries the set index; nullptr: tc_q0..2 per element
+  const float4* tc_rest;  // the rest dictionary (layer_rest.h): 3 float4 per set, then the same in pair order; tc_lid carries the set index; nullptr: tc_q0..2 per element
   uint32_t restSets;      // its sets (0 without)
   const uint2* bc_lid;
   const float2* bc_aw;

@@ -57,6 +57,7 @@ PIES_DEV uint32_t hi16(uint32_t v) { return v >> 16; }
 // same bits either way.  The 256-register instantiations have both (launch_layer: PIES_LAYER_TET_FORM); the 128-register ones keep tet_core.
 template <int BLOCK, int TETV, int WPE = 1, bool DICT = false, int FORM = 0>
 __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D, LayerLaunch L, LayerParams P) {
+  static_assert(FORM == 0 || TETV == 0, "the row-pair form is the full projection");
   static_assert(3 * kLayerRestMaxSets <= BLOCK, "the prologue requests the rest dictionary with one load per lane");
   constexpr int kDistPreload = (WPE > 1 || BLOCK > 512) ? 6 : kDistPreloadMax;
   constexpr int kDistAhead = 3;  // colours of a distance segment whose records are in flight
@@ -104,7 +105,8 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
     }
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) radReg[k] = needRadius ? D.lrad[lp(min(k * BLOCK + tid, m - 1))] : 0.0f;
-    if (DICT) tabReg = D.tc_rest[min(tid, tabLen - 1u)];  // (DICT: at least one set)
+    // (DICT: at least one set; the row-pair form takes the table's second copy, whose rows stand in pair order: layer_rest.h)
+    if (DICT) tabReg = D.tc_rest[(FORM == 1 ? tabLen : 0u) + min(tid, tabLen - 1u)];
   };
   // Node records in: from the level-ordered copy (the tile's two runs are contiguous: coalesced) or, with one strip, in
   // the first launch of a substep / after a collision pass, gathered from the node array.  Four requests per lane are in flight before
@@ -167,21 +169,29 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
   __syncthreads();
   PIES_STAMP();
 
-  // an element's tile-local node ids and, with the dictionary, its rest constants (LDS reads; a lattice's lanes mostly share a row)
+  // an element's tile-local node ids
   auto tet_ids = [&](const uint2& w, uint32_t& i1, uint32_t& i2, uint32_t& i3, uint32_t& i4) {
     if (DICT) { i1 = w.x & kLayerRestIdMask; i2 = (w.x >> 16) & kLayerRestIdMask; i3 = w.y & kLayerRestIdMask; i4 = (w.y >> 16) & kLayerRestIdMask; }
     else { i1 = lo16(w.x); i2 = hi16(w.x); i3 = lo16(w.y); i4 = hi16(w.y); }
   };
-  auto rest_ok = [&](const uint2& w) { return !DICT || PIES_IN_BOUNDS(layer_rest_set(w.x, w.y) < D.restSets, 14u); };
+  // DICT: the scene took the dictionary, so layer_rest_usable held: at most kLayerRestMaxSets = 64 sets, and the set index is the
+  // two 3-bit fields of the record's first word (layer_rest_set6); the fields of the second word are zero and are not read.
+  auto set_of = [&](const uint2& w) { return layer_rest_set6(w.x); };
+  auto rest_ok = [&](const uint2& w) { return !DICT || PIES_IN_BOUNDS(set_of(w) < D.restSets, 14u); };
   auto rest_read = [&](const uint2& w, float4& q0, float4& q1, float4& q2) {
-    const float4* __restrict__ row = stab + 3u * layer_rest_set(w.x, w.y);
+    const float4* __restrict__ row = stab + 3u * set_of(w);
     q0 = row[0]; q1 = row[1]; q2 = row[2];
   };
-  // one element's projection in the instantiation's form (FORM 1 with the dictionary reads the table's row as pairs itself)
+  // one element's projection in the instantiation's form.  FORM 1 with the dictionary reads the table's row itself: its words stand
+  // in LDS as that form pairs them (layer_rest.h), so every pair is two neighbouring words of a 128-bit read.
   auto project = [&](const uint2& w, float4& x1, float4& x2, float4& x3, float4& x4, float4& q0, float4& q1, float4& q2) {
     if (FORM == 1 && TETV == 0) {
-      if (DICT) rows::tet_rows(x1, x2, x3, x4, rows::rest_of(reinterpret_cast<const float*>(stab + 3u * layer_rest_set(w.x, w.y))));
-      else rows::tet_rows(x1, x2, x3, x4, rows::rest_of(q0, q1, q2));
+      if (DICT) {
+        const float4* __restrict__ row = stab + 3u * set_of(w);
+        rows::tet_rows(x1, x2, x3, x4, rows::rest_of_row(row[0], row[1], row[2]));
+      } else {
+        rows::tet_rows(x1, x2, x3, x4, rows::rest_of(q0, q1, q2));
+      }
     } else {
       if (DICT) rest_read(w, q0, q1, q2);
       tet_core<TETV>(x1, x2, x3, x4, q0, q1, q2);
@@ -212,13 +222,18 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
     } else if (kind == LAYER_TET) {
       // the record of the next colour is requested before this colour's SVD (unconditionally, from a clamped slot:
       // a conditional load would have to be waited for where the branches join)
+      // (with the dictionary the look-ahead is the 8 bytes of ids alone, and the constants are read from LDS together with the node
+      // records, nothing held across the projection: reading the next colour's before the barrier instead, 12 registers held,
+      // measured slower - 882 against 905 substeps/s on config 2, 876 streamed; held across the barrier only, 950 against 992.
+      // Decoding the next colour's record and requesting the one after it between this colour's stores and the barrier was
+      // measured as well, 976 against 994: the wavefronts that compute are the last to reach the barrier, so what stands in front
+      // of it is on their path, while behind it the decode fills the wait for the gather.  The colour offsets held as
+      // scalars (readfirstlane), with the loop for classes larger than the workgroup behind a scalar test, cost 5 instructions more
+      // per colour than these per-lane tests and measured 990 against 997.  DESIGN.md section 4.)
       const uint32_t last = off[ncol] > off[0] ? off[ncol] - 1 : 0;  // a valid slot (the segment is not empty)
       uint32_t lo = off[0], hi = off[1];
       bool have = lo + tid < hi;
       uint32_t t0 = min(lo + tid, last);
-      // (with the dictionary the look-ahead is the 8 bytes of ids alone, and the constants are read from LDS together with the node
-      // records, nothing held across the projection: reading the next colour's before the barrier instead, 12 registers held,
-      // measured slower - 882 against 905 substeps/s on config 2, 876 streamed)
       uint2 id = D.tc_lid[t0];
       float4 a0, a1, a2, b0, b1, b2;
       if (!DICT) { a0 = D.tc_q0[t0]; a1 = D.tc_q1[t0]; a2 = D.tc_q2[t0]; }

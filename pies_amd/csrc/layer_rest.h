@@ -27,10 +27,25 @@ PIES_REST_HD void layer_rest_pack(const uint32_t ids[4], uint32_t set, uint32_t 
 PIES_REST_HD uint32_t layer_rest_set(uint32_t x, uint32_t y) {
   return ((x >> 13) & 7u) | ((x >> 29) << 3) | (((y >> 13) & 7u) << 6) | ((y >> 29) << 9);
 }
+// The set index of a scene that takes the dictionary: layer_rest_usable refuses more than kLayerRestMaxSets = 64 sets, so only the
+// two 3-bit fields of the first word can be non-zero and the second word need not be read.  (set < 64; the format is unchanged.)
+PIES_REST_HD uint32_t layer_rest_set6(uint32_t x) { return ((x >> 13) & 7u) | ((x >> 29) << 3); }
 PIES_REST_HD void layer_rest_unpack(const uint32_t in[2], uint32_t ids[4], uint32_t* set) {
   ids[0] = in[0] & kLayerRestIdMask; ids[1] = (in[0] >> 16) & kLayerRestIdMask;
   ids[2] = in[1] & kLayerRestIdMask; ids[3] = (in[1] >> 16) & kLayerRestIdMask;
   *set = layer_rest_set(in[0], in[1]);
+}
+
+static_assert(kLayerRestMaxSets <= 64, "layer_rest_set6 reads six bits of the set index");
+
+// A table row in the order of the row-pair form.  A set is 12 floats r[0..11] = Qinv (9, as in tc_q0..2), min strain, max strain, w.  The
+// projection on row pairs (tet_rows.h) multiplies (r0, r3), (r1, r4), (r2, r5) as pairs; this order stores each pair side by
+// side so that it is one aligned two-word LDS read:  r0 r3 r1 r4 | r2 r5 r6 r7 | r8 r9 r10 r11.
+// (pies_finalize uploads the table twice, 3 float4 per set each time: plain, then in this order.  An instantiation of k_layer copies
+// the one it reads into LDS.  The per-element arrays tc_q0..2 keep their layout.)
+PIES_REST_HD void layer_rest_row_permute(const float plain[12], float row[12]) {
+  const uint32_t order[12] = {0, 3, 1, 4, 2, 5, 6, 7, 8, 9, 10, 11};  // order[k] = the plain row's word that stands at word k
+  for (int k = 0; k < 12; ++k) row[k] = plain[order[k]];
 }
 
 // LDS of a gfx950 workgroup (= of a compute unit): what a host-only handle, which has no device to ask, decides with

@@ -136,7 +136,7 @@ struct LayerDevice {
   uint32_t* pc_lid = nullptr;  // 1 x 16 bit in a word
   uint32_t* dc_lid = nullptr;  // a | b << 16
   uint2* tc_lid = nullptr;     // (n1 | n2 << 16, n3 | n4 << 16); with a rest dictionary 13-bit ids + the set index (layer_rest.h)
-  float4* restTable = nullptr;  // the rest dictionary: 3 float4 per set (Qinv, min strain, max strain, w), nullptr without
+  float4* restTable = nullptr;  // the rest dictionary: 3 float4 per set (Qinv, min strain, max strain, w), twice (plain, pair order: layer_rest.h), nullptr without
   uint2* bc_lid = nullptr;
 };
 

@@ -343,23 +343,34 @@ struct Rest {
 template <class V4> PIES_ROWS_FN Rest rest_of(const V4& a0, const V4& a1, const V4& a2) {
   return Rest{rp_make(a0.x, a0.w), rp_make(a0.y, a1.x), rp_make(a0.z, a1.y), a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
 }
-// the same record as 12 consecutive floats (a row of the rest dictionary in LDS: the pairs are two-word reads)
+// the same record as 12 consecutive floats
 PIES_ROWS_FN Rest rest_of(const float* __restrict__ r) {
   return Rest{rp_make(r[0], r[3]), rp_make(r[1], r[4]), rp_make(r[2], r[5]), r[6], r[7], r[8], r[9], r[10], r[11]};
+}
+// from a row of the rest dictionary as the device holds it (layer_rest.h: layer_rest_row_permute), read as three 4-word pieces:
+// every pair is two neighbouring words of a piece, so it arrives as a pair
+template <class V4> PIES_ROWS_FN Rest rest_of_row(const V4& r0, const V4& r1, const V4& r2) {
+  return Rest{rp_make(r0.x, r0.y), rp_make(r0.z, r0.w), rp_make(r1.x, r1.y), r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
 }
 
 // tet_core<0> on node records (any type with x, y, z): TetrahedralConstraint applied as a PBD projection
 template <class V4> PIES_ROWS_FN void tet_rows(V4& x1, V4& x2, V4& x3, V4& x4, const Rest& R, Paths* paths = nullptr) {
   // the edges P[j] = x_(j+2) - x1 by component; A[i] = (F[0][i], F[1][i], F[2][i]) with F[c][i] = P[0][i] q[c][0] + P[1][i] q[c][1] +
   // P[2][i] q[c][2] (mat3_mul_cm): column i of the matrix the reference hands to its SVD
-  const float e0[3] = {x2.x - x1.x, x3.x - x1.x, x4.x - x1.x};
-  const float e1[3] = {x2.y - x1.y, x3.y - x1.y, x4.y - x1.y};
+  // (the x, y of a record lie side by side: the x and y components of an edge are one pair subtraction, d[j] = (e0[j], e1[j]), and
+  // a product takes e0[j] / e1[j] as the pair's low / high half on both rows)
+  const rp p1 = rp_make(x1.x, x1.y), p2 = rp_make(x2.x, x2.y), p3 = rp_make(x3.x, x3.y), p4 = rp_make(x4.x, x4.y);
+  const rp d[3] = {rp_sub(p2, p1), rp_sub(p3, p1), rp_sub(p4, p1)};
+  const float e0[3] = {d[0].x, d[1].x, d[2].x};
+  const float e1[3] = {d[0].y, d[1].y, d[2].y};
   const float e2[3] = {x2.z - x1.z, x3.z - x1.z, x4.z - x1.z};
   Col A[3];
   A[0].p = rp_add(rp_add(rp_mul(rp_splat(e0[0]), R.q0), rp_mul(rp_splat(e0[1]), R.q1)), rp_mul(rp_splat(e0[2]), R.q2));
-  A[0].z = e0[0] * R.q20 + e0[1] * R.q21 + e0[2] * R.q22;
   A[1].p = rp_add(rp_add(rp_mul(rp_splat(e1[0]), R.q0), rp_mul(rp_splat(e1[1]), R.q1)), rp_mul(rp_splat(e1[2]), R.q2));
-  A[1].z = e1[0] * R.q20 + e1[1] * R.q21 + e1[2] * R.q22;
+  // (A[0].z, A[1].z) = e0[j], e1[j] against Qinv[2][j]: the edges' pairs as they are
+  const rp z01 = rp_add(rp_add(rp_mul(d[0], rp_splat(R.q20)), rp_mul(d[1], rp_splat(R.q21))), rp_mul(d[2], rp_splat(R.q22)));
+  A[0].z = z01.x;
+  A[1].z = z01.y;
   A[2].p = rp_add(rp_add(rp_mul(rp_splat(e2[0]), R.q0), rp_mul(rp_splat(e2[1]), R.q1)), rp_mul(rp_splat(e2[2]), R.q2));
   A[2].z = e2[0] * R.q20 + e2[1] * R.q21 + e2[2] * R.q22;
   // det3_cm(F), F[c][r] = row c of A[r]
@@ -387,7 +398,6 @@ PIES_ROWS_UNROLL
   // projected = (0, Fh row 0, Fh row 1, Fh row 2); pos += w * (proj - pos), x and y as a pair
   const float w = R.w;
   const rp w2 = rp_splat(w);
-  const rp p1 = rp_make(x1.x, x1.y), p2 = rp_make(x2.x, x2.y), p3 = rp_make(x3.x, x3.y), p4 = rp_make(x4.x, x4.y);
   const rp r1 = rp_add(p1, rp_mul(w2, rp_sub(rp_splat(0.0f), p1)));
   const rp r2 = rp_add(p2, rp_mul(w2, rp_sub(Fh[0].p, p2)));
   const rp r3 = rp_add(p3, rp_mul(w2, rp_sub(Fh[1].p, p3)));
