@@ -294,6 +294,24 @@ public:
     _refreshSkin(id);
     return id;
   }
+  // Extension (pies_raycast in pies_hip.h states the rule): the nearest hit of every ray on the scene's triangles (raycast; the
+  // triangle index counts the triangles in the order they were added) or on a skin's (raycastSkin; index local to the skin), at
+  // the positions the device holds now.  Directions are not normalised: t counts in units of |d|, position = o + t d; u and v
+  // are the weights of the triangle's second and third corner.  A ray without a hit within tMax has hit == false, t = +inf.
+  struct RayHit {
+    bool hit;
+    uint32_t triangle;
+    float t, u, v;
+    glm::vec3 position;
+  };
+  std::vector<RayHit> raycast(const std::vector<glm::vec3>& origins, const std::vector<glm::vec3>& directions, float tMax,
+                              bool cullBack = false) {
+    return _raycast(PIES_RAY_SCENE_TRIANGLES, 0, origins, directions, tMax, cullBack);
+  }
+  std::vector<RayHit> raycastSkin(uint32_t skin, const std::vector<glm::vec3>& origins, const std::vector<glm::vec3>& directions,
+                                  float tMax, bool cullBack = false) {
+    return _raycast(PIES_RAY_SKIN, skin, origins, directions, tMax, cullBack);
+  }
   void addFixedRegions(const std::vector<glm::mat4>& regionMatrices, float w) {
     std::vector<float> m = _flattenMats(regionMatrices);
     _ck(pies_add_fixed_regions(_handle(), static_cast<uint32_t>(regionMatrices.size()), m.data(), w));
@@ -426,6 +444,28 @@ private:
     _skinScratch.resize(6 * size_t(nv));
     _ck(pies_read_skin(_handle(), k, _skinScratch.data(), _skinScratch.data() + 3 * size_t(nv), nv));
     _copySkin(k, _skinScratch.data(), _skinScratch.data() + 3 * size_t(nv), nv);
+  }
+
+  std::vector<RayHit> _raycast(int target, uint32_t skin, const std::vector<glm::vec3>& origins, const std::vector<glm::vec3>& directions,
+                               float tMax, bool cullBack) {
+    if (origins.size() != directions.size()) throw std::runtime_error("Pies::Solver: raycast needs one direction per origin");
+    const uint32_t n = static_cast<uint32_t>(origins.size());
+    std::vector<float> o = _flatten(origins), d = _flatten(directions), t(n), uv(2 * size_t(n));
+    std::vector<uint32_t> tri(n);
+    _ck(pies_raycast(_handle(), target, skin, n, o.data(), d.data(), tMax, cullBack ? PIES_RAY_CULL_BACK : 0u, tri.data(), t.data(),
+                     uv.data()));
+    std::vector<RayHit> hits(n);
+    for (size_t i = 0; i < n; ++i) {
+      RayHit& h = hits[i];
+      h.hit = tri[i] != PIES_RAY_MISS;
+      h.triangle = tri[i];
+      h.t = t[i];
+      h.u = uv[2 * i];
+      h.v = uv[2 * i + 1];
+      const glm::vec3 &p = origins[i], &q = directions[i];
+      h.position = h.hit ? glm::vec3(p[0] + t[i] * q[0], p[1] + t[i] * q[1], p[2] + t[i] * q[2]) : p;
+    }
+    return hits;
   }
 
   // opens the device handle on first use

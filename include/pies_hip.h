@@ -373,6 +373,36 @@ int pies_export_release(pies_solver_t* s, uint64_t frame);
  * was begun is not part of it (PIES_ERR_STATE). */
 int pies_read_skin(pies_solver_t* s, uint32_t skin, float* positions, float* normals, uint32_t n);
 int pies_export_acquire_skin(pies_solver_t* s, uint64_t frame, uint32_t skin, const float** positions, const float** normals, uint32_t* n);
+/* EXTENSION (the reference draws nodes and has no ray query; its element grid _spatialHashTets was never finished): n_rays rays
+ * against the surface as the device holds it now - picking, grabbing, line-of-sight probes without a read-back.  origins and
+ * directions: n_rays x 3 floats each; directions are not normalised, t is measured in units of |d|.  The outputs may each be NULL:
+ * hit_triangle (n_rays), hit_t (n_rays), hit_uv (n_rays x 2: the weights of corners b and c at the hit).
+ * Targets.  PIES_RAY_SCENE_TRIANGLES: the PIES_TRIANGLES container, indexed in the order the host added the triangles, at the node
+ * positions the device holds (PBD and PD; under PIES_FLAG_RENUMBER_NODES the indices stay the host's).  PIES_RAY_SKIN: the
+ * triangles of skin `skin` (index local to that skin) at its current deformed vertices, evaluated on the same stream first; `skin`
+ * is ignored for the other target.
+ * The rule for one (ray, triangle) pair, ray (o, d), corners a, b, c, in fp32 without fused multiply-adds, every dot product
+ * summed left to right as x x + y y + z z, cross(p, q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z, p.x q.y - p.y q.x):
+ *   e1 = b - a, e2 = c - a, p = cross(d, e2), det = e1 . p;    miss unless |det| >= FLT_MIN (PIES_RAY_CULL_BACK: det >= FLT_MIN);
+ *   inv = 1 / det;                                             miss unless inv is finite;
+ *   s = o - a, u = (s . p) inv;                                miss unless u >= 0 && u <= 1;
+ *   q = cross(s, e1), v = (d . q) inv;                         miss unless v >= 0 && u + v <= 1;
+ *   t = (e2 . q) inv + 0.0f (a -0 becomes +0);                 miss unless t >= 0 && t <= t_max.
+ * Every test is the positive form written, so a NaN anywhere is a miss.  The hit of a ray is the pair with the smallest t, the
+ * lowest triangle index on equal t; without one hit_triangle = PIES_RAY_MISS, hit_t = +inf, hit_uv = (0, 0).  The winner is a
+ * minimum of 64-bit keys (bits of t, triangle) without atomics: every kernel variant and every split of the triangles gives the
+ * same bits, and two calls agree bit for bit.
+ * Runs on the handle's stream behind whatever ticks are queued and synchronises before it returns; node state, export frames,
+ * captured graphs and pies_launch_counts are left as they were; its buffers are allocated at the first call and freed by the
+ * next pies_finalize, pies_clear or pies_destroy.  Brute force over all triangles.
+ * PIES_ERR_INVALID: a NULL input array with n_rays > 0, an unknown target, a skin id out of range, a negative or NaN t_max (+inf
+ * is allowed).  PIES_ERR_UNSUPPORTED: more than 2^26 rays.  n_rays == 0 returns PIES_OK.  PIES_ERR_HIP: a PIES_DEVICE_NONE
+ * handle (the arguments are checked first).  A target without triangles gives all misses. */
+enum { PIES_RAY_SCENE_TRIANGLES = 0, PIES_RAY_SKIN = 1 };
+enum { PIES_RAY_CULL_BACK = 1 }; /* flags */
+#define PIES_RAY_MISS 0xFFFFFFFFu
+int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, const float* origins, const float* directions,
+                 float t_max, uint32_t flags, uint32_t* hit_triangle, float* hit_t, float* hit_uv);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:
@@ -412,7 +442,9 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * product, 4 residual; default 3) / _WINDOW_SORT / _WINDOW_HALO32 (tests: 32-bit halo list), PIES_CG_CHUNK_ROWS, PIES_PCG_NEVER_EXIT (profiling: every captured CG launch works),
  * PIES_REFERENCE_TURNS (0: the reference's node-node order as one sequential chain, 1: by turns whatever the size; default: by turns from
  * 1 024 nodes on), PIES_FALLBACK_VISITS (candidate tests a pass left to the sequential loop may cost before it latches: 1e9),
- * PIES_PAIR_QUADS (0: one lane per pair in the pair order's levels) / _QUAD_BLOCKS / _QUAD_THREADS / PIES_PAIR_LOOK_WAVES (wavefronts of a level workgroup that look at frontier nodes, at most).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
+ * PIES_PAIR_QUADS (0: one lane per pair in the pair order's levels) / _QUAD_BLOCKS / _QUAD_THREADS / PIES_PAIR_LOOK_WAVES (wavefronts of a level workgroup that look at frontier nodes, at most);
+ * pies_raycast, read at every call: PIES_RAY_VARIANT (wide: one ray per lane, narrow: one triangle per lane; unset: narrow up to
+ * PIES_RAY_NARROW_MAX rays, default 512: the measured crossover), PIES_RAY_CHUNKS (pins the triangle chunks of the wide variant, 1 .. 1 024).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
  * race with other API calls of the process (a handle reads the switches at different times of its life).  None of
  * them is read from the environment: the only environment variables the library looks at are PIES_SCHEDULE (default schedule
  * of new handles), PIES_PROFILER_SAFE (profiling runs) and the print-only PIES_PCG_DEBUG / PIES_LAYER_DEBUG. */

@@ -42,6 +42,9 @@ SKINS, SKIN_VERTICES = 21, 22  # pies_count: embedded surface meshes (pies_add_s
 LAYER_REST_SETS = 23  # pies_count: sets in the rest dictionary of schedule LAYERED's tetrahedral container (0: per-element arrays)
 LAYER_MAX_TILES = 24  # pies_count: tiles of the phase of schedule LAYERED's plan that has most (0: not active)
 LAYER_MAX_CLASS = 25  # pies_count: the largest colour class of any tile and container of schedule LAYERED's plan (0: not active)
+RAY_SCENE_TRIANGLES, RAY_SKIN = 0, 1  # pies_raycast targets
+RAY_CULL_BACK = 1  # pies_raycast flag
+RAY_MISS = 0xFFFFFFFF  # PIES_RAY_MISS
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -62,7 +65,7 @@ SYMBOLS = [
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
-    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume",
+    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -195,6 +198,7 @@ def load():
     sig["pies_export_acquire_skin"] = [vp, C.c_uint64, u32, C.POINTER(pf), C.POINTER(pf), pu]
     sig["pies_voxelize_tri_mesh"] = [vp, u32, pf, u32, pu, pf, f32, pu, pf, C.POINTER(C.c_uint8)]
     sig["pies_add_tri_mesh_volume"] = [vp, u32, pf, u32, pu, pf, f32, f32, f32, f32, f32, f32, f32, u32, pu, pu, pu, pu]
+    sig["pies_raycast"] = [vp, i32, u32, u32, pf, pf, f32, u32, pu, pf, pf]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -431,6 +435,19 @@ class Solver:
                                                   min_strain, max_strain, volume_stiffness, compression, stretching, resolution,
                                                   *[C.byref(x) for x in out]))
         return tuple(x.value for x in out)
+
+    def raycast(self, origins, directions, t_max=float("inf"), target=RAY_SCENE_TRIANGLES, skin=0, cull_back=False):
+        """pies_raycast: the nearest hit of every ray (origins, directions: n x 3; t in units of |d|) on the scene's triangles or
+        on skin `skin` (target=RAY_SKIN), at the positions the device holds now.  Returns (triangle uint32 (n), t float32 (n),
+        uv float32 (n, 2)); a miss is (RAY_MISS, +inf, (0, 0))."""
+        o, d = _f32(origins).reshape(-1, 3), _f32(directions).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("raycast: origins and directions differ in length")
+        n = len(o)
+        tri, t, uv = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty((n, 2), np.float32)
+        self._ck(self._L.pies_raycast(self._h, target, skin, n, _pf(o), _pf(d), t_max, RAY_CULL_BACK if cull_back else 0,
+                                      _pu(tri), _pf(t), _pf(uv)))
+        return tri, t, uv
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

@@ -35,6 +35,7 @@ struct RestSets {
 void free_device(pies_solver* s) {
   destroy_graph(s);
   skin_free_device(s);
+  ray_free_device(s);
   for (void* p : s->dev.allocations) (void)hipFree(p);
   s->dev = DeviceScene{};
 }

@@ -16,6 +16,7 @@
 #include "pd_contact_kernels.h"
 #include "pair_kernels.h"
 #include "skin_kernels.h"
+#include "ray_kernels.h"
 
 namespace pies {
 
@@ -177,6 +178,23 @@ struct NodeOrder {
   bool active() const { return !order.empty(); }
 };
 
+// Device buffers of pies_raycast.  free_device drops them, so the triangle list never outlives the scene or the node numbering
+// it was built from; every buffer grows on demand and a handle that never casts a ray holds none.
+struct RayBuffers {
+  std::vector<void*> allocations;
+  uint32_t* tri = nullptr;      // the scene's triangles, host order, node ids in DEVICE numbering
+  uint32_t nTris = 0;
+  bool triBuilt = false;
+  float4* records = nullptr;    // wide variant: (a, e1, e2) per triangle of the target last staged
+  size_t recordCap = 0;         // triangles
+  uint64_t* partial = nullptr;  // one key per (part, ray) of a batch
+  size_t partialCap = 0;        // keys
+  float* rays = nullptr;        // origins (3 n) then directions (3 n)
+  uint32_t* outTri = nullptr;   // results, n rays each
+  float *outT = nullptr, *outUv = nullptr;
+  size_t rayCap = 0;            // rays
+};
+
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
 // its place, so a field added here needs no line of its own there.  Buffers that outlive a finalize (the pinned stages, the export
 // buffers, the skins' records) and the adapted counts (pcgBudget, pairRounds, sortPasses, ncRounds) are members of pies_solver.
@@ -331,6 +349,8 @@ struct pies_solver {
   float* h_skinExport[2] = {nullptr, nullptr};  // pinned, per frame parity
   size_t skinExport_n = 0;           // vertices the three export buffers hold
   uint32_t frameSkinVerts[2] = {0, 0};  // skin vertices frame (parity) carries
+  // ---- ray casts (pies_raycast, raycast.cpp): built at the first call, freed with the scene's buffers (free_device) ----
+  pies::RayBuffers ray{};
   // ---- PD: a substep whose solve ends above the tolerance is run again with a larger CG budget (pies_tick) ----
   bool pcgRetry = true;
   uint32_t pcgRetries = 0;         // substeps run again since the handle was created
@@ -370,6 +390,8 @@ bool build_layer_plan(pies_solver* s);
 // skin.cpp : device records of the skins (no-ops without skins); skin_free_device forgets them (free_device, pies_clear)
 int skin_upload(pies_solver* s);
 void skin_free_device(pies_solver* s);
+// raycast.cpp : forgets the buffers of pies_raycast (free_device)
+void ray_free_device(pies_solver* s);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of
