@@ -1,5 +1,5 @@
 // Device-side helpers of the node grid shared by hash_kernels.hip (grid build, group-ordered and reference-ordered
-// resolve) and pair_kernels.hip (pair-ordered resolve).
+// resolve) and pair_lists.hip / pair_levels.hip / pair_turns.hip (resolve by dependency levels, through pair_device.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -47,7 +47,7 @@ struct HashArrays {
 // zero + range + prefix sum + emit + radix sort + cell index; returns the number of launches
 // sortPasses: radix passes captured for the entries' sort; a pass takes up to 11 key bits (grid_box, hash_device.h)
 // groups: group sizes and pass lists of the group order (k_grid_groups; also its "too many nodes in a cell" latch) - the pair order
-// over ranges of at most two cells looks at the buckets itself (k_pair_groups) and builds without it
+// over ranges of at most two cells looks at the buckets itself (k_pair_groups, pair_lists.hip) and builds without it
 uint32_t launch_hash_build(hipStream_t st, const HashArrays& H, const NodeArrays& nd, float gridSpacing, uint32_t sortPasses, bool groups = true);
 constexpr uint32_t kMaxBucket = 2048;  // nodes overlapping one cell beyond which the parallel orders hand the pass to the sequential loop (the
                                        // reference's PBD loop has no limit and no latch, Solver.cpp:81-130; until round 4 this was a failure)

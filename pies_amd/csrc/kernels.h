@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 
 namespace pies {
 
@@ -10,6 +11,13 @@ namespace pies {
 // pies_set_tuning (process wide, by name) - NOT read from the environment: a host's environment cannot alter a shipped solver.
 // Returns the value as a string, or nullptr when the switch is not set.  (capi.cpp)
 const char* tuning_env(const char* name);
+// a switch that holds a number: its value when it is set and lies in [lo, hi], else `fallback`
+inline uint32_t tuning_uint(const char* name, int lo, int hi, uint32_t fallback) {
+  const char* e = tuning_env(name);
+  if (!e) return fallback;
+  const int v = std::atoi(e);
+  return v >= lo && v <= hi ? static_cast<uint32_t>(v) : fallback;
+}
 
 struct NodeArrays {
   float4* pos;    // x, y, z, invMass

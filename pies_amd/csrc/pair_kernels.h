@@ -1,4 +1,6 @@
-// Launch wrappers of the pair-ordered node-node resolve (pair_kernels.hip).
+// The node-node resolve by dependency levels: the arrays and control words of a pass, its two launchers (pair_levels.hip: the
+// pair order; pair_turns.hip: the reference's order by turns) and the host steps both share (pair_lists.hip).  The device code
+// the three files share is pair_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +26,7 @@ constexpr uint32_t kPairSpilled = 11;    // groups the small list kernel passed 
 constexpr uint32_t kPairFallback = 13;   // the sequential loop runs this pass: by turns it could not be proved exact twice, or (either order) a pile
                                          // the lists do not hold (more than 1 024 partners of a node, more entries than reserved)
 constexpr uint32_t kPairFallbacks = 14;  // lifetime: passes the sequential loop had to run
-constexpr uint32_t kPairBarrier = 16;   // [16] counter and [17] abort word of the grid barrier of a repeated pass (k_pair_repeat)
+constexpr uint32_t kPairBarrier = 16;   // [16] counter and [17] abort word of the grid barrier of the launch that finishes a pass's levels (pair_device.h)
 constexpr uint32_t kPairWords = 32;
 
 constexpr uint32_t kPairLists = 64;     // the frontier is kept as this many sub-lists: a wavefront appends to one of them, so that the
@@ -60,7 +62,7 @@ struct PairArrays {
   uint32_t* ctl;
 };
 
-// One pass of Solver.cpp:85-130 in the pair order (DESIGN.md section 6): save, lists, start, `rounds` level launches, the tail
+// One pass of Solver.cpp:85-130 in the pair order (DESIGN.md section 7): save, lists, start, `rounds` level launches, the tail
 // that finishes whatever levels are left, and the (normally skipped) repeat with the widest slack.  Returns the launches.
 uint32_t launch_collide_pairs(hipStream_t st, const HashArrays& H, const PairArrays& P, const NodeArrays& nd, float gridSpacing, float friction,
                               float staticThreshold, uint32_t rounds);
@@ -68,8 +70,22 @@ uint32_t launch_collide_pairs(hipStream_t st, const HashArrays& H, const PairArr
 // One pass of Solver.cpp:85-130 in the REFERENCE's order - ascending node index, the node's range from its live position, buckets in
 // dx, dy, dz order, every overlapping visit resolved at once - executed by dependency levels of whole TURNS (a node's turn = all of
 // its visits): the turns whose members (the node and the partners within reach) have all had their earlier turns share no node,
-// so a level is one launch.  Same result as k_collide_reference's single chain, bit for bit (see pair_kernels.hip).
+// so a level is one launch.  Same result as k_collide_reference's single chain, bit for bit (see pair_turns.hip).
 uint32_t launch_collide_turns(hipStream_t st, const HashArrays& H, const PairArrays& P, const NodeArrays& nd, float gridSpacing, float friction,
                               float staticThreshold, uint32_t rounds);
+
+// ---- what the two launchers share (pair_lists.hip); each returns its launches ---------------------------------------------------
+// the state the pass starts from, every node's meetings with itself, the groups the list kernels work through
+uint32_t pass_begin(hipStream_t st, const HashArrays& H, const PairArrays& P, const NodeArrays& nd, float friction, float staticThreshold);
+// the lists of attempt `repeat` (1: the repeat, which returns at once unless the first attempt armed it)
+uint32_t pass_lists(hipStream_t st, const HashArrays& H, const PairArrays& P, float friction, float staticThreshold, uint32_t repeat);
+// behind the levels of attempt `repeat`: verification, the check that keeps the result or puts the saved state back; after the
+// first attempt the repeat is armed, after the second the sequential loop takes a pass that neither attempt could keep
+uint32_t pass_end(hipStream_t st, const HashArrays& H, const PairArrays& P, const NodeArrays& nd, float gridSpacing, float friction,
+                  float staticThreshold, uint32_t repeat);
+// Workgroups of `threads` threads of a kernel that the current device (the solver's) holds at once, halved so that a second solver
+// on the card leaves room: the size of a launch whose workgroups wait for each other at a grid barrier.  0: not known (the caller
+// uses one workgroup).  Computed once per kernel and device (a process may hold handles on several).
+uint32_t resident_blocks_halved(const void* kernel, int threads);
 
 }  // namespace pies

@@ -179,7 +179,7 @@ static int collision_order(const pies_solver* s) {
   if (order == PIES_COLLISION_ORDER_GROUPS && !s->collideFast) order = PIES_COLLISION_ORDER_REFERENCE;
   return order;
 }
-// The reference's order runs by dependency levels of turns (pair_kernels.hip: launch_collide_turns) from 1 024 nodes on; below that -
+// The reference's order runs by dependency levels of turns (pair_turns.hip: launch_collide_turns) from 1 024 nodes on; below that -
 // and with PIES_REFERENCE_TURNS=0 - as the single chain of k_collide_reference, which is also the turns' fallback.
 static bool reference_by_turns(const pies_solver* s) {
   if (const char* e = tuning_env("PIES_REFERENCE_TURNS")) return e[0] != '0' && s->dev.pairs.turnCnt != nullptr;

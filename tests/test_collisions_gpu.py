@@ -417,6 +417,51 @@ def test_pair_level_variants_agree(pies, monkeypatch, tune):
         assert np.array_equal(ref[0], alt[0]) and np.array_equal(ref[1], alt[1]) and ref[2] == alt[2], var
 
 
+@pytest.mark.parametrize("shape, jitter, least_pairs", [((6, 7, 8), 0.05, 0), ((12, 10, 14), 0.08, 1000)], ids=["336-nodes", "1680-nodes"])
+def test_turn_level_variants_agree(pies, oracle, tune, shape, jitter, least_pairs):
+    """(reference order by turns) The levels behind the captured launches exist in several shapes - resident workgroups behind a
+    grid barrier (many, or one), the single workgroup of k_turn_tail, every level behind the barrier, two captured levels and the
+    rest in one launch.  They run the same turns in the same order of conflicting turns: identical results, bit for bit, and the
+    oracle's plain loop's.  336 nodes: a frontier smaller than one workgroup's wavefronts; 1 680 jittered nodes: partners spread
+    over several levels and sub-lists.  No variant may pass by handing the pass to the sequential loop."""
+    p, v = particles(shape, jitter=jitter)
+
+    def build(s):
+        s.addNodes(p)
+        s.set_velocities(v)
+
+    def run(rounds=None):
+        pies.set_tuning("PIES_REFERENCE_TURNS", "1")
+        try:
+            g = pies.Solver(scenes.pbd_options(pies, 3))
+            build(g)
+            g.set_flag(pies.FLAG_COLLISION_ORDER, 0)
+            if rounds is not None:
+                g.set_collision_rounds(rounds)
+            g.tick(2)
+        finally:
+            pies.set_tuning("PIES_REFERENCE_TURNS", None)
+        assert not g.failed and g.collision_fallbacks == 0
+        return g
+    g = run()
+    o = oracle.OracleSolver(scenes.pbd_options(oracle, 3))
+    build(o)
+    o.set_flag(oracle.FLAG_COLLISION_RULE, 0)
+    o.tick(2)
+    check(g, o)
+    ref = g.positions, g.velocities, g.collision_pairs  # (the count is read once: reading it starts it over)
+    assert ref[2] == o.collision_pairs > least_pairs
+    for var in [{"PIES_TURN_LEVEL_LAUNCHES": "0"}, {"PIES_TURN_FINISH_BLOCKS": "1"}, {"PIES_TURN_FINISH_BLOCKS": "0"}, {"rounds": 2}]:
+        for name, value in var.items():
+            if name != "rounds":
+                tune(name, value)
+        a = run(var.get("rounds"))
+        for name in var:
+            if name != "rounds":
+                tune(name, None)
+        assert np.array_equal(ref[0], a.positions) and np.array_equal(ref[1], a.velocities) and ref[2] == a.collision_pairs, var
+
+
 @RULES
 def test_distant_clusters_use_wide_keys(pies, oracle, rule):
     """The sort key packs the cell coordinates relative to the bounding box of all ranges: two clusters 300 000 apart on
