@@ -617,15 +617,15 @@ int pies_get_tri_grid_stats(pies_solver_t* s, uint32_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0;
   if (s->device == PIES_DEVICE_NONE || !s->dev.pd.tri.counters) return PIES_OK;
   HIP_TRY(s, hipSetDevice(s->device));
-  uint32_t c[16];
+  uint32_t c[kTriCounterWords];
   HIP_TRY(s, hipMemcpyAsync(c, s->dev.pd.tri.counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   uint32_t lists[64 * 16];
   HIP_TRY(s, hipMemcpyAsync(lists, s->dev.pd.tri.workCnt, sizeof(lists), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   for (int i = 0; i < 64; ++i) out[0] += lists[16 * i];
-  out[1] = c[9];
-  for (int k = 0; k < 3; ++k) { out[2 + k] = c[10 + k]; out[5 + k] = c[13 + k]; }
+  out[1] = c[kTriCtrHitRecords];
+  for (int k = 0; k < 3; ++k) { out[2 + k] = c[kTriCtrLongest + k]; out[5 + k] = c[kTriCtrListed + k]; }
   return PIES_OK;
 }
 
@@ -635,7 +635,7 @@ int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, ui
   if (s->device == PIES_DEVICE_NONE || !s->dev.pd.tri.counters) return PIES_OK;
   HIP_TRY(s, hipSetDevice(s->device));
   uint32_t m = 0;
-  HIP_TRY(s, hipMemcpyAsync(&m, s->dev.pd.tri.counters + 2, sizeof(m), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&m, s->dev.pd.tri.counters + kTriCtrContacts, sizeof(m), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   *count = m;
   if (ids && m) {

@@ -1,5 +1,5 @@
 // Exact-key open-addressing cell table shared by the node grid (hash_kernels.hip) and the triangle grid
-// (tri_kernels.hip): a cell id (three signed 21-bit coordinates) is packed into 63 bits and compared in
+// (tri_lists.hip): a cell id (three signed 21-bit coordinates) is packed into 63 bits and compared in
 // full, so two different cells never alias -- the reference's hash map is exact as well.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "dev_math.h"
+#include "floor_friction.h"
 #include "hash_device.h"
 #include "pd_contact_kernels.h"
 
@@ -225,14 +226,7 @@ __global__ void __launch_bounds__(kNcBlock) k_nc_floor_friction(NodeContactArray
   if (ns == 0u) return;
   const float4 v = vel[i];
   float vx = v.x, vy = v.y, vz = v.z;
-  for (uint32_t c = 0; c < ns; ++c) {  // (k_pd_velocity's loop)
-    const float px = vx, pz = vz;
-    float fr = friction;
-    if (sqrtf(px * px + 0.0f * 0.0f + pz * pz) < staticThreshold) fr = 1.0f;
-    vx += -fr * px;
-    vy += -fr * 0.0f;
-    vz += -fr * pz;
-  }
+  floor_friction(vx, vy, vz, ns, friction, staticThreshold);
   vel[i] = make_float4(vx, vy, vz, v.w);
 }
 

@@ -23,6 +23,8 @@
 #include "pd_kernels.h"
 #include "pd_cg_device.h"
 #include "pd_rhs_device.h"
+#include "floor_friction.h"
+#include "tri_device.h"
 
 namespace pies {
 
@@ -153,14 +155,7 @@ __global__ void __launch_bounds__(kBlock) k_pd_node_pair_floor_friction(const ui
   if (ns == 0u) return;
   const float4 v = vel[i];
   float vx = v.x, vy = v.y, vz = v.z;
-  for (uint32_t c = 0; c < ns; ++c) {  // (k_pd_velocity's loop)
-    const float px = vx, pz = vz;
-    float fr = friction;
-    if (sqrtf(px * px + 0.0f * 0.0f + pz * pz) < staticThreshold) fr = 1.0f;
-    vx += -fr * px;
-    vy += -fr * 0.0f;
-    vz += -fr * pz;
-  }
+  floor_friction(vx, vy, vz, ns, friction, staticThreshold);
   vel[i] = make_float4(vx, vy, vz, v.w);
 }
 
@@ -297,44 +292,7 @@ PIES_DEV void local_tet_pair(const float4* __restrict__ pos, const uint4* __rest
 }
 // (Asking for 5 wavefronts per SIMD - 77 VGPRs instead of 108, no spill - measured the same on one box: 26.0 / 186 us
 // against 26.1 / 192 us at 100k / 5.8M element pairs.)
-// Local step of the point-triangle contacts (CollisionConstraint.cpp:86-124) and w * (AtA p)_i (:176-194): the body of
-// tri_kernels.hip's k_pd_local_tri (same IEEE sequence), run by a few extra workgroups of the fused strain + volume launch
-// so that a substep without contacts does not pay a launch boundary per local/global iteration for it.
-template <uint32_t BLOCK> PIES_DEV void local_tri_contacts(const TriArrays& T, const float4* __restrict__ pos, float thickness, uint32_t block, uint32_t nblocks) {
-  const uint32_t M = T.counters[2];
-  for (uint32_t c = block * BLOCK + threadIdx.x; c < M; c += nblocks * BLOCK) {
-    const uint4 id = T.ids[c];
-    const float4 q[4] = {pos[id.x], pos[id.y], pos[id.z], pos[id.w]};
-    float p[4][3] = {{q[0].x, q[0].y, q[0].z}, {q[1].x, q[1].y, q[1].z}, {q[2].x, q[2].y, q[2].z}, {q[3].x, q[3].y, q[3].z}};
-    const float rel[3] = {p[0][0] - p[1][0], p[0][1] - p[1][1], p[0][2] - p[1][2]};
-    const float a[3] = {p[2][0] - p[1][0], p[2][1] - p[1][1], p[2][2] - p[1][2]};
-    const float b[3] = {p[3][0] - p[1][0], p[3][1] - p[1][1], p[3][2] - p[1][2]};
-    const float cr[3] = {a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]};
-    const float inv = 1.0f / sqrtf(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
-    const float n[3] = {cr[0] * inv, cr[1] * inv, cr[2] * inv};
-    const float nDotP = n[0] * rel[0] + n[1] * rel[1] + n[2] * rel[2];
-    if (nDotP < thickness) {
-      const float d = thickness - nDotP;
-      p[0][0] = p[0][0] + d * n[0];
-      p[0][1] = p[0][1] + d * n[1];
-      p[0][2] = p[0][2] + d * n[2];
-    }
-    // AtA = [[3,-1,-1,-1],[-1,1,0,0],[-1,0,1,0],[-1,0,0,1]], products accumulated from 0 in column order
-    const float AtA[4][4] = {{3.f, -1.f, -1.f, -1.f}, {-1.f, 1.f, 0.f, 0.f}, {-1.f, 0.f, 1.f, 0.f}, {-1.f, 0.f, 0.f, 1.f}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float ax = 0.f, ay = 0.f, az = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        ax += AtA[i][k] * p[k][0];
-        ay += AtA[i][k] * p[k][1];
-        az += AtA[i][k] * p[k][2];
-      }
-      T.contrib[4 * c + i] = make_float4(kTriContactW * ax, kTriContactW * ay, kTriContactW * az, 0.f);
-    }
-  }
-}
-constexpr uint32_t kTriLocalBlocks = 64;  // extra workgroups of the fused launch that sweep the contact list
+constexpr uint32_t kTriLocalBlocks = 64;  // extra workgroups of the fused launch that sweep the contact list (tri_local_contacts)
 }  // namespace pies
 #include "pd_local_packed.h"
 namespace pies {
@@ -347,7 +305,7 @@ __global__ void __launch_bounds__(kBlock) k_pd_local_tet_pair(const float4* __re
                                                               RestDictionary dict, Vec3f* __restrict__ contribTet, uint32_t count, TriArrays T,
                                                               float thickness, uint32_t tetBlocks) {
   if (blockIdx.x >= tetBlocks) {  // uniform per workgroup
-    local_tri_contacts<kBlock>(T, pos, thickness, blockIdx.x - tetBlocks, kTriLocalBlocks);
+    tri_local_contacts(T, pos, thickness, (blockIdx.x - tetBlocks) * kBlock + threadIdx.x, kTriLocalBlocks * kBlock);
     return;
   }
   if (PACKED) {
@@ -374,7 +332,7 @@ template <bool DICT>
 __global__ void __launch_bounds__(kTileLanes) k_pd_local_tiles(PdTileArrays T, const float4* __restrict__ pos, const float4* __restrict__ dictTable,
                                                                TriArrays tri, float thickness, uint32_t tileBlocks) {
   if (blockIdx.x >= tileBlocks) {  // uniform per workgroup
-    local_tri_contacts<kTileLanes>(tri, pos, thickness, blockIdx.x - tileBlocks, gridDim.x - tileBlocks);
+    tri_local_contacts(tri, pos, thickness, (blockIdx.x - tileBlocks) * kTileLanes + threadIdx.x, (gridDim.x - tileBlocks) * kTileLanes);
     return;
   }
   __shared__ float4 sPos[kTileNodes];
@@ -648,15 +606,7 @@ __global__ void __launch_bounds__(kBlock) k_pd_velocity(const float4* __restrict
   float vx = (k * (p.x - q.x)) / h + (h * fx) * p.w;
   float vy = (k * (p.y - q.y)) / h + (h * fy) * p.w;
   float vz = (k * (p.z - q.z)) / h + (h * fz) * p.w;
-  const uint32_t ns = staticFriction ? nstatic[i] : 0u;
-  for (uint32_t c = 0; c < ns; ++c) {
-    const float px = vx, pz = vz;  // perpVel = (vx, 0, vz)
-    float fr = friction;
-    if (sqrtf(px * px + 0.0f * 0.0f + pz * pz) < staticThreshold) fr = 1.0f;
-    vx += -fr * px;
-    vy += -fr * 0.0f;
-    vz += -fr * pz;
-  }
+  floor_friction(vx, vy, vz, staticFriction ? nstatic[i] : 0u, friction, staticThreshold);
   prev[i] = make_float4(p.x, p.y, p.z, 0.f);
   vel[i] = make_float4(vx, vy, vz, 0.f);
 }

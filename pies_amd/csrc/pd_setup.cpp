@@ -605,7 +605,7 @@ int pd_build(pies_solver* s) {
     if (int rc = dev_alloc(s, nt, &T.posIn, true)) return rc;
     if (int rc = dev_alloc(s, 4ull * nt, &T.ent, true)) return rc;
     if (int rc = dev_alloc(s, 4ull * nt, &T.boxOf, true)) return rc;
-    if (int rc = dev_alloc(s, 16, &T.counters, true)) return rc;
+    if (int rc = dev_alloc(s, kTriCounterWords, &T.counters, true)) return rc;
     if (int rc = dev_alloc(s, nt, &T.rng, true)) return rc;
     if (int rc = dev_alloc(s, nt, &T.head, true)) return rc;
     if (int rc = dev_alloc(s, T.maxContacts, &T.pool, true)) return rc;
@@ -637,7 +637,7 @@ int pd_build(pies_solver* s) {
     if (int rc = dev_alloc(s, 6ull * T.maxContacts, &T.rowCoef, true)) return rc;
     if (int rc = dev_alloc(s, T.maxContacts, &T.lvSlots, true)) return rc;
     cg.tIncCnt = T.incCnt; cg.tIncStart = T.incStart; cg.tInc = T.incSorted; cg.tIds = T.ids;
-    cg.tUsed = T.usedNodes; cg.tUsedCount = T.counters + 4;
+    cg.tUsed = T.usedNodes; cg.tUsedCount = T.counters + kTriCtrUsedNodes;
     cg.rowStart = T.rowStart; cg.rowLen = T.rowLen; cg.rowCol = T.rowCol; cg.rowCoef = T.rowCoef;
     if (int rc = dev_alloc(s, n, &cg.cAp, true)) return rc;
     if (const char* e = tuning_env("PIES_TRI_FAST_ROWS")) s->triFastRows = std::atoi(e) != 0;  // tests: force a variant from the first tick

@@ -366,8 +366,8 @@ static void pd_detect_triangles(Bracket& b) {
   const PdArrays& pd = s->dev.pd;
   s->triLevelsForked = tri_levels_forked(s);
   const bool levelsInLine = !s->triLevelsForked && pd.cg.useCAp == 0;  // the contact-light variant computes them with the list
-  launch_tri_detect(st, pd.tri, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, s->opt.collisionThickness,
-                    pd.cg.useCAp != 0, levelsInLine);
+  launch_tri_detect(st, pd.tri, s->dev.nd, pd.kdiag, pd.cg.cdiag, pd.cg.dinv, s->opt.collisionThresholdDistance, pd.cg.useCAp != 0,
+                    levelsInLine);
   // The dependency levels of the list (one workgroup, up to 1 ms with tens of thousands of contacts) are only needed by
   // the sequential passes behind the local/global iterations: a second branch of the substep, joined there.
   // Only in the contact-heavy graph variant: a fork and join inside a hipGraph costs about 100 us per replay (measured:
@@ -679,7 +679,7 @@ int adapt_pcg_budget(pies_solver* s) {
   if (s->dev.pd.tri.nt && s->dev.pd.tri.counters) {
     const int force = [] { const char* e = tuning_env("PIES_TRI_FAST_ROWS"); return e ? std::atoi(e) : -1; }();
     uint32_t contacts = 0;
-    HIP_TRY(s, hipMemcpyAsync(&contacts, s->dev.pd.tri.counters + 2, sizeof(contacts), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&contacts, s->dev.pd.tri.counters + kTriCtrContacts, sizeof(contacts), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     if (contacts >= 512) { fastRows = true; s->triQuiet = 0; }
     else if (contacts == 0 && fastRows && ++s->triQuiet >= 120) { fastRows = false; s->triQuiet = 0; }
@@ -756,14 +756,14 @@ int adapt_nc_rounds(pies_solver* s) {
 }
 
 int poll_failure(pies_solver* s) {
-  uint32_t* flagWord = s->dev.hash.counters ? s->dev.hash.counters + 3 : s->dev.pd.tri.counters ? s->dev.pd.tri.counters + 3 : nullptr;
+  uint32_t* flagWord = s->dev.hash.counters ? s->dev.hash.counters + 3 : s->dev.pd.tri.counters ? s->dev.pd.tri.counters + kTriCtrFailure : nullptr;
   if (s->simFailed || !flagWord || s->device == PIES_DEVICE_NONE) return PIES_OK;
   uint32_t flag = 0;
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipMemcpyAsync(&flag, flagWord, sizeof(flag), hipMemcpyDeviceToHost, s->stream));
   if (s->dev.ncActive && s->dev.pd.tri.counters) {  // PD with node-node contacts: the point-triangle pipeline's word as well
     uint32_t triFlag = 0;
-    HIP_TRY(s, hipMemcpyAsync(&triFlag, s->dev.pd.tri.counters + 3, sizeof(triFlag), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&triFlag, s->dev.pd.tri.counters + kTriCtrFailure, sizeof(triFlag), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     flag |= triFlag;
   }
@@ -777,9 +777,9 @@ int poll_failure(pies_solver* s) {
     }
     s->error = flag & 2    ? "node-node collision grid overflow (more cells or entries than reserved)"
                : flag & 4  ? "runaway pile-up: a node-node pass that only the sequential loop can run (more than 1024 nodes within reach of one node, or more than 2048 in a cell under the group order) would cost more candidate tests than PIES_FALLBACK_VISITS allows (1e9: about a minute)"
-               : flag & 16 ? "more than 1000 triangles in one grid cell, or more than 1000 cells in a triangle's search range (the reference's safety latches, Solver.cpp:741-755)"
-               : flag & 32 ? "a triangle's swept bounding box is non-finite"
-               : flag & 64 ? "point-triangle contact list overflow"
+               : flag & kTriFailBucket ? "more than 1000 triangles in one grid cell, or more than 1000 cells in a triangle's search range (the reference's safety latches, Solver.cpp:741-755)"
+               : flag & kTriFailNonFinite ? "a triangle's swept bounding box is non-finite"
+               : flag & kTriFailOverflow ? "point-triangle contact list overflow"
                : flag & 8  ? "node-node collision pass: the wait for a neighbouring group timed out (PIES_COLLIDE_SPIN_LIMIT)"
                : flag & 128 ? "node-node collision grid: more cell entries than the build reserves (sized from the radii at finalize)"
                : flag & 256 ? "node-node collision pass: more than 512 nodes within reach of one node, or more pairs than reserved (runaway pile-up)"

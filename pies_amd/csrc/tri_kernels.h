@@ -46,10 +46,10 @@ struct TriArrays {
   float4* ent;         // 4 per listed triangle, slot by slot: {box min of its six corner positions, bits(triangle)}, {box max, regular ? 1 : 0},
                        // {bits: min cell, packed lengths}, {bits: node ids} - all a searching triangle needs of a partner, in one line
   float4* boxOf;       // the same four records per triangle (k_tri_box), copied into ent once the slots have their storage
-  uint32_t* counters;  // [0] [1] - [2] contacts [3] failure flag [4] nodes with contacts [5] incidences
-                       // [8] merged row entries [6] dependency levels of the contact list [7] form of the sequential passes: 0 on an LDS copy of the
-                       // touched nodes, 2 through L2, 1 more than kTriMaxLevels levels (single-wavefront walk)
-                       // [9] hit records [10..12] longest range (in cells of the class) listed per class [13..15] triangles per class
+  uint32_t* counters;  // kTriCounterWords words, indexed by TriCounter (below): [0] [1] - [2] contacts [3] failure bits (sticky)
+                       // [4] nodes with contacts [5] incidences [6] dependency levels of the contact list [7] form of the sequential
+                       // passes (TriPassForm) [8] merged row entries [9] hit records [10..12] longest range (in cells of the class)
+                       // listed per class [13..15] triangles per class
   int4* rng;           // per triangle: min cell, packed lengths
   uint2* work;         // pairs left for the CCD: {triangle, partner | corners to test << 29}, in 64 lists of maxWork / 64
   uint32_t maxWork;
@@ -80,12 +80,25 @@ struct TriArrays {
 constexpr uint32_t kTriNil = 0xffffffffu;
 constexpr uint32_t kWorkShards = 64;   // lists of the CCD's work list (k_tri_pairs)
 constexpr uint32_t kGridTile = 2048;   // slots per tile of the prefix sum over the slots (256 threads x 8)
+enum TriCounter : uint32_t {  // the words of TriArrays::counters (kTriCtrLongest, kTriCtrListed: + size class)
+  kTriCtrContacts = 2, kTriCtrFailure = 3, kTriCtrUsedNodes = 4, kTriCtrIncidences = 5, kTriCtrLevels = 6, kTriCtrPassForm = 7,
+  kTriCtrRowEntries = 8, kTriCtrHitRecords = 9, kTriCtrLongest = 10, kTriCtrListed = 13, kTriCounterWords = 16
+};
+// bits of counters[kTriCtrFailure] (1 .. 8 and 128 .. belong to the node grid's word, hash_kernels.h; the host reads both as one)
+constexpr uint32_t kTriFailBucket = 16;     // the reference's bucket latches (Solver.cpp:741-745, 751-755)
+constexpr uint32_t kTriFailNonFinite = 32;  // a triangle with a non-finite or far-away corner
+constexpr uint32_t kTriFailOverflow = 64;   // more pairs, hit records or contacts than reserved
+enum TriPassForm : uint32_t {  // counters[kTriCtrPassForm], set with the dependency levels
+  kTriPassLds = 0,   // level by level on an LDS copy of the touched nodes
+  kTriPassWalk = 1,  // more than kTriMaxLevels levels: one wavefront walks the list, 64 contacts at a time
+  kTriPassL2 = 2     // level by level through L2
+};
 // Before the grid is built (rides in the substep's first launch, k_pd_predict: one launch less): the slots the last substep listed triangles in, the tile sums and the substep's counters back to zero
-// ([0] and [4]-[8] are zeroed by k_tri_box, which runs before their first use: this kernel's own workgroups still read [4]),
-// the per-node incidence counts of the last substep's contacts.
+// ([0] and used nodes .. row entries are zeroed by k_tri_box, which runs before their first use: this kernel's own workgroups still
+// read the used nodes), the per-node incidence counts of the last substep's contacts.
 __device__ __forceinline__ void tri_reset(const TriArrays& T, uint32_t tid, uint32_t stride) {
-  const uint32_t usedNodes = T.counters[4];
-  if (tid < 16u && (tid == 1u || tid == 2u || tid >= 9u)) T.counters[tid] = 0;  // ([3] is the sticky failure flag)
+  const uint32_t usedNodes = T.counters[kTriCtrUsedNodes];
+  if (tid < kTriCounterWords && (tid == 1u || tid == kTriCtrContacts || tid >= kTriCtrHitRecords)) T.counters[tid] = 0;  // (the failure bits are sticky)
   for (uint32_t b = tid; b < T.slots / kGridTile; b += stride) T.tileSum[b] = 0;
   if (tid < kWorkShards) T.workCnt[16u * tid] = 0;
   for (uint32_t t = tid; t < T.nt; t += stride) {
@@ -103,11 +116,14 @@ constexpr uint32_t kTriMaxLevels = 2048;  // longer chains (one node in thousand
 
 struct PdArrays;
 
-// after the predict kernel: grid build, detection (pairs + hit records, scan, contact list), per-node incidence + diagonal; returns launches
+// after the predict kernel: grid build and detection (pairs + hit records; tri_detect.hip), then its second half, launch_tri_lists
+// (tri_lists.hip): scan, contact list, per-node incidence + diagonal
 // (levelsInLine, contact-light variant only: the dependency levels of the list are computed by the same launch as the list -
 // launch_tri_levels must not be called for that substep)
-uint32_t launch_tri_detect(hipStream_t st, const TriArrays& T, const NodeArrays& nd, const float* kdiag, float* cdiag, float* dinv,
-                           float threshold, float thickness, bool mergedRows, bool levelsInLine);
+void launch_tri_detect(hipStream_t st, const TriArrays& T, const NodeArrays& nd, const float* kdiag, float* cdiag, float* dinv, float threshold,
+                       bool mergedRows, bool levelsInLine);
+void launch_tri_lists(hipStream_t st, const TriArrays& T, const NodeArrays& nd, const float* kdiag, float* cdiag, float* dinv, bool mergedRows,
+                      bool levelsInLine);
 // dependency levels of the contact list for the sequential passes (may run on another stream beside the local/global iterations)
 void launch_tri_levels(hipStream_t st, const TriArrays& T);
 void launch_pd_local_tri(hipStream_t st, const TriArrays& T, const float4* pos, float thickness);

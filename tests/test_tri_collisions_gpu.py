@@ -239,6 +239,63 @@ def test_thousands_of_contacts_level_schedule(pies, oracle, monkeypatch, contact
     assert most > 1024 and not g.failed
 
 
+def _chain_depth(contacts):
+    """level(c) = 1 + the highest level of an earlier contact of the list that shares a node with c; returns the highest level"""
+    last, depth = {}, 0
+    for c in contacts:
+        lv = 1 + max(last.get(int(n), 0) for n in c)
+        for n in c:
+            last[int(n)] = lv
+        depth = max(depth, lv)
+    return depth
+
+
+def test_chain_deeper_than_the_level_cap_takes_the_walk(pies, oracle, tune):
+    """700 small triangles hovering over one large one: 2 000+ contacts name the large triangle, so the list's dependency chain
+    is deeper than kTriMaxLevels and the sequential passes take the single-wavefront walk, 64 contacts at a time.  The touched
+    nodes fit the LDS copy and the list the node-owner levels, so the default run reaches the walk through the node-owner
+    path's `stuck` exit and PIES_TRI_LDS=0 through the overflow of the chunked relaxation.  One tick from rest (the second
+    tick has 92 contacts in 5 levels): list equal to the oracle's, state held by the yardstick, the two runs equal bit for bit."""
+    rng = np.random.default_rng(7)
+    big = np.float32([[0.1, 5.0, 0.1], [0.1, 5.01, 3.9], [3.9, 5.0, 0.1]])
+    u = rng.uniform(0.05, 0.9, (2800, 2)); u = u[u.sum(1) < 0.9][:700]
+    base = big[0] + u[:, :1] * (big[1] - big[0]) + u[:, 1:] * (big[2] - big[0]); base[:, 1] += 0.05
+    c = np.repeat(base, 3, axis=0).reshape(700, 3, 3)
+    c[:, 1] += [0.03, 0, 0]; c[:, 2] += [0, 0, 0.03]; c[:, :, 1] += rng.uniform(0.0, 0.02, (700, 3))
+    nodes = np.concatenate([big, c.reshape(-1, 3)]).astype(np.float32)
+    tris = np.arange(len(nodes), dtype=np.uint32).reshape(-1, 3)
+
+    def build(s):
+        s.addNodes(nodes)
+        s.add_triangles(tris)
+        s.set_prev_positions(s.positions)
+    o = oracle.OracleSolver(pd_options(oracle, 3))
+    o64 = oracle.OracleSolver(pd_options(oracle, 3))
+    o64.set_flag(oracle.FLAG_PD_SOLVE_FP64, 1)
+    for s in (o, o64):
+        build(s)
+        s.tick()
+    assert not o.failed and np.array_equal(o64.tri_collisions, o.tri_collisions)
+    co = o.tri_collisions
+    depth = _chain_depth(co)
+    assert depth > 2048, "the list's chain (%d levels) no longer exceeds kTriMaxLevels = 2048: the walk is not reached" % depth
+    assert len(np.unique(co)) <= 4096 and len(co) <= 65536  # the node-owner path takes the list (and leaves by `stuck`)
+    states = []
+    for lds in ("1", "0"):
+        tune("PIES_TRI_LDS", lds)
+        g = pies.Solver(pd_options(pies, 3))
+        g.set_pcg(3e-7, 256)
+        build(g)
+        g.tick()
+        assert np.array_equal(g.tri_collisions, co), (lds, len(g.tri_collisions), len(co))
+        yardstick("chain_deeper_than_the_level_cap[lds=%s]" % lds, g, o, o64, names=("positions", "velocities"))
+        assert not g.failed
+        states.append((g.positions.copy(), g.velocities.copy(), g.prev_positions.copy()))
+        g.close()
+    for a, b in zip(*states):
+        assert np.array_equal(a, b)
+
+
 def test_config5_l250k_with_binding_contacts(pies, oracle):
     """BASELINE config 5, one GPU's share: a 250 000-particle body (25x25x400 lattice beam, strain + volume constraints,
     PD, 10 local/global iterations) with the point-triangle pipeline on AND binding: the beam lies on the floor (floor
