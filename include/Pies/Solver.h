@@ -17,6 +17,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -312,6 +313,27 @@ public:
                                   float tMax, bool cullBack = false) {
     return _raycast(PIES_RAY_SKIN, skin, origins, directions, tMax, cullBack);
   }
+  // Extension (pies_closest_points in pies_hip.h states the rule): for every point the closest point of the scene's triangles
+  // (closestPoints; the triangle index counts the triangles in the order they were added) or of a skin's (closestPointsSkin; index
+  // local to the skin) within maxDistance, at the positions the device holds now.  u and v are the weights of the triangle's
+  // second and third corner at `position`.  A point without a triangle within maxDistance has found == false, distance = +inf and
+  // position = the point itself.  With winding == true, `winding` is the winding number of the target's triangles at the point
+  // and inside == |winding| > 0.5 (meaningful for closed surfaces; several bodies: inside any of them); otherwise both are 0.
+  struct SurfacePoint {
+    bool found;
+    uint32_t triangle;
+    float distance, u, v;
+    glm::vec3 position;
+    float winding;
+    bool inside;
+  };
+  std::vector<SurfacePoint> closestPoints(const std::vector<glm::vec3>& points, float maxDistance = INFINITY, bool winding = false) {
+    return _closestPoints(PIES_RAY_SCENE_TRIANGLES, 0, points, maxDistance, winding);
+  }
+  std::vector<SurfacePoint> closestPointsSkin(uint32_t skin, const std::vector<glm::vec3>& points, float maxDistance = INFINITY,
+                                              bool winding = false) {
+    return _closestPoints(PIES_RAY_SKIN, skin, points, maxDistance, winding);
+  }
   void addFixedRegions(const std::vector<glm::mat4>& regionMatrices, float w) {
     std::vector<float> m = _flattenMats(regionMatrices);
     _ck(pies_add_fixed_regions(_handle(), static_cast<uint32_t>(regionMatrices.size()), m.data(), w));
@@ -466,6 +488,27 @@ private:
       h.position = h.hit ? glm::vec3(p[0] + t[i] * q[0], p[1] + t[i] * q[1], p[2] + t[i] * q[2]) : p;
     }
     return hits;
+  }
+
+  std::vector<SurfacePoint> _closestPoints(int target, uint32_t skin, const std::vector<glm::vec3>& points, float maxDistance, bool winding) {
+    const uint32_t n = static_cast<uint32_t>(points.size());
+    std::vector<float> p = _flatten(points), d(n), uv(2 * size_t(n)), q(3 * size_t(n)), w(winding ? n : 0);
+    std::vector<uint32_t> tri(n);
+    _ck(pies_closest_points(_handle(), target, skin, n, p.data(), maxDistance, tri.data(), d.data(), uv.data(), q.data(),
+                            winding ? w.data() : nullptr));
+    std::vector<SurfacePoint> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      SurfacePoint& o = out[i];
+      o.found = tri[i] != PIES_NEAR_NONE;
+      o.triangle = tri[i];
+      o.distance = d[i];
+      o.u = uv[2 * i];
+      o.v = uv[2 * i + 1];
+      o.position = glm::vec3(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+      o.winding = winding ? w[i] : 0.0f;
+      o.inside = std::fabs(o.winding) > 0.5f;
+    }
+    return out;
   }
 
   // opens the device handle on first use

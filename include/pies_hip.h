@@ -403,6 +403,48 @@ enum { PIES_RAY_CULL_BACK = 1 }; /* flags */
 #define PIES_RAY_MISS 0xFFFFFFFFu
 int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, const float* origins, const float* directions,
                  float t_max, uint32_t flags, uint32_t* hit_triangle, float* hit_t, float* hit_uv);
+/* EXTENSION (the reference has no distance query): for n_points points the closest point of the surface as the device holds it
+ * now, and optionally the winding number of the surface there - penetration depth and direction of a prop the host moves, anchors
+ * that follow a (triangle, u, v), proximity probes, "is this point inside the body", all without a read-back.  points: n_points x 3
+ * floats.  target and skin mean what they mean for pies_raycast (PIES_RAY_SCENE_TRIANGLES: the PIES_TRIANGLES container in the
+ * host's order, also under PIES_FLAG_RENUMBER_NODES; PIES_RAY_SKIN: the triangles of skin `skin`, index local to that skin, its
+ * vertices evaluated on the same stream first).  The outputs may each be NULL: out_triangle (n_points), out_distance (n_points),
+ * out_uv (n_points x 2: the weights of corners b and c at the closest point), out_point (n_points x 3), out_winding (n_points).
+ * The rule for one (point p, triangle a b c) pair, in fp32 without fused multiply-adds, every dot product summed left to right as
+ * x x + y y + z z (the region walk of Ericson's closest point on a triangle; e11, e12, e22 are computed once per triangle):
+ *   e1 = b - a, e2 = c - a;  e11 = e1.e1, e12 = e1.e2, e22 = e2.e2;
+ *   ap = p - a;  d1 = e1.ap, d2 = e2.ap;  d3 = d1 - e11, d4 = d2 - e12, d5 = d1 - e12, d6 = d2 - e22;
+ *   vc = d1 d4 - d3 d2;  vb = d5 d2 - d1 d6;  va = d3 d6 - d5 d4;
+ *   the first that holds:  d1 <= 0 && d2 <= 0                        (u, v) = (0, 0)
+ *                          d3 >= 0 && d4 <= d3                       (1, 0)
+ *                          vc <= 0 && d1 >= 0 && d3 <= 0             (d1 / (d1 - d3), 0)
+ *                          d6 >= 0 && d5 <= d6                       (0, 1)
+ *                          vb <= 0 && d2 >= 0 && d6 <= 0             (0, d2 / (d2 - d6))
+ *                          va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0   w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); (1 - w, w)
+ *                          otherwise                                 inv = 1 / ((va + vb) + vc); (vb inv, vc inv)
+ *   q = (a + e1 u) + e2 v;  r = p - q;  dd = r.r;
+ *   a candidate iff dd <= FLT_MAX && dd <= max_distance * max_distance (the product rounded to fp32).
+ * Every test is the positive form written, so a NaN anywhere is no candidate.  The answer for a point is the candidate with the
+ * smallest dd, the lowest triangle index on equal dd (the normal case for a point nearest to a shared edge or corner): the minimum
+ * of the 64-bit key float_as_uint(dd) << 32 | triangle - dd is a sum of squares, +0 or larger, so the bit patterns order like the
+ * values - taken without atomics, so every kernel variant and every split of the triangles gives the same bits and two calls agree
+ * bit for bit.  out_triangle = that triangle, out_distance = sqrtf(dd), out_uv = (u, v), out_point = q, all from the winning pair
+ * evaluated once more; without a candidate PIES_NEAR_NONE, +inf, (0, 0) and p itself.
+ * out_winding: the generalised winding number of the target's triangle set at the point, the solid angle of a pair exactly as
+ * pies_voxelize_tri_mesh states it, summed in a fixed two-level order: per tile of 256 consecutive triangles in ascending index
+ * from 0.0f, then the tile sums in ascending tile index from 0.0f, then divided by 4 pi (12.566370614359172f).  The order is a
+ * function of the triangle count alone - not of the point count, the kernel variant or a chunking -, so two calls agree bit for
+ * bit.  "Inside" is |w| > 0.5 and means something for closed surfaces: on a scene with several closed bodies it is "inside any
+ * of them"; open sheets contribute fractions, and a target that is not closed has no inside.
+ * Runs on the handle's stream behind whatever ticks are queued and synchronises before it returns; node state, export frames,
+ * captured graphs and pies_launch_counts are left as they were; its buffers are allocated at the first call and freed by the
+ * next pies_finalize, pies_clear or pies_destroy.  Brute force over all triangles.
+ * PIES_ERR_INVALID: NULL points with n_points > 0, an unknown target, a skin id out of range, a negative or NaN max_distance (+inf
+ * is allowed; 0 finds only dd == 0).  PIES_ERR_UNSUPPORTED: more than 2^26 points.  n_points == 0 returns PIES_OK.  PIES_ERR_HIP:
+ * a PIES_DEVICE_NONE handle (the arguments are checked first).  A target without triangles gives no candidate and winding 0. */
+#define PIES_NEAR_NONE 0xFFFFFFFFu
+int pies_closest_points(pies_solver_t* s, int target, uint32_t skin, uint32_t n_points, const float* points, float max_distance,
+                        uint32_t* out_triangle, float* out_distance, float* out_uv, float* out_point, float* out_winding);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:
@@ -444,7 +486,10 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * 1 024 nodes on), PIES_FALLBACK_VISITS (candidate tests a pass left to the sequential loop may cost before it latches: 1e9),
  * PIES_PAIR_QUADS (0: one lane per pair in the pair order's levels) / _QUAD_BLOCKS / _QUAD_THREADS / PIES_PAIR_LOOK_WAVES (wavefronts of a level workgroup that look at frontier nodes, at most);
  * pies_raycast, read at every call: PIES_RAY_VARIANT (wide: one ray per lane, narrow: one triangle per lane; unset: narrow up to
- * PIES_RAY_NARROW_MAX rays, default 512: the measured crossover), PIES_RAY_CHUNKS (pins the triangle chunks of the wide variant, 1 .. 1 024).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
+ * PIES_RAY_NARROW_MAX rays, default 512: the measured crossover), PIES_RAY_CHUNKS (pins the triangle chunks of the wide variant, 1 .. 1 024);
+ * pies_closest_points, read at every call: PIES_NEAR_VARIANT (wide: one point per lane, narrow: one triangle per lane; unset: narrow
+ * up to PIES_NEAR_NARROW_MAX points, default 4 096: the end of the measured sweep), PIES_NEAR_CHUNKS
+ * (pins the triangle chunks of the wide variant, 1 .. 1 024); the winding pass has one form.  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
  * race with other API calls of the process (a handle reads the switches at different times of its life).  None of
  * them is read from the environment: the only environment variables the library looks at are PIES_SCHEDULE (default schedule
  * of new handles), PIES_PROFILER_SAFE (profiling runs) and the print-only PIES_PCG_DEBUG / PIES_LAYER_DEBUG. */

@@ -45,6 +45,7 @@ LAYER_MAX_CLASS = 25  # pies_count: the largest colour class of any tile and con
 RAY_SCENE_TRIANGLES, RAY_SKIN = 0, 1  # pies_raycast targets
 RAY_CULL_BACK = 1  # pies_raycast flag
 RAY_MISS = 0xFFFFFFFF  # PIES_RAY_MISS
+NEAR_NONE = 0xFFFFFFFF  # PIES_NEAR_NONE: pies_closest_points found no candidate
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -65,7 +66,7 @@ SYMBOLS = [
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
-    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast",
+    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -199,6 +200,7 @@ def load():
     sig["pies_voxelize_tri_mesh"] = [vp, u32, pf, u32, pu, pf, f32, pu, pf, C.POINTER(C.c_uint8)]
     sig["pies_add_tri_mesh_volume"] = [vp, u32, pf, u32, pu, pf, f32, f32, f32, f32, f32, f32, f32, u32, pu, pu, pu, pu]
     sig["pies_raycast"] = [vp, i32, u32, u32, pf, pf, f32, u32, pu, pf, pf]
+    sig["pies_closest_points"] = [vp, i32, u32, u32, pf, f32, pu, pf, pf, pf, pf]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -448,6 +450,20 @@ class Solver:
         self._ck(self._L.pies_raycast(self._h, target, skin, n, _pf(o), _pf(d), t_max, RAY_CULL_BACK if cull_back else 0,
                                       _pu(tri), _pf(t), _pf(uv)))
         return tri, t, uv
+
+    def closest_points(self, points, max_distance=float("inf"), target=RAY_SCENE_TRIANGLES, skin=0, winding=False):
+        """pies_closest_points: for every point (n x 3) the closest point of the scene's triangles or of skin `skin`
+        (target=RAY_SKIN) within max_distance, at the positions the device holds now.  Returns (triangle uint32 (n), distance
+        float32 (n), uv float32 (n, 2), point float32 (n, 3)) and, with winding=True, the winding number float32 (n) as a fifth
+        (inside a closed surface: |w| > 0.5); no candidate is (NEAR_NONE, +inf, (0, 0), the point itself)."""
+        p = _f32(points).reshape(-1, 3)
+        n = len(p)
+        tri, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        uv, q = np.empty((n, 2), np.float32), np.empty((n, 3), np.float32)
+        w = np.empty(n, np.float32) if winding else None
+        self._ck(self._L.pies_closest_points(self._h, target, skin, n, _pf(p), max_distance, _pu(tri), _pf(dist), _pf(uv), _pf(q),
+                                             _pf(w) if winding else None))
+        return (tri, dist, uv, q, w) if winding else (tri, dist, uv, q)
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

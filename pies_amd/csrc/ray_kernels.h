@@ -33,7 +33,8 @@ struct RayBatch {  // rays [0, n): origins and directions 3 floats each
   uint32_t flags = 0;  // PIES_RAY_CULL_BACK
 };
 
-// Wide variant.  Staging: one lane per triangle gathers the corners once and stores the record (a, e1, e2) as 3 float4.
+// Wide variant.  Staging: one lane per triangle gathers the corners once and stores the record (a, e1, e2) as 3 float4; the three
+// words left over hold e1.e1, e1.e2, e2.e2 for pies_closest_points (near_kernels.h), which stages with this kernel too.
 void launch_ray_stage(hipStream_t st, const RayTarget& T, float4* records);
 // One ray per lane; the records go through LDS in tiles and are read as wave-wide broadcasts.  grid.y = chunks splits the
 // tiles; partial[chunk * R.n + ray] receives the chunk's key.

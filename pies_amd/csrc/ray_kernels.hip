@@ -17,17 +17,10 @@
 #include <cfloat>
 
 #include "../../include/pies_hip.h"
+#include "surface_device.h"
 
 namespace pies {
 namespace {
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 load3(const float* p) { return {p[0], p[1], p[2]}; }
 
 // The rule for one (ray, triangle) pair: ray (o, d), triangle corner a and edges e1 = b - a, e2 = c - a.  Every test in the
 // positive form: a NaN anywhere is a miss.
@@ -47,17 +40,10 @@ __device__ __forceinline__ bool ray_pair(V3 o, V3 d, V3 a, V3 e1, V3 e2, float t
   return t >= 0.0f && t <= tMax;
 }
 
-__device__ __forceinline__ uint64_t ray_key(float t, uint32_t triangle) {
-  return static_cast<uint64_t>(__float_as_uint(t)) << 32 | triangle;
-}
+__device__ __forceinline__ uint64_t ray_key(float t, uint32_t triangle) { return surface_key(t, triangle); }
 
-__device__ __forceinline__ void gather_triangle(const RayTarget& T, uint32_t t, V3& a, V3& e1, V3& e2) {
-  const uint32_t* id = T.tri + 3ull * t;
-  a = load3(T.pos + static_cast<size_t>(T.stride) * id[0]);
-  e1 = sub(load3(T.pos + static_cast<size_t>(T.stride) * id[1]), a);
-  e2 = sub(load3(T.pos + static_cast<size_t>(T.stride) * id[2]), a);
-}
-
+// The last three words are the triangle's own dot products e1.e1, e1.e2, e2.e2: pies_closest_points reads them (near_kernels.hip),
+// a ray cast does not.
 __global__ void __launch_bounds__(kRayBlock) k_ray_stage(RayTarget T, float4* __restrict__ records) {
   const uint32_t t = blockIdx.x * kRayBlock + threadIdx.x;
   if (t >= T.nTris) return;
@@ -66,7 +52,7 @@ __global__ void __launch_bounds__(kRayBlock) k_ray_stage(RayTarget T, float4* __
   float4* r = records + 3ull * t;
   r[0] = make_float4(a.x, a.y, a.z, e1.x);
   r[1] = make_float4(e1.y, e1.z, e2.x, e2.y);
-  r[2] = make_float4(e2.z, 0.0f, 0.0f, 0.0f);
+  r[2] = make_float4(e2.z, dot(e1, e1), dot(e1, e2), dot(e2, e2));
 }
 
 __global__ void __launch_bounds__(kRayBlock) k_ray_cast(const float4* __restrict__ records, uint32_t nTris, RayBatch R,

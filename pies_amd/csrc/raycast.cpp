@@ -23,20 +23,24 @@ constexpr size_t kRayBatchKeys = 1ull << 24;  // partial keys of one batch of ra
 constexpr uint32_t kRayNarrowMaxDefault = 512;  // measured crossover on BASELINE config 3's beam surface (narrow no slower up to 512 rays)
 constexpr uint32_t kRayWorkgroupsWanted = 1024;  // wide variant: ray blocks x chunks to aim for (4 workgroups per CU)
 
-// Replaces *d by a buffer of `count` elements (the stream is idle between calls: every call ends in a synchronisation).
-template <class T> int ray_grow(pies_solver* s, size_t count, T** d) {
+}  // namespace
+
+// Replaces *d by a buffer of `bytes` bytes (the stream is idle between calls: every call ends in a synchronisation).
+int ray_grow_bytes(pies_solver* s, size_t bytes, void** d) {
   RayBuffers& B = s->ray;
   if (*d) {
-    B.allocations.erase(std::remove(B.allocations.begin(), B.allocations.end(), static_cast<void*>(*d)), B.allocations.end());
+    B.allocations.erase(std::remove(B.allocations.begin(), B.allocations.end(), *d), B.allocations.end());
     (void)hipFree(*d);
     *d = nullptr;
   }
   void* p = nullptr;
-  HIP_TRY(s, hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+  HIP_TRY(s, hipMalloc(&p, std::max<size_t>(bytes, 1)));
   B.allocations.push_back(p);
-  *d = static_cast<T*>(p);
+  *d = p;
   return PIES_OK;
 }
+
+namespace {
 
 // The scene's triangle list in the numbering the device holds; built once per pies_finalize (free_device forgets it).
 int ray_build_scene_triangles(pies_solver* s) {
@@ -64,24 +68,10 @@ int all_misses(uint32_t n, uint32_t* hitTriangle, float* hitT, float* hitUv) {
 }
 
 }  // namespace
-}  // namespace pies
 
-extern "C" {
-
-int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, const float* origins, const float* directions,
-                 float t_max, uint32_t flags, uint32_t* hit_triangle, float* hit_t, float* hit_uv) {
-  if (!s) return PIES_ERR_INVALID;
-  if (n_rays && (!origins || !directions)) return fail(s, PIES_ERR_INVALID, "pies_raycast: origins or directions is NULL");
-  if (target != PIES_RAY_SCENE_TRIANGLES && target != PIES_RAY_SKIN) return fail(s, PIES_ERR_INVALID, "pies_raycast: unknown target");
-  if (target == PIES_RAY_SKIN && skin >= s->h_skins.size()) return fail(s, PIES_ERR_INVALID, "pies_raycast: no such skin");
-  if (!(t_max >= 0.0f)) return fail(s, PIES_ERR_INVALID, "pies_raycast: t_max must be >= 0 (+inf is allowed)");
-  if (n_rays > kRayMaxRays) return fail(s, PIES_ERR_UNSUPPORTED, "pies_raycast: more than 2^26 rays");
-  if (n_rays == 0) return PIES_OK;
-  if (s->device == PIES_DEVICE_NONE) return fail(s, PIES_ERR_HIP, "host-only handle (PIES_DEVICE_NONE): rays are cast on the device");
-  if (int rc = pies_internal_ensure_ready(s)) return rc;
+// The triangles of a checked (target, skin) at the positions the device holds; a skin's vertices are evaluated on the stream first.
+int ray_open_target(pies_solver* s, int target, uint32_t skin, RayTarget* out) {
   RayBuffers& B = s->ray;
-
-  // ---- the target's triangles ----
   RayTarget T;
   if (target == PIES_RAY_SKIN) {
     const HostSkin& k = s->h_skins[skin];
@@ -99,6 +89,28 @@ int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, c
     T.pos = reinterpret_cast<const float*>(s->dev.nd.pos);
     T.tri = B.tri;
   }
+  *out = T;
+  return PIES_OK;
+}
+
+}  // namespace pies
+
+extern "C" {
+
+int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, const float* origins, const float* directions,
+                 float t_max, uint32_t flags, uint32_t* hit_triangle, float* hit_t, float* hit_uv) {
+  if (!s) return PIES_ERR_INVALID;
+  if (n_rays && (!origins || !directions)) return fail(s, PIES_ERR_INVALID, "pies_raycast: origins or directions is NULL");
+  if (target != PIES_RAY_SCENE_TRIANGLES && target != PIES_RAY_SKIN) return fail(s, PIES_ERR_INVALID, "pies_raycast: unknown target");
+  if (target == PIES_RAY_SKIN && skin >= s->h_skins.size()) return fail(s, PIES_ERR_INVALID, "pies_raycast: no such skin");
+  if (!(t_max >= 0.0f)) return fail(s, PIES_ERR_INVALID, "pies_raycast: t_max must be >= 0 (+inf is allowed)");
+  if (n_rays > kRayMaxRays) return fail(s, PIES_ERR_UNSUPPORTED, "pies_raycast: more than 2^26 rays");
+  if (n_rays == 0) return PIES_OK;
+  if (s->device == PIES_DEVICE_NONE) return fail(s, PIES_ERR_HIP, "host-only handle (PIES_DEVICE_NONE): rays are cast on the device");
+  if (int rc = pies_internal_ensure_ready(s)) return rc;
+  RayBuffers& B = s->ray;
+  RayTarget T;
+  if (int rc = ray_open_target(s, target, skin, &T)) return rc;
   if (T.nTris == 0) {
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     return all_misses(n_rays, hit_triangle, hit_t, hit_uv);

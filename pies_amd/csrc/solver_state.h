@@ -193,6 +193,12 @@ struct RayBuffers {
   uint32_t* outTri = nullptr;   // results, n rays each
   float *outT = nullptr, *outUv = nullptr;
   size_t rayCap = 0;            // rays
+  // pies_closest_points (nearest.cpp) shares tri, records and partial - the winding pass keeps its tile sums in partial - and
+  // has the points and results to itself
+  float* nearPoints = nullptr;    // 3 n
+  uint32_t* nearTri = nullptr;    // results: n, n, 2 n, 3 n, n
+  float *nearDistance = nullptr, *nearUv = nullptr, *nearPoint = nullptr, *nearWinding = nullptr;
+  size_t nearCap = 0;             // points
 };
 
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
@@ -390,8 +396,18 @@ bool build_layer_plan(pies_solver* s);
 // skin.cpp : device records of the skins (no-ops without skins); skin_free_device forgets them (free_device, pies_clear)
 int skin_upload(pies_solver* s);
 void skin_free_device(pies_solver* s);
-// raycast.cpp : forgets the buffers of pies_raycast (free_device)
+// raycast.cpp : forgets the buffers of pies_raycast and pies_closest_points (free_device)
 void ray_free_device(pies_solver* s);
+// raycast.cpp, shared with nearest.cpp : replaces a buffer of s->ray (ray_free_device frees it); the triangles of a checked
+// (target, skin) of pies_raycast at the positions the device holds, a skin's vertices evaluated on the stream first
+int ray_grow_bytes(pies_solver* s, size_t bytes, void** d);
+template <class T> int ray_grow(pies_solver* s, size_t count, T** d) {
+  void* p = *d;
+  const int rc = ray_grow_bytes(s, count * sizeof(T), &p);
+  *d = static_cast<T*>(p);
+  return rc;
+}
+int ray_open_target(pies_solver* s, int target, uint32_t skin, pies::RayTarget* out);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of

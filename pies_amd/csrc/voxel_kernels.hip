@@ -10,6 +10,8 @@
 // tests/test_trimesh.py restates in numpy.
 #include "voxel_kernels.h"
 
+#include "surface_device.h"
+
 namespace pies {
 namespace {
 
@@ -45,18 +47,7 @@ __global__ void __launch_bounds__(kVoxelBlock) k_winding(const float* __restrict
       const float ax = q[0] - cx, ay = q[1] - cy, az = q[2] - cz;
       const float bx = q[3] - cx, by = q[4] - cy, bz = q[5] - cz;
       const float dx = q[6] - cx, dy = q[7] - cy, dz = q[8] - cz;
-      const float la = sqrtf(ax * ax + ay * ay + az * az);
-      const float lb = sqrtf(bx * bx + by * by + bz * bz);
-      const float ld = sqrtf(dx * dx + dy * dy + dz * dz);
-      // det [A, B, D] (columns), the expansion det3 of skin.cpp
-      const float num = ax * (by * dz - dy * bz) - bx * (ay * dz - dy * az) + dx * (ay * bz - by * az);
-      const float ab = ax * bx + ay * by + az * bz;
-      const float bd = bx * dx + by * dy + bz * dz;
-      const float da = dx * ax + dy * ay + dz * az;
-      const float den = la * lb * ld + ab * ld + bd * la + da * lb;
-      float omega = 2.0f * atan2f(num, den);
-      if ((num == 0.0f && den == 0.0f) || !(fabsf(omega) <= 3.402823466e+38f)) omega = 0.0f;  // (NaN too)
-      sum = sum + omega;
+      sum = sum + solid_angle(ax, ay, az, bx, by, bz, dx, dy, dz);  // (surface_device.h: shared with pies_closest_points)
     }
   }
   if (live) {
