@@ -334,6 +334,82 @@ public:
                                               bool winding = false) {
     return _closestPoints(PIES_RAY_SKIN, skin, points, maxDistance, winding);
   }
+  // Extension (pies_collide_props in pies_hip.h states the rule): kinematic props - spheres, capsules and rounded oriented boxes
+  // the host moves.  collideProps pushes the nodes out of them on the device, in the order given; a touched node takes the prop's
+  // velocity at the contact along the normal (it keeps an outward normal velocity of its own) and loses the share `friction` of
+  // its tangential velocity relative to the prop.  Per prop it returns the touches' impulse and torque about the prop's pivot -
+  // the host applies -impulse and -torque to its own rigid body - and the number of nodes touched.  Call it once per frame
+  // before tick; getVertices() is refreshed the way tick refreshes it.
+  struct Prop : pies_prop_t {
+    // pivot = the centre (capsule: end a) until setMotion names another
+    static Prop sphere(const glm::vec3& centre, float radius) { return _shape(PIES_PROP_SPHERE, centre, radius); }
+    static Prop capsule(const glm::vec3& a, const glm::vec3& b, float radius) {
+      Prop p = _shape(PIES_PROP_CAPSULE, a, radius);
+      for (int k = 0; k < 3; ++k) p.end[k] = b[k];
+      return p;
+    }
+    // axes: unit and orthogonal; rounding: the radius the box's corners and edges are rounded with (it grows the box)
+    static Prop box(const glm::vec3& centre, const glm::vec3& halfExtents, const glm::vec3& axis0 = glm::vec3(1.0f, 0.0f, 0.0f),
+                    const glm::vec3& axis1 = glm::vec3(0.0f, 1.0f, 0.0f), const glm::vec3& axis2 = glm::vec3(0.0f, 0.0f, 1.0f),
+                    float rounding = 0.0f) {
+      Prop p = _shape(PIES_PROP_BOX, centre, rounding);
+      for (int k = 0; k < 3; ++k) {
+        p.half[k] = halfExtents[k];
+        p.axes[k] = axis0[k];
+        p.axes[3 + k] = axis1[k];
+        p.axes[6 + k] = axis2[k];
+      }
+      return p;
+    }
+    Prop& setMotion(const glm::vec3& linear, const glm::vec3& angularVelocity, const glm::vec3& about) {
+      for (int k = 0; k < 3; ++k) {
+        velocity[k] = linear[k];
+        angular[k] = angularVelocity[k];
+        pivot[k] = about[k];
+      }
+      return *this;
+    }
+    Prop& setVelocity(const glm::vec3& linear) {
+      for (int k = 0; k < 3; ++k) velocity[k] = linear[k];
+      return *this;
+    }
+    Prop& setFriction(float f) {
+      friction = f;
+      return *this;
+    }
+
+   private:
+    static Prop _shape(int shape, const glm::vec3& centre, float radius) {
+      Prop p;
+      std::memset(static_cast<pies_prop_t*>(&p), 0, sizeof(pies_prop_t));
+      p.shape = shape;
+      p.radius = radius;
+      for (int k = 0; k < 3; ++k) p.centre[k] = p.pivot[k] = centre[k];
+      p.axes[0] = p.axes[4] = p.axes[8] = 1.0f;
+      return p;
+    }
+  };
+  struct PropReaction {
+    glm::vec3 impulse, torque;
+    uint32_t hits;
+  };
+  std::vector<PropReaction> collideProps(const std::vector<Prop>& props) {
+    const uint32_t n = static_cast<uint32_t>(props.size());
+    std::vector<pies_prop_t> records(props.begin(), props.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n));
+    std::vector<uint32_t> hits(n);
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_collide_props(_handle(), n, records.data(), impulse.data(), torque.data(), hits.data(), nullptr));
+    _refreshPositions();
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
+    std::vector<PropReaction> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].hits = hits[k];
+    }
+    return out;
+  }
   void addFixedRegions(const std::vector<glm::mat4>& regionMatrices, float w) {
     std::vector<float> m = _flattenMats(regionMatrices);
     _ck(pies_add_fixed_regions(_handle(), static_cast<uint32_t>(regionMatrices.size()), m.data(), w));

@@ -445,6 +445,66 @@ int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, c
 #define PIES_NEAR_NONE 0xFFFFFFFFu
 int pies_closest_points(pies_solver_t* s, int target, uint32_t skin, uint32_t n_points, const float* points, float max_distance,
                         uint32_t* out_triangle, float* out_distance, float* out_uv, float* out_point, float* out_winding);
+/* EXTENSION (the reference's only obstacle is the floor, Src/Solver.cpp): kinematic props - spheres, capsules and rounded oriented
+ * boxes the host moves.  The nodes are pushed out of them where HBM holds them, the velocity response is relative to the moving
+ * prop, and the reaction impulse and torque per prop come back so that the host can drive a rigid body of its own: the first
+ * device-side edit of node state (the other one, pies_write_nodes, downloads, overwrites a whole host array and uploads four).
+ * props: n_props records, applied in ascending index.  The outputs may each be NULL: out_impulse, out_torque (n_props x 3),
+ * out_hits (n_props), out_node_prop (pies_count(PIES_NODES) entries in host numbering: the index of the last prop that touched the
+ * node, or PIES_PROP_NONE).
+ * The rule, in fp32 without fused multiply-adds.  Dot products are summed left to right as x x + y y + z z, cross is pies_raycast's,
+ * a vector times (or divided by) a scalar is taken componentwise, a + b * t is the product rounded, then the sum.  fmaxf and fminf
+ * return the other operand when one is a NaN.  Every test is the positive form written, so a NaN anywhere is "not touched".
+ * A node has position p (invMass in .w), velocity v and radius r.  A node with invMass == 0 is never touched.  Otherwise the props
+ * are applied in ascending index, each to the state the previous one left.  R = prop.radius + r: the node's own radius counts, as
+ * it does for the floor.
+ *   The sphere rule, centre c:  d = p - c, dd = d.d;  touched iff dd < R * R (the product rounded);
+ *                               n = d / sqrtf(dd) if dd > 0, else (0, 1, 0);  q = c + n * R.
+ *   PIES_PROP_SPHERE   the sphere rule with c = centre.
+ *   PIES_PROP_CAPSULE  a = centre, b = end;  ab = b - a, ap = p - a, den = ab.ab;
+ *                      t = den > 0 ? fminf(fmaxf((ap.ab) / den, 0), 1) : 0;  the sphere rule with c = a + ab * t.
+ *   PIES_PROP_BOX      l_j = axis_j . (p - centre);  inside iff fabsf(l_j) <= half_j for j = 0, 1, 2.
+ *                      inside:   e_j = half_j - fabsf(l_j), j* the smallest e_j (the lowest j on a tie);
+ *                                n = axis_j* if l_j* >= 0, else -axis_j*;  q = p + n * (e_j* + R);  always touched.
+ *                      outside:  k_j = fminf(fmaxf(l_j, -half_j), half_j);
+ *                                the sphere rule with c = ((centre + axis_0 * k_0) + axis_1 * k_1) + axis_2 * k_2.
+ *   A touch:  p = q, and the previous position becomes q as well - PD's velocity update reads position - prevPosition
+ *             (Src/Solver.cpp:389-392), so the push does not turn into velocity there; PBD overwrites the previous position (:48).
+ *             u = velocity + cross(angular, q - pivot);  rel = v - u, vn = rel.n;  tang = rel - n * vn;
+ *             v' = u + (tang * (1 - friction) + n * fmaxf(vn, 0));
+ *             the touch's impulse j = (v - v') * (1 / invMass), its torque cross(q - pivot, j);  then v = v'.
+ *             The position correction itself carries no impulse: j is the change of momentum of the velocity response alone.
+ * out_hits[k] counts the nodes prop k touched.  out_impulse[k] and out_torque[k] are the touches' j and torque summed in a fixed
+ * two-level order: per tile of 256 consecutive HOST node ids in ascending id from 0.0f (an untouched node adds 0), then the tile
+ * sums in ascending tile index from 0.0f.  The order is a function of the node count alone - not of a kernel variant, not of
+ * PIES_FLAG_RENUMBER_NODES - and nothing is summed with atomics, so two calls agree bit for bit.  The host applies -impulse and
+ * -torque (about pivot) to its own body.
+ * Runs on the handle's stream behind whatever ticks are queued, finalizes a changed scene first and synchronises before it
+ * returns; export frames begun earlier, captured graphs and pies_launch_counts are left as they were.  The edit is in HBM only:
+ * the host mirror is marked stale for positions, previous positions and velocities, so pies_read_nodes, pies_tick and a scene edit
+ * see it; nothing is uploaded.  Its buffers are allocated at the first call and freed by the next pies_finalize, pies_clear or
+ * pies_destroy.
+ * PIES_ERR_INVALID: NULL props with n_props > 0, an unknown shape, a negative or non-finite radius or half extent, friction
+ * outside [0, 1], a non-finite field the shape uses (velocity, angular and pivot always; centre; a capsule's end; a box's axes and
+ * half extents).  PIES_ERR_UNSUPPORTED: n_props > PIES_PROP_MAX.  n_props == 0 returns PIES_OK and touches nothing (out_node_prop
+ * is all PIES_PROP_NONE).  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first). */
+enum { PIES_PROP_SPHERE = 0, PIES_PROP_CAPSULE = 1, PIES_PROP_BOX = 2 };
+#define PIES_PROP_NONE 0xFFFFFFFFu
+#define PIES_PROP_MAX 64
+typedef struct pies_prop {
+  int32_t shape;
+  float radius;      /* sphere, capsule: radius; box: rounding radius; >= 0 */
+  float centre[3];   /* sphere: centre; capsule: end a; box: centre */
+  float end[3];      /* capsule: end b; otherwise ignored */
+  float axes[9];     /* box: axis j = axes[3 j .. 3 j + 2], unit and orthogonal (the host's duty); otherwise ignored */
+  float half[3];     /* box: half extents >= 0 */
+  float velocity[3]; /* velocity of the pivot */
+  float angular[3];  /* angular velocity about the pivot */
+  float pivot[3];    /* point the angular velocity and the returned torque refer to */
+  float friction;    /* 0 .. 1: share of the tangential relative velocity a touch removes */
+} pies_prop_t;
+int pies_collide_props(pies_solver_t* s, uint32_t n_props, const pies_prop_t* props, float* out_impulse, float* out_torque,
+                       uint32_t* out_hits, uint32_t* out_node_prop);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:

@@ -46,6 +46,9 @@ RAY_SCENE_TRIANGLES, RAY_SKIN = 0, 1  # pies_raycast targets
 RAY_CULL_BACK = 1  # pies_raycast flag
 RAY_MISS = 0xFFFFFFFF  # PIES_RAY_MISS
 NEAR_NONE = 0xFFFFFFFF  # PIES_NEAR_NONE: pies_closest_points found no candidate
+PROP_SPHERE, PROP_CAPSULE, PROP_BOX = 0, 1, 2  # pies_prop_t.shape
+PROP_NONE = 0xFFFFFFFF  # PIES_PROP_NONE: no prop touched the node
+PROP_MAX = 64  # PIES_PROP_MAX
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -66,7 +69,7 @@ SYMBOLS = [
     "pies_get_pd_tile_plan", "pies_get_tri_grid_stats", "pies_set_rest", "pies_get_collision_fallbacks",
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
-    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points",
+    "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -117,6 +120,47 @@ class Options(C.Structure):
             if not hasattr(self, k):
                 raise AttributeError(k)
             setattr(self, k, v)
+
+
+class Prop(C.Structure):
+    """pies_prop_t field for field: a kinematic sphere, capsule or rounded box of pies_collide_props."""
+    _fields_ = [
+        ("shape", C.c_int32), ("radius", C.c_float), ("centre", C.c_float * 3), ("end", C.c_float * 3),
+        ("axes", C.c_float * 9), ("half", C.c_float * 3), ("velocity", C.c_float * 3), ("angular", C.c_float * 3),
+        ("pivot", C.c_float * 3), ("friction", C.c_float),
+    ]
+
+    @classmethod
+    def _make(cls, shape, radius, centre, velocity, angular, pivot, friction):
+        p = cls()
+        p.shape, p.radius, p.friction = shape, radius, friction
+        p.centre[:] = [float(x) for x in centre]
+        p.velocity[:] = [float(x) for x in velocity]
+        p.angular[:] = [float(x) for x in angular]
+        p.pivot[:] = [float(x) for x in (centre if pivot is None else pivot)]
+        p.axes[:] = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+        return p
+
+    @classmethod
+    def sphere(cls, centre, radius, velocity=(0, 0, 0), angular=(0, 0, 0), pivot=None, friction=0.0):
+        """pivot None: the centre"""
+        return cls._make(PROP_SPHERE, radius, centre, velocity, angular, pivot, friction)
+
+    @classmethod
+    def capsule(cls, a, b, radius, velocity=(0, 0, 0), angular=(0, 0, 0), pivot=None, friction=0.0):
+        """the segment a b with a radius; pivot None: end a"""
+        p = cls._make(PROP_CAPSULE, radius, a, velocity, angular, pivot, friction)
+        p.end[:] = [float(x) for x in b]
+        return p
+
+    @classmethod
+    def box(cls, centre, half, axes=None, rounding=0.0, velocity=(0, 0, 0), angular=(0, 0, 0), pivot=None, friction=0.0):
+        """axes: 3 x 3, row j the unit axis j (None: the world's); rounding: the rounding radius; pivot None: the centre"""
+        p = cls._make(PROP_BOX, rounding, centre, velocity, angular, pivot, friction)
+        p.half[:] = [float(x) for x in half]
+        if axes is not None:
+            p.axes[:] = [float(x) for x in np.asarray(axes, dtype=np.float32).reshape(9)]
+        return p
 
 
 _lib = None
@@ -201,6 +245,7 @@ def load():
     sig["pies_add_tri_mesh_volume"] = [vp, u32, pf, u32, pu, pf, f32, f32, f32, f32, f32, f32, f32, u32, pu, pu, pu, pu]
     sig["pies_raycast"] = [vp, i32, u32, u32, pf, pf, f32, u32, pu, pf, pf]
     sig["pies_closest_points"] = [vp, i32, u32, u32, pf, f32, pu, pf, pf, pf, pf]
+    sig["pies_collide_props"] = [vp, u32, C.POINTER(Prop), pf, pf, pu, pu]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -464,6 +509,22 @@ class Solver:
         self._ck(self._L.pies_closest_points(self._h, target, skin, n, _pf(p), max_distance, _pu(tri), _pf(dist), _pf(uv), _pf(q),
                                              _pf(w) if winding else None))
         return (tri, dist, uv, q, w) if winding else (tri, dist, uv, q)
+
+    def collide_props(self, props, reaction=True, node_prop=False):
+        """pies_collide_props: pushes the nodes out of the props (a sequence of Prop, applied in order) where the device holds
+        them; the velocity response is relative to the moving prop.  Returns (impulse float32 (k, 3), torque float32 (k, 3), hits
+        uint32 (k)) with reaction=True - the host applies -impulse and -torque (about the prop's pivot) to its own body -, followed by
+        the last prop that touched every node (uint32 (n), PROP_NONE: none) with node_prop=True; None when neither is asked for."""
+        props = list(props)
+        k = len(props)
+        arr = (Prop * max(k, 1))(*props)
+        imp, tor, hits = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)) if reaction else (None,) * 3
+        who = np.empty(self.count(NODES), np.uint32) if node_prop else None
+        self._ck(self._L.pies_collide_props(self._h, k, arr if k else None, _pf(imp) if reaction else None,
+                                            _pf(tor) if reaction else None, _pu(hits) if reaction else None,
+                                            _pu(who) if node_prop else None))
+        out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
+        return out or None
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

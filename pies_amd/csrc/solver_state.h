@@ -199,6 +199,15 @@ struct RayBuffers {
   uint32_t* nearTri = nullptr;    // results: n, n, 2 n, 3 n, n
   float *nearDistance = nullptr, *nearUv = nullptr, *nearPoint = nullptr, *nearWinding = nullptr;
   size_t nearCap = 0;             // points
+  // pies_collide_props (props.cpp) has its buffers to itself; they live here so that free_device drops them with the others
+  pies_prop_t* propRecords = nullptr;  // PIES_PROP_MAX records
+  float* propOut = nullptr;            // PIES_PROP_MAX x kPropSumWords: the folded sums
+  uint64_t* propTileMask = nullptr;    // per tile of 256 host ids: the props that touched it
+  size_t propTileCap = 0;              // tiles
+  float* propTileSums = nullptr;       // per (tile, prop): kPropSumWords words
+  size_t propSumCap = 0;               // (tile, prop) records
+  uint32_t* propNodeProp = nullptr;    // per host id: the last prop that touched the node
+  size_t propNodeCap = 0;              // nodes
 };
 
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
@@ -396,7 +405,7 @@ bool build_layer_plan(pies_solver* s);
 // skin.cpp : device records of the skins (no-ops without skins); skin_free_device forgets them (free_device, pies_clear)
 int skin_upload(pies_solver* s);
 void skin_free_device(pies_solver* s);
-// raycast.cpp : forgets the buffers of pies_raycast and pies_closest_points (free_device)
+// raycast.cpp : forgets the buffers of pies_raycast, pies_closest_points and pies_collide_props (free_device)
 void ray_free_device(pies_solver* s);
 // raycast.cpp, shared with nearest.cpp : replaces a buffer of s->ray (ray_free_device frees it); the triangles of a checked
 // (target, skin) of pies_raycast at the positions the device holds, a skin's vertices evaluated on the stream first
