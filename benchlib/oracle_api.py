@@ -321,6 +321,19 @@ class OracleSolver:
         lib().ora_get_rest(self._h, ctype, _pf(out))
         return out
 
+    def set_rest(self, ctype, rest, first=0):
+        """ora_set_rest: rest data of constraints first .. of a container, in rest()'s layout (the product's Solver.set_rest)"""
+        r = np.ascontiguousarray(rest, dtype=np.float32)
+        n = r.size // _REST_PER[ctype]
+        if first + n > self.count(ctype):
+            raise ValueError("set_rest: range beyond the container")
+        # bound here and not in lib(): an oracle library built before the entry point existed still serves everything else
+        fn = getattr(lib(), "ora_set_rest", None)
+        if fn is None:
+            raise RuntimeError("this oracle library has no ora_set_rest: build it again (make -C oracle)")
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        fn(self._h, ctype, first, n, _pf(r))
+
     def tick(self, n=1):
         for _ in range(n):
             lib().ora_tick(self._h)

@@ -1445,9 +1445,14 @@ static PositionCon makePosition(uint32_t id, const Node& n, float w) {
   return c;
 }
 // A = [0 ; diffToBary_ * worldToDiff] with diffToBary_(r,c) = diffToBary[r][c] (glm indices), B = I
+static void tetAFromQinv(const mat3& Qinv, float A[4][4]);
 static void tetA(const Node& x1, const Node& x2, const Node& x3, const Node& x4, mat3& Qinv, float A[4][4]) {
   mat3 baryToDiff(x2.position - x1.position, x3.position - x1.position, x4.position - x1.position);
   Qinv = inverse(baryToDiff);
+  tetAFromQinv(Qinv, A);
+}
+// (also after ora_set_rest replaced Qinv)
+static void tetAFromQinv(const mat3& Qinv, float A[4][4]) {
   const float D[3][4] = {{-1, 1, 0, 0}, {-1, 0, 1, 0}, {-1, 0, 0, 1}};
   for (int j = 0; j < 4; ++j) A[0][j] = 0.0f;
   for (int r = 0; r < 3; ++r)
@@ -2010,6 +2015,31 @@ void ora_get_rest(ora_solver* s, int type, float* out) {
   if (type == 2) for (auto& c : s->tetCons) for (int col = 0; col < 3; ++col) for (int r = 0; r < 3; ++r) out[k++] = c.Qinv[col][r];
   if (type == 3) for (auto& c : s->volumeCons) for (int col = 0; col < 3; ++col) for (int r = 0; r < 3; ++r) out[k++] = c.Qinv[col][r];
   if (type == 4) for (auto& c : s->bendCons) out[k++] = c.initialAngle;
+}
+// The counterpart of pies_set_rest: rest data of constraints [first, first + n) of a container replaced, in ora_get_rest's layout.
+// What the factories derive from Qinv (A, AtA, AtB) follows it; the auxiliary variables stay.  Out-of-range requests are ignored.
+void ora_set_rest(ora_solver* s, int type, uint32_t first, uint32_t n, const float* rest) {
+  auto in_range = [&](size_t size) { return static_cast<uint64_t>(first) + n <= size; };
+  auto set_qinv = [&](auto& list) {
+    if (!in_range(list.size())) return;
+    for (uint32_t i = 0; i < n; ++i) {
+      auto& c = list[first + i];
+      for (int col = 0; col < 3; ++col) for (int r = 0; r < 3; ++r) c.Qinv[col][r] = rest[9ull * i + 3 * col + r];
+      float A[4][4];
+      tetAFromQinv(c.Qinv, A);
+      const auto projected = c.projected;
+      c.init(c.id, c.w, A, I4, c.nodeIds);
+      c.projected = projected;
+    }
+  };
+  switch (type) {
+    case 1: if (in_range(s->distanceCons.size())) for (uint32_t i = 0; i < n; ++i) s->distanceCons[first + i].targetDistance = rest[i]; break;
+    case 2: set_qinv(s->tetCons); break;
+    case 3: set_qinv(s->volumeCons); break;
+    case 4: if (in_range(s->bendCons.size())) for (uint32_t i = 0; i < n; ++i) s->bendCons[first + i].initialAngle = rest[i]; break;
+    default: return;
+  }
+  s->pdDirty = true;
 }
 
 void ora_tick(ora_solver* s) { s->tick(); }

@@ -831,6 +831,13 @@ int pies_write_nodes(pies_solver_t* s, int what, const float* in, uint32_t n) {
     case PIES_NODE_INV_MASS: dst = &s->h_invMass; break;
     default: return fail(s, PIES_ERR_INVALID, "pies_write_nodes: unknown selector");
   }
+  // Projective Dynamics: the system matrix K = diag(1 / (invMass h^2)) + sum w A^T A, its preconditioner, the SELL rows and the
+  // row dictionary are built from the masses in pies_finalize (pd_build), and k_pd_predict forms M s_n / h^2 from pos.w: new
+  // masses in pos.w alone would leave the two sides of the solve with different M.  PBD keeps mass in pos.w only.  (A host
+  // that writes back the masses it read - a full state restore every frame - keeps its scene.)
+  if (what == PIES_NODE_INV_MASS && s->opt.solver == PIES_SOLVER_PD && !dst->empty() &&
+      std::memcmp(dst->data(), in, dst->size() * sizeof(float)) != 0)
+    s->sceneDirty = true;
   if (!dst->empty()) std::memcpy(dst->data(), in, dst->size() * sizeof(float));
   s->hostNodesDirty = true;
   if (what == PIES_NODE_RADIUS && s->dev.hash.counters && !s->sceneDirty) {  // the collision grid is sized from the radii
