@@ -4,20 +4,26 @@
 // an fmaf, a separate multiply and add stay separate, every per-element decision is taken from the element's own data - the
 // results are bit for bit the same.  What differs is what stands around the arithmetic:
 //
-//  * every 3x3 quantity that is updated row by row (A, B = A V, V, the recomposition's t and out, the blend) is held per column as
-//    a pair (rows 0, 1) plus a float (row 2), and the row-wise updates - a rotation, the polish, B = A V0, the recomposition, the
-//    blend - are written on the pairs.  The pairs exist in the source, so the compiler has packed forms (v_pk_fma_f32 ...)
-//    without assembling operands: a pair is only ever formed where its halves are produced side by side (the x, y of a node
-//    record, two words of a rest-table row, the result of a pair operation), a scalar coefficient is splatted once and reused,
-//    and dot products and all per-element scalar chains read the halves as plain floats.
-//  * the rare paths stand behind wave-uniform tests and carry nothing through the common path: the first certifying snapshot
-//    is straight-line code and the sweeps of the plain iteration run only when some lane's snapshot is not clean; the start of an
-//    element with fewer than two pairs out of tolerance and the completion of a collapsed direction likewise.  A ballot only skips
-//    work that no lane needs: no lane's result depends on another lane.
+//  * the matrices of the decomposition (A, B = A V, V, the recomposition's t) are held BY ROWS for columns 0 and 1 (struct Mat:
+//    r[k] = (M[k][0], M[k][1]), a pair) with column 2 beside them.  Everything the common path does to columns 0 and 1 together is
+//    then one pair operation whose operands are pairs as they stand, one half splatted or the halves swapped - all operand
+//    selections of a packed instruction (op_sel), no moves: the Gram entries (s00, s11) and (s02, s12), the pair tests against
+//    column 2, (d0, d1) and (m00, m11) against a splat, the cofactors (c11, c00) and (c02, c12), B = A V0 row by row, the norms and
+//    the rotation <0, 1> (two pair operations per row), the polish with (t02, t12) one recip_rough chain on pairs, the certifying
+//    snapshot, the singular values of columns 0, 1 as one rsqrt chain on pairs, and t = B diag(g).  The matrix handed to the SVD
+//    arrives in that form for nothing: row c of it is the edges' (x, y) pairs against Qinv[c][j] splatted.  What is left scalar is
+//    meant to be: c0.c1, column 2's own entries, the closed form's per-element chain, the rotation's coefficients.  The
+//    recomposition's out[r] and the blend are pairs over (x, y) as the node records are, which needs V's columns 0, 1 as (rows 0,
+//    1): the one transposition of the common path.
+//  * the rare paths carry nothing through the common path: the first certifying snapshot is straight-line code and the sweeps of
+//    the plain iteration run only for lanes whose snapshot is not clean; the start of an element with fewer than two pairs out of
+//    tolerance and the completion of a collapsed direction likewise.  They run on columns (Col: rows 0, 1 as a pair, row 2; to_cols
+//    / from_cols), as rotations <0, 2> and <1, 2> want.  Each stands behind a plain per-lane test: the compiler's branch around a
+//    region no lane enters (s_cbranch_execz) skips it, and asks for no ballot in front.
 //
 // PIES_ROWS_SCALAR (or a host compiler) turns a pair into a struct of two floats: the same code in scalar instructions.  The
-// arithmetic compiles for the host (tests/cpp/tet_rows_example.cpp compares it with the oracle's bit for bit); a ballot is then the
-// lane's own predicate.  Used by k_layer only: k_tet, k_wave and the experiment variants keep tet_core.
+// arithmetic compiles for the host (tests/cpp/tet_rows_example.cpp compares it with the oracle's bit for bit).  Used by k_layer
+// only: k_tet, k_wave and the experiment variants keep tet_core.
 #pragma once
 #if defined(__HIP__)
 #include "dev_math.h"
@@ -44,7 +50,6 @@ PIES_ROWS_FN float rf_max(float a, float b) { return fmaxf(a, b); }
 PIES_ROWS_FN float rf_copysign(float a, float b) { return __builtin_copysignf(a, b); }
 PIES_ROWS_FN int rf_bits(float a) { return __float_as_int(a); }
 PIES_ROWS_FN float rf_float(int a) { return __int_as_float(a); }
-PIES_ROWS_FN bool any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }  // (wave-uniform)
 #else
 inline float rf_fma(float a, float b, float c) { return std::fmaf(a, b, c); }
 inline float rf_abs(float a) { return std::fabs(a); }
@@ -53,7 +58,6 @@ inline float rf_max(float a, float b) { return std::fmax(a, b); }
 inline float rf_copysign(float a, float b) { return std::copysign(a, b); }
 inline int rf_bits(float a) { int32_t i; std::memcpy(&i, &a, 4); return i; }
 inline float rf_float(int a) { float f; std::memcpy(&f, &a, 4); return f; }
-inline bool any_lane(bool p) { return p; }
 #endif
 
 // ---- a pair of rows ---------------------------------------------------------------------------------------------------------------
@@ -144,40 +148,114 @@ template <int P, int Q> PIES_ROWS_FN void rotate(Col (&b)[3], Col (&v)[3], const
   v[Q].p = rp_fma(sn2, vx.p, rp_mul(cs2, vy.p));
   v[Q].z = rf_fma(sn, vx.z, cs * vy.z);
 }
-// jacobi_pair<P, Q>: the test, and the rotation behind a wave-uniform branch
+// jacobi_pair<P, Q>: the test, and the rotation for the lanes that need it
 template <int P, int Q> PIES_ROWS_FN void test_pair(Col (&b)[3], Col (&v)[3]) {
   const float alpha = cdot(b[P], b[P]);
   const float beta = cdot(b[Q], b[Q]);
   const float gamma = cdot(b[P], b[Q]);
   const bool need = pair_needs(alpha, beta, gamma);
-  if (!any_lane(need)) return;
   if (need) rotate<P, Q>(b, v, alpha, beta, gamma);
 }
-// jacobi_polish
-PIES_ROWS_FN void polish(Col (&b)[3], Col (&v)[3], bool* guarded = nullptr) {
-  const float n0 = cdot(b[0], b[0]), n1 = cdot(b[1], b[1]), n2 = cdot(b[2], b[2]);
-  const float g01 = cdot(b[0], b[1]), g02 = cdot(b[0], b[2]), g12 = cdot(b[1], b[2]);
-  float t01 = g01 * recip_rough(n1 - n0), t02 = g02 * recip_rough(n2 - n0), t12 = g12 * recip_rough(n2 - n1);
+
+// ---- the common path on a 3x3 held BY ROWS for columns 0, 1 ----------------------------------------------------------------------
+// r[k] = (M[k][0], M[k][1]): columns 0 and 1 side by side, row by row; column 2 as a Col.  What the common path does to columns 0
+// and 1 together - their norms, their products with column 2, the one rotation <0, 1>, the polish, B = A V0 - is then a pair
+// operation whose operands are whole pairs, a half splatted or the two halves swapped: all of them operand selections of a packed
+// instruction.  The rare paths (rotations <0, 2>, <1, 2>, the completion) run on columns (to_cols / from_cols).
+struct Mat {
+  rp r[3];
+  Col c;
+};
+PIES_ROWS_FN rp rp_swap(rp a) { return rp_make(a.y, a.x); }
+PIES_ROWS_FN void to_cols(const Mat& m, Col (&c)[3]) {
+  c[0].p = rp_make(m.r[0].x, m.r[1].x); c[0].z = m.r[2].x;
+  c[1].p = rp_make(m.r[0].y, m.r[1].y); c[1].z = m.r[2].y;
+  c[2] = m.c;
+}
+PIES_ROWS_FN void from_cols(const Col (&c)[3], Mat& m) {
+  m.r[0] = rp_make(c[0].p.x, c[1].p.x);
+  m.r[1] = rp_make(c[0].p.y, c[1].p.y);
+  m.r[2] = rp_make(c[0].z, c[1].z);
+  m.c = c[2];
+}
+// cdot of columns: (c0.c0, c1.c1), c0.c1, (c0.c2, c1.c2); c2.c2 is cdot(m.c, m.c)
+PIES_ROWS_FN rp dot_self(const Mat& m) { return rp_fma(m.r[2], m.r[2], rp_fma(m.r[1], m.r[1], rp_mul(m.r[0], m.r[0]))); }
+PIES_ROWS_FN float dot_01(const Mat& m) { return rf_fma(m.r[2].x, m.r[2].y, rf_fma(m.r[1].x, m.r[1].y, m.r[0].x * m.r[0].y)); }
+PIES_ROWS_FN rp dot_with2(const Mat& m) {
+  return rp_fma(m.r[2], rp_splat(m.c.z), rp_fma(m.r[1], rp_splat(m.c.p.y), rp_mul(m.r[0], rp_splat(m.c.p.x))));
+}
+// pair_needs of (column 0, column 2) and (column 1, column 2): both sides as pairs, the comparisons per half
+PIES_ROWS_FN void pair_needs2(rp alpha, float beta, rp gamma, bool& n0, bool& n1) {
+  const rp lhs = rp_mul(gamma, gamma);
+  const rp rhs = rp_fma(rp_splat(kTol2), rp_mul(alpha, rp_splat(beta)), rp_splat(kTiny2));
+  n0 = lhs.x > rhs.x;
+  n1 = lhs.y > rhs.y;
+}
+// rsqrt_nr and recip_rough on both halves
+PIES_ROWS_FN rp rsqrt_nr2(rp x) {
+  rp y = rp_make(rf_float(0x5f3759df - (rf_bits(x.x) >> 1)), rf_float(0x5f3759df - (rf_bits(x.y) >> 1)));
+  const rp mhx = rp_neg(rp_mul(rp_splat(0.5f), x));
+  y = rp_mul(y, rp_fma(mhx, rp_mul(y, y), rp_splat(1.5f)));
+  y = rp_mul(y, rp_fma(mhx, rp_mul(y, y), rp_splat(1.5f)));
+  y = rp_mul(y, rp_fma(mhx, rp_mul(y, y), rp_splat(1.5f)));
+  return y;
+}
+PIES_ROWS_FN rp recip_rough2(rp x) {
+  const rp max_ = rp_neg(rp_make(rf_abs(x.x), rf_abs(x.y)));
+  rp y = rp_make(rf_float(0x7EF311C7 - (rf_bits(x.x) & 0x7fffffff)), rf_float(0x7EF311C7 - (rf_bits(x.y) & 0x7fffffff)));
+  y = rp_mul(y, rp_fma(max_, y, rp_splat(2.0f)));
+  y = rp_mul(y, rp_fma(max_, y, rp_splat(2.0f)));
+  return rp_make(rf_copysign(y.x, x.x), rf_copysign(y.y, x.y));
+}
+
+// jacobi_pair<0, 1> on rows: (alpha, beta) one pair chain, the rotation two pair operations per row of B and of V
+PIES_ROWS_FN void rotate01(Mat& b, Mat& v, const float alpha, const float beta, const float gamma) {
+  const float delta = beta - alpha;
+  const float g2 = gamma + gamma;
+  const float hw = rf_fma(delta, delta, g2 * g2);
+  const float h = hw * rsqrt_nr(hw);
+  const float c1 = h + rf_abs(delta);
+  const float s1 = delta < 0.0f ? -g2 : g2;
+  const float inv = rsqrt_nr(rf_fma(c1, c1, s1 * s1));
+  const rp cs = rp_mul(rp_make(c1, s1), rp_splat(inv));  // (cs, sn)
+  const rp sc = rp_make(-cs.y, cs.x);  // (-sn, cs): -(sn y) is (-sn) y, the sign of a product being the signs' product
+PIES_ROWS_UNROLL
+  for (int k = 0; k < 3; ++k) {  // column 0: cs x - sn y, column 1: sn x + cs y
+    b.r[k] = rp_fma(cs, rp_splat(b.r[k].x), rp_mul(sc, rp_splat(b.r[k].y)));
+    v.r[k] = rp_fma(cs, rp_splat(v.r[k].x), rp_mul(sc, rp_splat(v.r[k].y)));
+  }
+}
+PIES_ROWS_FN void test_pair01(Mat& b, Mat& v) {
+  const rp ab = dot_self(b);
+  const float gamma = dot_01(b);
+  const bool need = pair_needs(ab.x, ab.y, gamma);
+  if (need) rotate01(b, v, ab.x, ab.y, gamma);
+}
+// jacobi_polish on rows
+PIES_ROWS_FN void polish(Mat& b, Mat& v, bool* guarded = nullptr) {
+  const rp n01 = dot_self(b);
+  const float n2 = cdot(b.c, b.c);
+  const float g01 = dot_01(b);
+  const rp g2 = dot_with2(b);
+  float t01 = g01 * recip_rough(n01.y - n01.x);
+  const rp t2 = rp_mul(g2, recip_rough2(rp_sub(rp_splat(n2), n01)));  // (t02, t12)
+  float t02 = t2.x, t12 = t2.y;
   if (guarded) *guarded = !(rf_abs(t01) <= 3.0e38f) || !(rf_abs(t02) <= 3.0e38f) || !(rf_abs(t12) <= 3.0e38f);  // (the host test's statistics: equal norms, inf or NaN)
   if (!(rf_abs(t01) < 2.5e-4f)) t01 = 0.0f;  // (also NaN: equal norms)
   if (!(rf_abs(t02) < 2.5e-4f)) t02 = 0.0f;
   if (!(rf_abs(t12) < 2.5e-4f)) t12 = 0.0f;
-  const rp p01 = rp_splat(t01), p02 = rp_splat(t02), p12 = rp_splat(t12);
-  const rp m01 = rp_splat(-t01), m02 = rp_splat(-t02), m12 = rp_splat(-t12);
-  const Col x = b[0], y = b[1], z = b[2];
-  b[0].p = rp_fma(m02, z.p, rp_fma(m01, y.p, x.p));
-  b[0].z = rf_fma(-t02, z.z, rf_fma(-t01, y.z, x.z));
-  b[1].p = rp_fma(m12, z.p, rp_fma(p01, x.p, y.p));
-  b[1].z = rf_fma(-t12, z.z, rf_fma(t01, x.z, y.z));
-  b[2].p = rp_fma(p12, y.p, rp_fma(p02, x.p, z.p));
-  b[2].z = rf_fma(t12, y.z, rf_fma(t02, x.z, z.z));
-  const Col vx = v[0], vy = v[1], vz = v[2];
-  v[0].p = rp_fma(m02, vz.p, rp_fma(m01, vy.p, vx.p));
-  v[0].z = rf_fma(-t02, vz.z, rf_fma(-t01, vy.z, vx.z));
-  v[1].p = rp_fma(m12, vz.p, rp_fma(p01, vx.p, vy.p));
-  v[1].z = rf_fma(-t12, vz.z, rf_fma(t01, vx.z, vy.z));
-  v[2].p = rp_fma(p12, vy.p, rp_fma(p02, vx.p, vz.p));
-  v[2].z = rf_fma(t12, vy.z, rf_fma(t02, vx.z, vz.z));
+  const rp pm01 = rp_make(-t01, t01), m2 = rp_make(-t02, -t12);
+PIES_ROWS_UNROLL
+  for (int k = 0; k < 3; ++k) {  // x - t01 y - t02 z | y + t01 x - t12 z | z + t02 x + t12 y
+    const float bz = k == 0 ? b.c.p.x : k == 1 ? b.c.p.y : b.c.z, vz = k == 0 ? v.c.p.x : k == 1 ? v.c.p.y : v.c.z;
+    const rp bx = b.r[k], vx = v.r[k];
+    b.r[k] = rp_fma(m2, rp_splat(bz), rp_fma(pm01, rp_swap(bx), bx));
+    v.r[k] = rp_fma(m2, rp_splat(vz), rp_fma(pm01, rp_swap(vx), vx));
+    const float bn = rf_fma(t12, bx.y, rf_fma(t02, bx.x, bz)), vn = rf_fma(t12, vx.y, rf_fma(t02, vx.x, vz));
+    if (k == 0) { b.c.p.x = bn; v.c.p.x = vn; }
+    else if (k == 1) { b.c.p.y = bn; v.c.p.y = vn; }
+    else { b.c.z = bn; v.c.z = vn; }
+  }
 }
 
 // which paths an element took (the host test counts them; the device passes nullptr and the bookkeeping folds away)
@@ -187,15 +265,22 @@ struct Paths {
   int sweeps = 0;
 };
 
-// The decomposition A V = B of svd3: a[i] = column i of the matrix (= what svd3 calls A[i]).  s[i] = |b_i|, rs[i] = 1 / |b_i|.
-PIES_ROWS_FN void svd(const Col (&a)[3], Col (&b)[3], Col (&v)[3], float (&s)[3], float (&rs)[3], Paths* paths) {
-  const float s00 = cdot(a[0], a[0]), s11 = cdot(a[1], a[1]), s22 = cdot(a[2], a[2]);
-  const float s01 = cdot(a[0], a[1]), s02 = cdot(a[0], a[2]), s12 = cdot(a[1], a[2]);
-  const bool n01 = pair_needs(s00, s11, s01), n02 = pair_needs(s00, s22, s02), n12 = pair_needs(s11, s22, s12);
+// The decomposition A V = B of svd3 (column i of a = what svd3 calls A[i]).  sv = |b_i|, rsv = 1 / |b_i|: columns 0, 1 as a pair,
+// column 2.
+PIES_ROWS_FN void svd(const Mat& a, Mat& b, Mat& v, rp& sv01, float& sv2, rp& rsv01, float& rsv2, Paths* paths) {
+  const rp sd = dot_self(a);  // (s00, s11)
+  const float s22 = cdot(a.c, a.c);
+  const float s01 = dot_01(a);
+  const rp so = dot_with2(a);  // (s02, s12)
+  const float s00 = sd.x, s11 = sd.y, s02 = so.x, s12 = so.y;
+  const bool n01 = pair_needs(s00, s11, s01);
+  bool n02, n12;
+  pair_needs2(sd, s22, so, n02, n12);
   const int cnt = (n01 ? 1 : 0) + (n02 ? 1 : 0) + (n12 ? 1 : 0);
   // (straight-line: consumed only where cnt >= 2, where svd3 computes the same values)
   const float q = ((s00 + s11) + s22) * 0.333333343f;
-  const float d0 = s00 - q, d1 = s11 - q, d2 = s22 - q;
+  const rp d01 = rp_sub(sd, rp_splat(q));
+  const float d0 = d01.x, d1 = d01.y, d2 = s22 - q;
   const float p1 = rf_fma(s12, s12, rf_fma(s02, s02, s01 * s01));
   const float p2 = rf_fma(d0, d0, rf_fma(d1, d1, rf_fma(d2, d2, p1 + p1)));  // 6 p^2
   const bool closed = cnt >= 2 && p2 > 1.0e-30f && p2 < 1.0e16f;
@@ -210,75 +295,94 @@ PIES_ROWS_FN void svd(const Col (&a)[3], Col (&b)[3], Col (&v)[3], float (&s)[3]
 PIES_ROWS_UNROLL
     for (int k = 6; k >= 0; --k) c = rf_fma(c, x, kCos[k]);
     const float lam = q + rf_copysign((p + p) * c, r);
-    const float m00 = s00 - lam, m11 = s11 - lam, m22 = s22 - lam;
-    const float c00 = rf_fma(m11, m22, -(s12 * s12)), c11 = rf_fma(m00, m22, -(s02 * s02)), c22 = rf_fma(m00, m11, -(s01 * s01));
-    const float c01 = rf_fma(s02, s12, -(s01 * m22)), c02 = rf_fma(s01, s12, -(s02 * m11)), c12 = rf_fma(s01, s02, -(s12 * m00));
+    // the cofactors of S - lam: (m00, m11) one pair subtraction, (c11, c00) and (c02, c12) two pair operations each
+    const rp m01 = rp_sub(sd, rp_splat(lam));
+    const float m00 = m01.x, m11 = m01.y, m22 = s22 - lam;
+    const rp cd = rp_fma(m01, rp_splat(m22), rp_neg(rp_mul(so, so)));
+    const rp co = rp_fma(rp_splat(s01), rp_swap(so), rp_neg(rp_mul(so, rp_swap(m01))));
+    const float c00 = cd.y, c11 = cd.x, c22 = rf_fma(m00, m11, -(s01 * s01));
+    const float c01 = rf_fma(s02, s12, -(s01 * m22)), c02 = co.x, c12 = co.y;
     const float a0 = rf_abs(c00), a1 = rf_abs(c11), a2 = rf_abs(c22);
     const bool k0 = a0 >= a1 && a0 >= a2, k1 = !k0 && a1 >= a2;
     const float v0 = k0 ? c00 : (k1 ? c01 : c02), v1 = k0 ? c01 : (k1 ? c11 : c12), v2 = k0 ? c02 : (k1 ? c12 : c22);
     const float n2 = rf_fma(v2, v2, rf_fma(v1, v1, v0 * v0));
     const bool okn = n2 > kTiny2;
     const float in = rsqrt_nr(okn ? n2 : 1.0f);
-    const float nx = okn ? v0 * in : 0.0f, ny = okn ? v1 * in : 0.0f, nz = okn ? v2 * in : 1.0f;
+    const rp nm = rp_mul(rp_make(v0, v1), rp_splat(in));
+    const float nx = okn ? nm.x : 0.0f, ny = okn ? nm.y : 0.0f, nz = okn ? v2 * in : 1.0f;
     const float sg = rf_copysign(1.0f, nz);
     const float aa = -recip12(rf_abs(nz) + 1.0f) * sg;  // -1 / (sg + nz)
     const float bb = (nx * ny) * aa;
-    // V0 = [t1, t2, n]: the one place where a frame's rows 0, 1 are paired from per-element scalars
-    v[0].p = rp_make(rf_fma(sg * nx, nx * aa, 1.0f), sg * bb);
-    v[0].z = -(sg * nx);
-    v[1].p = rp_make(bb, rf_fma(ny, ny * aa, sg));
-    v[1].z = -ny;
-    v[2].p = rp_make(nx, ny);
-    v[2].z = nz;
+    const float sx = sg * nx;
+    // V0 = [t1, t2, n] by rows
+    v.r[0] = rp_make(rf_fma(sx, nx * aa, 1.0f), bb);
+    v.r[1] = rp_make(sg * bb, rf_fma(ny, ny * aa, sg));
+    v.r[2] = rp_make(-sx, -ny);
+    v.c.p = rp_make(nx, ny);
+    v.c.z = nz;
 PIES_ROWS_UNROLL
-    for (int i = 0; i < 3; ++i) {  // B = A V0, row pairs against splatted entries of V0
-      const float vi0 = v[i].p.x, vi1 = v[i].p.y, vi2 = v[i].z;
-      b[i].p = rp_fma(a[2].p, rp_splat(vi2), rp_fma(a[1].p, rp_splat(vi1), rp_mul(a[0].p, rp_splat(vi0))));
-      b[i].z = rf_fma(a[2].z, vi2, rf_fma(a[1].z, vi1, a[0].z * vi0));
+    for (int k = 0; k < 3; ++k) {  // B = A V0: row k of A splatted against the rows of V0; column 2 per entry
+      const float ak0 = a.r[k].x, ak1 = a.r[k].y, ak2 = k == 0 ? a.c.p.x : k == 1 ? a.c.p.y : a.c.z;
+      b.r[k] = rp_fma(rp_splat(ak2), v.r[2], rp_fma(rp_splat(ak1), v.r[1], rp_mul(rp_splat(ak0), v.r[0])));
+      const float bk = rf_fma(ak2, nz, rf_fma(ak1, ny, ak0 * nx));
+      if (k == 0) b.c.p.x = bk;
+      else if (k == 1) b.c.p.y = bk;
+      else b.c.z = bk;
     }
-    test_pair<0, 1>(b, v);
+    test_pair01(b, v);
     polish(b, v, paths ? &paths->polishGuard : nullptr);
   }
-  if (any_lane(!closed)) {  // rare: at most one pair out of tolerance (a rest state, an axis-aligned flat element), or p2 out of range
-    if (!closed) {
-      PIES_RARE_PATH();
+  if (!closed) {  // rare: at most one pair out of tolerance (a rest state, an axis-aligned flat element), or p2 out of range
+    PIES_RARE_PATH();
+    Col bc[3], vc[3];
+    to_cols(a, bc);
 PIES_ROWS_UNROLL
-      for (int i = 0; i < 3; ++i) {
-        b[i] = a[i];
-        v[i].p = rp_make(i == 0 ? 1.0f : 0.0f, i == 1 ? 1.0f : 0.0f);
-        v[i].z = i == 2 ? 1.0f : 0.0f;
-      }
-      if (n01) rotate<0, 1>(b, v, s00, s11, s01);
-      else if (n02) rotate<0, 2>(b, v, s00, s22, s02);
-      else if (n12) rotate<1, 2>(b, v, s11, s22, s12);
+    for (int i = 0; i < 3; ++i) {
+      vc[i].p = rp_make(i == 0 ? 1.0f : 0.0f, i == 1 ? 1.0f : 0.0f);
+      vc[i].z = i == 2 ? 1.0f : 0.0f;
     }
+    if (n01) rotate<0, 1>(bc, vc, s00, s11, s01);
+    else if (n02) rotate<0, 2>(bc, vc, s00, s22, s02);
+    else if (n12) rotate<1, 2>(bc, vc, s11, s22, s12);
+    from_cols(bc, b);
+    from_cols(vc, v);
   }
   // The first certifying snapshot, straight-line.  (An element with cnt == 0 has B = A: the snapshot recomputes s00, s11, s22 and the
   // three tests of above from the same operands - clean, with svd3's n = s - so it needs no case of its own.)
-  float n0 = cdot(b[0], b[0]), n1 = cdot(b[1], b[1]), n2 = cdot(b[2], b[2]);
+  rp n01_ = dot_self(b);
+  float n2_ = cdot(b.c, b.c);
   bool clean;
   {
-    const float g02 = cdot(b[0], b[2]), g12 = cdot(b[1], b[2]), g01 = cdot(b[0], b[1]);
-    const bool t02 = pair_needs(n0, n2, g02), t12 = pair_needs(n1, n2, g12), t01 = pair_needs(n0, n1, g01);
+    const rp g2 = dot_with2(b);
+    const float g01 = dot_01(b);
+    bool t02, t12;
+    pair_needs2(n01_, n2_, g2, t02, t12);
+    const bool t01 = pair_needs(n01_.x, n01_.y, g01);
     clean = !(int(t02) | int(t12) | int(t01));
   }
-  if (any_lane(!clean)) {  // rare: the sweeps of the plain iteration, for the lanes whose snapshot was not clean
-    if (!clean) {
-      PIES_RARE_PATH();
-      for (int sweep = 1;; ++sweep) {  // (sweep = the snapshot taken next; svd3's sweep 0 is the one above)
-        test_pair<0, 2>(b, v);
-        test_pair<1, 2>(b, v);
-        test_pair<0, 1>(b, v);
-        n0 = cdot(b[0], b[0]); n1 = cdot(b[1], b[1]); n2 = cdot(b[2], b[2]);  // (sweeps exhausted: these are svd3's recomputed norms)
-        if (sweep == kMaxSweeps) break;
-        const float g02 = cdot(b[0], b[2]), g12 = cdot(b[1], b[2]), g01 = cdot(b[0], b[1]);
-        const bool t02 = pair_needs(n0, n2, g02), t12 = pair_needs(n1, n2, g12), t01 = pair_needs(n0, n1, g01);
-        clean = !(int(t02) | int(t12) | int(t01));
-        if (paths) paths->sweeps = sweep;
-        if (clean) break;
-      }
-      if (paths) { paths->fallback = true; paths->exhausted = !clean; }
+  if (!clean) {  // rare: the sweeps of the plain iteration, for the lanes whose snapshot was not clean (on columns)
+    PIES_RARE_PATH();
+    Col bc[3], vc[3];
+    to_cols(b, bc);
+    to_cols(v, vc);
+    float n0 = n01_.x, n1 = n01_.y, n2 = n2_;
+    for (int sweep = 1;; ++sweep) {  // (sweep = the snapshot taken next; svd3's sweep 0 is the one above)
+      test_pair<0, 2>(bc, vc);
+      test_pair<1, 2>(bc, vc);
+      test_pair<0, 1>(bc, vc);
+      n0 = cdot(bc[0], bc[0]); n1 = cdot(bc[1], bc[1]); n2 = cdot(bc[2], bc[2]);  // (sweeps exhausted: these are svd3's recomputed norms)
+      if (sweep == kMaxSweeps) break;
+      const float g02 = cdot(bc[0], bc[2]), g12 = cdot(bc[1], bc[2]), g01 = cdot(bc[0], bc[1]);
+      const bool t02 = pair_needs(n0, n2, g02), t12 = pair_needs(n1, n2, g12), t01 = pair_needs(n0, n1, g01);
+      clean = !(int(t02) | int(t12) | int(t01));
+      if (paths) paths->sweeps = sweep;
+      if (clean) break;
     }
+    if (paths) { paths->fallback = true; paths->exhausted = !clean; }
+    from_cols(bc, b);
+    from_cols(vc, v);
+    n01_ = rp_make(n0, n1);
+    n2_ = n2;
   }
   if (paths) {
     paths->closedForm = closed;
@@ -286,14 +390,14 @@ PIES_ROWS_UNROLL
     paths->onePair = cnt == 1;
     paths->rangeOut = cnt >= 2 && !closed;
   }
-  const float nn[3] = {n0, n1, n2};
-PIES_ROWS_UNROLL
-  for (int i = 0; i < 3; ++i) {
-    const bool ok = nn[i] > kTiny2;
-    const float r = rsqrt_nr(ok ? nn[i] : 1.0f);
-    rs[i] = ok ? r : 0.0f;  // a collapsed direction: s = 0, handled by the recomposition
-    s[i] = nn[i] * rs[i];
-  }
+  // the singular values: columns 0, 1 as one pair chain (a collapsed direction: s = 0, handled by the recomposition)
+  const bool ok0 = n01_.x > kTiny2, ok1 = n01_.y > kTiny2, ok2 = n2_ > kTiny2;
+  const rp r01 = rsqrt_nr2(rp_make(ok0 ? n01_.x : 1.0f, ok1 ? n01_.y : 1.0f));
+  const float r2 = rsqrt_nr(ok2 ? n2_ : 1.0f);
+  rsv01 = rp_make(ok0 ? r01.x : 0.0f, ok1 ? r01.y : 0.0f);
+  rsv2 = ok2 ? r2 : 0.0f;
+  sv01 = rp_mul(n01_, rsv01);
+  sv2 = n2_ * rsv2;
 }
 
 // complete_t<K, I, J>: t[K] = sg * (u_I x u_J)
@@ -305,32 +409,38 @@ template <int K, int I, int J> PIES_ROWS_FN void complete(const Col (&b)[3], con
 }
 
 // svd3_recompose: out[r] = row r of U diag(snew) V^T as (columns 0, 1 | column 2)
-PIES_ROWS_FN void recompose(const Col (&b)[3], const Col (&v)[3], const float (&s)[3], const float (&rs)[3], const float (&snew)[3],
-                            Col (&out)[3], Paths* paths) {
-  const bool ok0 = s[0] > kTiny, ok1 = s[1] > kTiny, ok2 = s[2] > kTiny;
-  const float g0 = ok0 ? snew[0] * rs[0] : 0.0f;
-  const float g1 = ok1 ? snew[1] * rs[1] : 0.0f;
-  const float g2 = ok2 ? snew[2] * rs[2] : 0.0f;
-  Col t[3];
-  t[0].p = rp_mul(b[0].p, rp_splat(g0)); t[0].z = b[0].z * g0;
-  t[1].p = rp_mul(b[1].p, rp_splat(g1)); t[1].z = b[1].z * g1;
-  t[2].p = rp_mul(b[2].p, rp_splat(g2)); t[2].z = b[2].z * g2;
+PIES_ROWS_FN void recompose(const Mat& b, const Mat& v, const rp s01, const float s2, const rp rs01, const float rs2, const rp snew01,
+                            const float snew2, Col (&out)[3], Paths* paths) {
+  const bool ok0 = s01.x > kTiny, ok1 = s01.y > kTiny, ok2 = s2 > kTiny;
+  const rp gm = rp_mul(snew01, rs01);
+  const rp g01 = rp_make(ok0 ? gm.x : 0.0f, ok1 ? gm.y : 0.0f);
+  const float g2 = ok2 ? snew2 * rs2 : 0.0f;
+  Mat t;
+PIES_ROWS_UNROLL
+  for (int k = 0; k < 3; ++k) t.r[k] = rp_mul(b.r[k], g01);
+  t.c.p = rp_mul(b.c.p, rp_splat(g2));
+  t.c.z = b.c.z * g2;
   const int nbad = (ok0 ? 0 : 1) + (ok1 ? 0 : 1) + (ok2 ? 0 : 1);
-  if (any_lane(nbad == 1)) {  // rare: a flattened element
-    if (nbad == 1) {
-      PIES_RARE_PATH();
-      if (!ok0) complete<0, 1, 2>(b, rs, t, snew[0]);
-      else if (!ok1) complete<1, 2, 0>(b, rs, t, snew[1]);
-      else complete<2, 0, 1>(b, rs, t, snew[2]);
-    }
+  if (nbad == 1) {  // rare: a flattened element (on columns)
+    PIES_RARE_PATH();
+    Col bc[3], tc[3];
+    to_cols(b, bc);
+    to_cols(t, tc);
+    const float rs[3] = {rs01.x, rs01.y, rs2};
+    if (!ok0) complete<0, 1, 2>(bc, rs, tc, snew01.x);
+    else if (!ok1) complete<1, 2, 0>(bc, rs, tc, snew01.y);
+    else complete<2, 0, 1>(bc, rs, tc, snew2);
+    from_cols(tc, t);
   }
   if (paths) { paths->completed = nbad == 1; paths->twoCollapsed = nbad >= 2; }
-  out[0].p = rp_fma(rp_splat(t[2].p.x), v[2].p, rp_fma(rp_splat(t[1].p.x), v[1].p, rp_mul(rp_splat(t[0].p.x), v[0].p)));
-  out[0].z = rf_fma(t[2].p.x, v[2].z, rf_fma(t[1].p.x, v[1].z, t[0].p.x * v[0].z));
-  out[1].p = rp_fma(rp_splat(t[2].p.y), v[2].p, rp_fma(rp_splat(t[1].p.y), v[1].p, rp_mul(rp_splat(t[0].p.y), v[0].p)));
-  out[1].z = rf_fma(t[2].p.y, v[2].z, rf_fma(t[1].p.y, v[1].z, t[0].p.y * v[0].z));
-  out[2].p = rp_fma(rp_splat(t[2].z), v[2].p, rp_fma(rp_splat(t[1].z), v[1].p, rp_mul(rp_splat(t[0].z), v[0].p)));
-  out[2].z = rf_fma(t[2].z, v[2].z, rf_fma(t[1].z, v[1].z, t[0].z * v[0].z));
+  // V's columns 0, 1 as (rows 0, 1): the one transposition of the common path, two pair moves
+  const rp v0 = rp_make(v.r[0].x, v.r[1].x), v1 = rp_make(v.r[0].y, v.r[1].y);
+PIES_ROWS_UNROLL
+  for (int r = 0; r < 3; ++r) {
+    const float t0 = t.r[r].x, t1 = t.r[r].y, t2 = r == 0 ? t.c.p.x : r == 1 ? t.c.p.y : t.c.z;
+    out[r].p = rp_fma(rp_splat(t2), v.c.p, rp_fma(rp_splat(t1), v1, rp_mul(rp_splat(t0), v0)));
+    out[r].z = rf_fma(t2, v.c.z, rf_fma(t1, v.r[2].y, t0 * v.r[2].x));
+  }
 }
 
 // An element's rest constants as the projection reads them: Qinv's entries [0][j], [1][j] side by side (they multiply the same
@@ -361,40 +471,36 @@ template <class V4> PIES_ROWS_FN void tet_rows(V4& x1, V4& x2, V4& x3, V4& x4, c
   // a product takes e0[j] / e1[j] as the pair's low / high half on both rows)
   const rp p1 = rp_make(x1.x, x1.y), p2 = rp_make(x2.x, x2.y), p3 = rp_make(x3.x, x3.y), p4 = rp_make(x4.x, x4.y);
   const rp d[3] = {rp_sub(p2, p1), rp_sub(p3, p1), rp_sub(p4, p1)};
-  const float e0[3] = {d[0].x, d[1].x, d[2].x};
-  const float e1[3] = {d[0].y, d[1].y, d[2].y};
   const float e2[3] = {x2.z - x1.z, x3.z - x1.z, x4.z - x1.z};
-  Col A[3];
-  A[0].p = rp_add(rp_add(rp_mul(rp_splat(e0[0]), R.q0), rp_mul(rp_splat(e0[1]), R.q1)), rp_mul(rp_splat(e0[2]), R.q2));
-  A[1].p = rp_add(rp_add(rp_mul(rp_splat(e1[0]), R.q0), rp_mul(rp_splat(e1[1]), R.q1)), rp_mul(rp_splat(e1[2]), R.q2));
-  // (A[0].z, A[1].z) = e0[j], e1[j] against Qinv[2][j]: the edges' pairs as they are
-  const rp z01 = rp_add(rp_add(rp_mul(d[0], rp_splat(R.q20)), rp_mul(d[1], rp_splat(R.q21))), rp_mul(d[2], rp_splat(R.q22)));
-  A[0].z = z01.x;
-  A[1].z = z01.y;
-  A[2].p = rp_add(rp_add(rp_mul(rp_splat(e2[0]), R.q0), rp_mul(rp_splat(e2[1]), R.q1)), rp_mul(rp_splat(e2[2]), R.q2));
-  A[2].z = e2[0] * R.q20 + e2[1] * R.q21 + e2[2] * R.q22;
-  // det3_cm(F), F[c][r] = row c of A[r]
-  const float f00 = A[0].p.x, f10 = A[0].p.y, f20 = A[0].z, f01 = A[1].p.x, f11 = A[1].p.y, f21 = A[1].z, f02 = A[2].p.x, f12 = A[2].p.y,
-              f22 = A[2].z;
+  // row c of the matrix, columns 0, 1 = (F[c][0], F[c][1]): the edges' pairs as they are against Qinv[c][j] splatted (a half of a
+  // pair of the rest table for c = 0, 1); column 2 = e2[j] splatted against the table's pairs, and one scalar chain
+  Mat A;
+  A.r[0] = rp_add(rp_add(rp_mul(d[0], rp_splat(R.q0.x)), rp_mul(d[1], rp_splat(R.q1.x))), rp_mul(d[2], rp_splat(R.q2.x)));
+  A.r[1] = rp_add(rp_add(rp_mul(d[0], rp_splat(R.q0.y)), rp_mul(d[1], rp_splat(R.q1.y))), rp_mul(d[2], rp_splat(R.q2.y)));
+  A.r[2] = rp_add(rp_add(rp_mul(d[0], rp_splat(R.q20)), rp_mul(d[1], rp_splat(R.q21))), rp_mul(d[2], rp_splat(R.q22)));
+  A.c.p = rp_add(rp_add(rp_mul(rp_splat(e2[0]), R.q0), rp_mul(rp_splat(e2[1]), R.q1)), rp_mul(rp_splat(e2[2]), R.q2));
+  A.c.z = e2[0] * R.q20 + e2[1] * R.q21 + e2[2] * R.q22;
+  // det3_cm(F), F[c][i] = row c of column i
+  const float f00 = A.r[0].x, f10 = A.r[1].x, f20 = A.r[2].x, f01 = A.r[0].y, f11 = A.r[1].y, f21 = A.r[2].y, f02 = A.c.p.x, f12 = A.c.p.y,
+              f22 = A.c.z;
   const float detF = +f00 * (f11 * f22 - f21 * f12) - f10 * (f01 * f22 - f21 * f02) + f20 * (f01 * f12 - f11 * f02);
-  Col B[3], V[3];
-  float s[3], rs[3];
-  svd(A, B, V, s, rs, paths);
-  float sn[3];
-PIES_ROWS_UNROLL
-  for (int i = 0; i < 3; ++i) sn[i] = rf_min(rf_max(s[i], R.lo), R.hi);
+  Mat B, V;
+  rp s01, rs01;
+  float s2, rs2;
+  svd(A, B, V, s01, s2, rs01, rs2, paths);
+  float sn0 = rf_min(rf_max(s01.x, R.lo), R.hi), sn1 = rf_min(rf_max(s01.y, R.lo), R.hi), sn2 = rf_min(rf_max(s2, R.lo), R.hi);
   if (detF < 0.0f) {  // flip the smallest singular value (Constraints.cpp:106-108)
     int k = 0;
-    float m = s[0];
-    if (s[1] <= m) { k = 1; m = s[1]; }
-    if (s[2] <= m) { k = 2; }
-    sn[0] = (k == 0) ? -sn[0] : sn[0];
-    sn[1] = (k == 1) ? -sn[1] : sn[1];
-    sn[2] = (k == 2) ? -sn[2] : sn[2];
+    float m = s01.x;
+    if (s01.y <= m) { k = 1; m = s01.y; }
+    if (s2 <= m) { k = 2; }
+    sn0 = (k == 0) ? -sn0 : sn0;
+    sn1 = (k == 1) ? -sn1 : sn1;
+    sn2 = (k == 2) ? -sn2 : sn2;
   }
   if (paths) paths->flipped = detF < 0.0f;
   Col Fh[3];
-  recompose(B, V, s, rs, sn, Fh, paths);
+  recompose(B, V, s01, s2, rs01, rs2, rp_make(sn0, sn1), sn2, Fh, paths);
   // projected = (0, Fh row 0, Fh row 1, Fh row 2); pos += w * (proj - pos), x and y as a pair
   const float w = R.w;
   const rp w2 = rp_splat(w);

@@ -7,9 +7,10 @@ scatter and the barrier.
 The main loop's gather and the rare paths (the start of an element with fewer than two pairs out of tolerance, the rotating sweeps, the completion
 of a collapsed direction, the loop for classes larger than the workgroup) are told from the common one by a comment the
 sources emit under -DPIES_PATH_NOTES (dev_math.h: PIES_MAIN_TET_PATH, PIES_RARE_PATH); the tool compiles once with and once without it and reports
-both kernels' lengths, so that a difference made by the notes shows.
+both kernels' lengths, so that a difference made by the notes shows.  --dump writes the instructions along the path of the
+tet_rows.h kernel, block by block: where the moves of a source region stand.
 
-usage: python tools/layer_isa.py [--block 512] [--streamed] [--json profiles/rNN_layer_critical_path.json] [extra compiler flags]
+usage: python tools/layer_isa.py [--block 512] [--streamed] [--json profiles/rNN_layer_critical_path.json] [--dump path.s] [extra compiler flags]
        > profiles/rNN_layer_isa.txt"""
 import json
 import os
@@ -53,7 +54,7 @@ def basic_blocks(lines):
     blocks, cur, label, piece = [], None, "entry", 0
 
     def start(name):
-        b = {"name": name, "ops": [], "rare": False, "main": False, "branch": None}
+        b = {"name": name, "ops": [], "text": [], "rare": False, "main": False, "branch": None}
         blocks.append(b)
         return b
     cur = start(label)
@@ -72,6 +73,7 @@ def basic_blocks(lines):
             continue
         op = t.split()[0]
         cur["ops"].append(op)
+        cur["text"].append(t)
         if op.startswith(("s_cbranch", "s_branch")):
             cur["branch"] = (op, t.split()[1])
             piece += 1
@@ -151,7 +153,7 @@ def main_loop_path(blocks):
     return header, back, path, notes
 
 
-def report(txt, sym, title):
+def report(txt, sym, title, dump=None):
     lines, (vgprs, scratch, occupancy) = kernel_text(txt, sym)
     blocks = basic_blocks(lines)
     header, back, path, notes = main_loop_path(blocks)
@@ -175,6 +177,11 @@ def report(txt, sym, title):
     print("per colour step along the path: all %(all)d, VALU %(valu)d (moves %(moves)d, packed %(packed)d), scalar %(scalar)d, waits %(waits)d, memory %(memory)d"
           % total)
     print()
+    if dump:  # the instructions along the path, block by block: where the moves of a source region stand
+        with open(dump, "w") as f:
+            for i in path:
+                f.write("%s:\n" % blocks[i]["name"])
+                f.writelines("  %s\n" % t for t in blocks[i]["text"])
     return total, len(lines), (vgprs, scratch)
 
 
@@ -182,6 +189,7 @@ def main():
     argv = sys.argv[1:]
     block = int(take(argv, "--block", "512"))
     json_out = take(argv, "--json")
+    dump = take(argv, "--dump")
     dict_ = 0 if "--streamed" in argv else 1
     argv = [a for a in argv if a != "--streamed"]
     with tempfile.TemporaryDirectory() as tmp:
@@ -191,7 +199,7 @@ def main():
     for form, what in ((0, "tet_core (the form before tet_rows.h)"), (1, "tet_rows.h")):
         sym = "_ZN4pies7k_layerILi%dELi0ELi1ELb%dELi%dEEE" % (block, dict_, form)
         title = "k_layer<%d, 0, 1, %s, %d>, %s" % (block, "true" if dict_ else "false", form, what)
-        total, n_noted, regs = report(noted, sym, title)
+        total, n_noted, regs = report(noted, sym, title, dump if form == 1 else None)
         n_plain = len(kernel_text(plain, sym)[0])
         vg, sc = kernel_text(plain, sym)[1][:2]
         print("  (the product build of this kernel, without the notes: %d lines of ISA against %d with them; %s VGPRs, scratch %s)\n" % (n_plain, n_noted, vg, sc))
