@@ -279,6 +279,68 @@ def tet_A(x):
     return Qinv_cm, A
 
 
+# ---------------------------------------------------------------------------------------------------
+# shape and goal matching (ShapeMatchingConstraint.cpp:6-177): the group constraints of PD
+# ---------------------------------------------------------------------------------------------------
+def quat_mat(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def quat_mul(a, b):
+    return np.array([a[0] * b[0] - a[1:] @ b[1:], *(a[0] * b[1:] + b[0] * a[1:] + np.cross(a[1:], b[1:]))])
+
+
+def polar_rotation(F):
+    U, _, Vt = np.linalg.svd(F)
+    return U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+
+
+def shape_group(ids, r, im, w):
+    """:6-48.  r: material coordinates = the nodes' positions when the constraint is added; Qinv is formed here, once, with
+    the inverse masses of that moment, and the rotation starts at identity."""
+    r = np.asarray(r, np.float64)
+    rc = r - r.mean(0)
+    Q = (rc / np.asarray(im, np.float64)[:, None]).T @ rc
+    assert np.linalg.cond(Q) <= 50, np.linalg.cond(Q)
+    return dict(ids=np.asarray(ids), rc=rc, Qinv=np.linalg.inv(Q), q=np.array([1.0, 0, 0, 0]), w=float(w))
+
+
+def shape_project(c, x, im):
+    """:75-122.  Unweighted centroid, P with the CURRENT inverse masses, F = P Qinv, the stored quaternion refined towards the
+    rotation of F (it persists: c["q"] is updated), projected = R rc + centroid."""
+    x = np.asarray(x, np.float64)
+    cen = x.mean(0)
+    P = ((x - cen) / np.asarray(im, np.float64)[:, None]).T @ c["rc"]
+    F = P @ c["Qinv"]
+    q = c["q"]
+    for _ in range(100):
+        R = quat_mat(q)
+        omega = sum(np.cross(R[:, k], F[:, k]) for k in range(3)) * (1.0 / abs(sum(R[:, k] @ F[:, k] for k in range(3))) + 1e-9)
+        a = np.linalg.norm(omega)
+        if a < 1e-9:
+            break
+        q = quat_mul(np.array([np.cos(a / 2), *(np.sin(a / 2) * omega / a)]), q)
+        q /= np.linalg.norm(q)
+    c["q"] = q
+    R = quat_mat(q)
+    # the iteration converged on the polar rotation: neither its start nor its history can be observed in the result
+    assert np.abs(R - polar_rotation(F)).max() <= 1e-8, np.abs(R - polar_rotation(F)).max()
+    return c["rc"] @ R.T + cen
+
+
+def goal_group(ids, r, w):
+    """:124-137: the transform starts as the identity"""
+    return dict(ids=np.asarray(ids), r=np.asarray(r, np.float64), T=np.eye(4), w=float(w))
+
+
+def goal_project(c):
+    """:163-173: T (r, 1)"""
+    return c["r"] @ c["T"][:3, :3].T + c["T"][:3, 3]
+
+
 def pd_tick(o, S):
     """Solver.cpp:162-486 with floor contacts only (float64, dense direct solve)."""
     h = o["fixedTimestepSize"] / o["timeSubsteps"]
@@ -286,6 +348,8 @@ def pd_tick(o, S):
     pos, prev, vel, im = S["pos"], S["prev"], S["vel"], S["invMass"]
     n = len(pos)
     K = np.diag(1.0 / (im * h2))
+    for c in list(S.get("shape", ())) + list(S.get("goal", ())):  # A = B = I: w on the diagonal per membership
+        K[c["ids"], c["ids"]] += c["w"]
     for (i, tgt, w) in S["position"]:
         K[i, i] += w
     Ad = np.array([[0.5, -0.5], [-0.5, 0.5]])
@@ -322,6 +386,10 @@ def pd_tick(o, S):
                 for (ids, q, w, A) in S[name]:
                     p = tet_project(pos[ids], q, lo, hi, volume=vol)
                     f[ids] += w * (A.T @ p)
+            for c in S.get("shape", ()):
+                f[c["ids"]] += c["w"] * shape_project(c, pos[c["ids"]], im[c["ids"]])
+            for c in S.get("goal", ()):
+                f[c["ids"]] += c["w"] * goal_project(c)
             stat_p = []
             for i in statics:
                 p = pos[i].copy()
@@ -339,6 +407,28 @@ def pd_tick(o, S):
             pv = np.array([vel[i, 0], 0, vel[i, 2]])
             fr = 1.0 if np.linalg.norm(pv) < o["staticFrictionThreshold"] else o["friction"]
             vel[i] += -fr * pv
+
+
+def box_triangles(W, H, D):
+    """surface triangles of a lattice box, same generator order as the library (needed for the floor contacts)"""
+    gid = lambda i, j, k: k + D * (j + H * i)
+    tris = []
+    for i in range(W - 1):
+        for j in range(H - 1):
+            tris += [[gid(i, j, 0), gid(i + 1, j + 1, 0), gid(i + 1, j, 0)], [gid(i, j, 0), gid(i, j + 1, 0), gid(i + 1, j + 1, 0)],
+                     [gid(i, j, D - 1), gid(i + 1, j, D - 1), gid(i + 1, j + 1, D - 1)],
+                     [gid(i, j, D - 1), gid(i + 1, j + 1, D - 1), gid(i, j + 1, D - 1)]]
+    for i in range(W - 1):
+        for k in range(D - 1):
+            tris += [[gid(i, 0, k), gid(i + 1, 0, k), gid(i + 1, 0, k + 1)], [gid(i, 0, k), gid(i + 1, 0, k + 1), gid(i, 0, k + 1)],
+                     [gid(i, H - 1, k), gid(i + 1, H - 1, k + 1), gid(i + 1, H - 1, k)],
+                     [gid(i, H - 1, k), gid(i, H - 1, k + 1), gid(i + 1, H - 1, k + 1)]]
+    for j in range(H - 1):
+        for k in range(D - 1):
+            tris += [[gid(0, j, k), gid(0, j + 1, k + 1), gid(0, j + 1, k)], [gid(0, j, k), gid(0, j, k + 1), gid(0, j + 1, k + 1)],
+                     [gid(W - 1, j, k), gid(W - 1, j + 1, k), gid(W - 1, j + 1, k + 1)],
+                     [gid(W - 1, j, k), gid(W - 1, j + 1, k + 1), gid(W - 1, j, k + 1)]]
+    return np.array(tris)
 
 
 def make_loops():
@@ -376,24 +466,8 @@ def make_loops():
     rest = pos0.astype(np.float32).astype(np.float64)
     jit = rng.uniform(-0.03, 0.03, pos0.shape)
     vel0 = rng.uniform(-0.5, 0.5, pos0.shape)
-    # surface triangles of the box, same generator order as the library (needed for the floor contacts)
     gid = lambda i, j, k: k + D * (j + H * i)
-    tris = []
-    for i in range(W - 1):
-        for j in range(H - 1):
-            tris += [[gid(i, j, 0), gid(i + 1, j + 1, 0), gid(i + 1, j, 0)], [gid(i, j, 0), gid(i, j + 1, 0), gid(i + 1, j + 1, 0)],
-                     [gid(i, j, D - 1), gid(i + 1, j, D - 1), gid(i + 1, j + 1, D - 1)],
-                     [gid(i, j, D - 1), gid(i + 1, j + 1, D - 1), gid(i, j + 1, D - 1)]]
-    for i in range(W - 1):
-        for k in range(D - 1):
-            tris += [[gid(i, 0, k), gid(i + 1, 0, k), gid(i + 1, 0, k + 1)], [gid(i, 0, k), gid(i + 1, 0, k + 1), gid(i, 0, k + 1)],
-                     [gid(i, H - 1, k), gid(i + 1, H - 1, k + 1), gid(i + 1, H - 1, k)],
-                     [gid(i, H - 1, k), gid(i, H - 1, k + 1), gid(i + 1, H - 1, k + 1)]]
-    for j in range(H - 1):
-        for k in range(D - 1):
-            tris += [[gid(0, j, k), gid(0, j + 1, k + 1), gid(0, j + 1, k)], [gid(0, j, k), gid(0, j, k + 1), gid(0, j + 1, k + 1)],
-                     [gid(W - 1, j, k), gid(W - 1, j + 1, k), gid(W - 1, j + 1, k + 1)],
-                     [gid(W - 1, j, k), gid(W - 1, j + 1, k + 1), gid(W - 1, j, k + 1)]]
+    tris = box_triangles(W, H, D)
     o = dict(OPT, iterations=6)
     tetrec = []
     for t in tets:
@@ -403,7 +477,7 @@ def make_loops():
     S = dict(pos=(pos0 + jit).astype(np.float32).astype(np.float64), prev=(pos0 + jit).astype(np.float32).astype(np.float64),
              vel=vel0.astype(np.float32).astype(np.float64), radius=np.full(len(pos0), 0.475), invMass=np.ones(len(pos0)),
              position=[(i, rest[i].copy(), 2.0) for i in pins], distance=[], tet=tetrec, volume=list(tetrec),
-             triangles=np.array(tris))
+             triangles=tris)
     init = {k: S[k].copy() for k in ("pos", "vel")}
     traj = []
     for _ in range(4):
@@ -484,8 +558,133 @@ def make_ccd():
     np.savez(os.path.join(HERE, "point_triangle_ccd.npz"), args=np.array(cases), threshold=np.float32(0.1), expected=np.array(exp))
 
 
+# ---------------------------------------------------------------------------------------------------
+# shape / goal matching fixtures
+# ---------------------------------------------------------------------------------------------------
+H32 = np.float32(0.012)
+
+
+def inertia32(im):
+    """diag of Solver.cpp:179-182 the way fp32 code forms it: 1 / (invMass * h^2)"""
+    return (np.float32(1.0) / (np.asarray(im, np.float32) * (H32 * H32))).astype(np.float64)
+
+
+def rot_axis(axis, angle):
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
+
+
+def make_shape_projection():
+    """shape_projection.npz: isolated groups, one local/global iteration each (no gravity, no floor, zero velocity, h = 0.012):
+    A = B = I makes the global step one scalar equation per node, x_new = (m x + w p) / (m + w).  The group size decides how the
+    device's workgroup (256 lanes, four wavefronts) walks the group - below, at and above one wavefront and one workgroup, and
+    several strides - and the rotation how long lane 0 iterates; the two are independent, so sizes up to 65 take all four
+    rotations and the large ones one each (the file stays near the size of the largest fixture)."""
+    g = np.random.default_rng(20261019)  # own stream: the fixtures above do not change
+    tetra = 0.6 * np.array([[1.0, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]])
+    pyramid = 0.8 * np.array([[1.0, 0, 1], [1, 0, -1], [-1, 0, 1], [-1, 0, -1], [0, 1.2, 0]])
+    ANGLES = (0.0, 0.3, 1.5, 2.8)
+    plan = [(n, a, 0.0, 0.05) for n in (4, 5, 63, 64, 65) for a in ANGLES]
+    plan += [(255, 0.3, 0.0, 0.05), (256, 1.5, 0.0, 0.05), (257, 2.8, 0.0, 0.05), (600, 1.5, 0.0, 0.05)]
+    plan += [(4, 0.3, 100.0, 0.3), (65, 1.5, 100.0, 0.3), (257, 2.8, 100.0, 0.3)]  # far from the origin: the float centroid
+    off, R_, X_, IM_, W_, E_, meta = [0], [], [], [], [], [], []
+    for n, angle, far, noise in plan:
+        r = tetra if n == 4 else pyramid if n == 5 else g.uniform(-1, 1, (n, 3)) * [1.0, 0.8, 0.6]
+        d = g.normal(size=3)
+        r = (r + far * d / np.linalg.norm(d)).astype(np.float32)  # the nodes are added here
+        im = g.uniform(0.05, 0.2, n).astype(np.float32)
+        m = inertia32(im)
+        w = np.float32(np.median(m))
+        c = shape_group(np.arange(n), r, im, w)
+        r64 = r.astype(np.float64)
+        x = (c["rc"] * [1.2, 0.8, 1.05]) @ rot_axis(g.normal(size=3), angle).T + r64.mean(0) + 0.2 * g.normal(size=3)
+        x = (x + noise * g.normal(size=(n, 3))).astype(np.float32)
+        p = shape_project(c, x, im)
+        exp = (m[:, None] * x.astype(np.float64) + float(w) * p) / (m[:, None] + float(w))
+        off.append(off[-1] + n)
+        R_.append(r); X_.append(x); IM_.append(im); W_.append(w); E_.append(exp); meta.append((angle, far))
+    np.savez(os.path.join(HERE, "shape_projection.npz"), offsets=np.array(off), r=np.concatenate(R_), x=np.concatenate(X_),
+             invMass=np.concatenate(IM_), w=np.array(W_, np.float32), expected=np.concatenate(E_), angle_far=np.array(meta))
+
+
+def transform(axis, angle, scale, t):
+    """a goal transform as pies_set_goal_transform takes it: 16 floats, column-major"""
+    T = np.eye(4)
+    T[:3, :3] = scale * rot_axis(axis, angle)
+    T[:3, 3] = t
+    return T.T.reshape(16).astype(np.float32)
+
+
+def make_pd_groups():
+    """pd_groups_tiny.npz: the whole PD loop with group constraints.  Body 1: the 3x3x4 tet box of pd_tiny (strain + volume, w = 1,
+    surface triangles, bottom layer within the floor's contact thickness) with a shape group over its k >= 2 half and a goal over
+    its k = 0 cap.  Body 2: 120 loose nodes with four shape groups - two overlapping ranges, a random subset, and four nodes
+    taken from where those three overlap, so nodes belong to one, two, three and four groups.  Non-uniform inverse masses.  Six
+    ticks of three iterations; the goal's transform is set before tick 0 and changed before tick 2; before tick 3 every node's mass
+    is rewritten (factors 0.3 ... 3): from then on K and P use the new masses and Qinv stays what the constructor made it."""
+    g = np.random.default_rng(20261020)
+    W, H, D = 3, 3, 4
+    tr = np.array([0.0, 0.02, 0.0])
+    box, tets, _ = lattice(W, H, D, tr, 1.0)
+    nb, nl = len(box), 120
+    loose = g.uniform(0, 3, (nl, 3)) + [6.0, 2.0, 0.0]
+    rest = np.concatenate([box, loose]).astype(np.float32).astype(np.float64)  # where the nodes are added
+    n = nb + nl
+    im = np.concatenate([g.uniform(0.7, 1.4, nb), g.uniform(0.5, 2.0, nl)]).astype(np.float32)
+    gid = lambda i, j, k: k + D * (j + H * i)
+    cap = [gid(i, j, 0) for i in range(W) for j in range(H)]
+    half = [gid(i, j, k) for i in range(W) for j in range(H) for k in (2, 3)]
+    A, B = np.arange(nb, nb + 70), np.arange(nb + 40, nb + nl)
+    Cs = np.sort(g.choice(np.arange(nb, nb + nl), 50, replace=False))
+    common = [i for i in range(nb + 40, nb + 70) if i in set(Cs.tolist())]
+    import itertools
+    four = next(list(q) for q in itertools.combinations(common, 4)
+                if np.linalg.cond((lambda rc: (rc / im[list(q), None]).T @ rc)(rest[list(q)] - rest[list(q)].mean(0))) < 10)
+    groups = [(half, 3000.0), (A, 2500.0), (B, 4000.0), (Cs, 1500.0), (four, 5000.0)]
+    w_goal = 3000.0
+    member = np.zeros(n, int)
+    for ids, _w in groups:
+        member[np.asarray(ids)] += 1
+    assert (member == 3).sum() >= 5 and (member == 4).sum() == 4
+
+    o = dict(OPT, iterations=3)
+    tetrec = []
+    for t in tets:
+        q, Am = tet_A(rest[t])
+        tetrec.append((list(t), q.astype(np.float32), 1.0, Am))
+    pos0 = (rest + g.uniform(-0.08, 0.08, rest.shape) * np.r_[np.full(nb, 0.4), np.ones(nl)][:, None]).astype(np.float32)
+    vel0 = (g.uniform(-1, 1, rest.shape) * np.r_[np.full(nb, 0.5), np.ones(nl)][:, None]).astype(np.float32)
+    S = dict(pos=pos0.astype(np.float64), prev=pos0.astype(np.float64), vel=vel0.astype(np.float64), radius=np.full(n, 0.475),
+             invMass=im.astype(np.float64), position=[], distance=[], tet=tetrec, volume=list(tetrec), triangles=box_triangles(W, H, D),
+             shape=[shape_group(ids, rest[np.asarray(ids)], im[np.asarray(ids)], w) for ids, w in groups],
+             goal=[goal_group(cap, rest[cap], w_goal)])
+    T0 = transform([0.2, 1.0, 0.1], 0.10, 1.02, [0.05, 0.10, -0.03])
+    T2 = transform([1.0, 0.3, -0.5], -0.15, 0.97, [-0.04, 0.06, 0.08])
+    factors = g.uniform(0.3, 3.0, n)
+    im3 = (im * factors).astype(np.float32)
+    P, V = [], []
+    for t in range(6):
+        if t in (0, 2):
+            S["goal"][0]["T"] = (T0 if t == 0 else T2).astype(np.float64).reshape(4, 4).T
+        if t == 3:
+            S["invMass"] = im3.astype(np.float64)
+        pd_tick(o, S)
+        P.append(S["pos"].copy())
+        V.append(S["vel"].copy())
+    assert len({tuple(np.round(c["q"], 6)) for c in S["shape"]}) == len(groups)  # every group turned, each its own way
+    sizes = np.array([len(ids) for ids, _ in groups])
+    np.savez(os.path.join(HERE, "pd_groups_tiny.npz"), dims=np.array([W, H, D]), translation=tr, loose=rest[nb:].astype(np.float32),
+             invMass=im, pos=pos0, vel=vel0, iterations=3, group_ids=np.concatenate([np.asarray(ids) for ids, _ in groups]).astype(np.uint32),
+             group_offsets=np.concatenate([[0], np.cumsum(sizes)]), group_w=np.array([w for _, w in groups], np.float32),
+             goal_ids=np.array(cap, np.uint32), goal_w=np.float32(w_goal), goal_ticks=np.array([0, 2]), goal_transforms=np.stack([T0, T2]),
+             mass_tick=3, invMass_written=im3, expected_pos=np.array(P), expected_vel=np.array(V))
+
+
 if __name__ == "__main__":
     make_projections()
     make_loops()
     make_ccd()
+    make_shape_projection()
+    make_pd_groups()
     print("golden vectors written to", HERE)

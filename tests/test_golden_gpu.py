@@ -14,13 +14,19 @@ pies_set_rest), one tick - and is compared with the fp64 expectation at the tole
   distance / bend;
 * point-triangle CCD (Src/CollisionDetection.cpp:227-302): two-triangle scenes, the contact list (pies_get_tri_contacts)
   against the fp64 decisions;
-* the whole-loop PBD restatement (pbd_tiny_coll{0,1}.npz) tick by tick under schedule EXACT, pd_tiny.npz under PD.
+* PD group constraints (Src/ShapeMatchingConstraint.cpp:6-177): isolated shape groups (shape_projection.npz), one scalar equation
+  per node with the projection on the right-hand side, through k_pd_local_shape and the fp64 contribution slots;
+* the whole-loop PBD restatement (pbd_tiny_coll{0,1}.npz) tick by tick under schedule EXACT, pd_tiny.npz under PD
+  (test_pd_parity_gpu.py), pd_groups_tiny.npz - shape groups, a goal and a mass write on the live scene - under PD.
 """
 import importlib.util
 import os
 
 import numpy as np
 import pytest
+
+from test_oracle_golden import build_pd_groups, build_shape_scene, pd_groups_edits, shape_gate, shape_options, shape_records
+from test_pd_parity_gpu import record
 
 pytestmark = pytest.mark.gpu
 
@@ -258,6 +264,124 @@ def test_bend_projection_goldens_through_the_pd_local_step(pies):
         want = (m * x[k].astype(np.float64) + w * exp[k]) / (m + w)
         scale = max(1.0, np.abs(exp[k] - x[k]).max())
         assert np.abs(out[k] - want).max() <= 2e-4 * scale, k
+
+
+# ---- PD group constraints: shape and goal matching ----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def shape_reference(oracle):
+    """shape_projection.npz and what the oracle makes of it (one scene, one tick, shared by the variants below)"""
+    recs = shape_records()
+    o = oracle.OracleSolver(shape_options(oracle))
+    build_shape_scene(o, recs)
+    o.tick()
+    assert not o.failed
+    return recs, o.positions
+
+
+SHAPE_VARIANTS = {"default": {}, "rhs_kernel": {"PIES_PD_FUSE_RHS": "0"}, "rhs_fused": {"PIES_PD_FUSE_RHS": "1"},
+                  "cg_two_launch": {"PIES_PD_CG_SINGLE": "0"}, "cg_single": {"PIES_PD_CG_SINGLE": "1"},
+                  "no_graph": {"PIES_NO_GRAPH": "1"}, "renumber_flag": {}}
+
+
+@pytest.mark.parametrize("variant", list(SHAPE_VARIANTS))
+def test_shape_projection_goldens_through_the_pd_local_step(pies, tune, shape_reference, variant):
+    """k_pd_local_shape, one workgroup per group, and the fp64 contribution slots rhs_of_node adds: every isolated group of
+    shape_projection.npz (sizes below, at and above a wavefront and a workgroup, and 600; rotations up to 2.8 rad; groups at the
+    origin and 100 units away) in one scene on node ranges of their own, one tick, against the fp64 restatement
+    x_new = (m x + w p) / (m + w).  Gate per record: twice the oracle's own distance from the restatement, or the solve's fp32
+    noise.  The variants change who adds up the slots (k_pd_rhs or the CG's residual kernel), the CG form and the launch path; all
+    meet the same gate.  (renumber_flag: K of this scene is diagonal, so the library finds nothing to gain and keeps the host's
+    order - the variant holds that decision path to the gate; groups under a renumbering that does apply are in
+    test_pd_groups_tiny_scene_goldens[renumbered].)"""
+    recs, ora = shape_reference
+    for name, value in SHAPE_VARIANTS[variant].items():
+        tune(name, value)
+    g = pd_solver(pies)
+    if variant == "renumber_flag":
+        g.set_flag(pies.FLAG_RENUMBER_NODES, 1)
+    build_shape_scene(g, recs)
+    g.tick(1)
+    out = g.positions
+    assert not g.failed and g.pcg_health()["short_solves"] == 0 and np.isfinite(out).all()
+    assert g.count(pies.PD_CG_SINGLE) == (0 if variant == "cg_two_launch" else 1) and g.count(pies.NODES_RENUMBERED) == 0
+    g.close()
+    first, worst, by_size = 0, [], {}
+    for k, (r, x, im, w, exp) in enumerate(recs):
+        n = len(r)
+        d_ora = float(np.abs(ora[first:first + n] - exp).max())
+        assert d_ora <= shape_gate(x), (k, d_ora)  # (the oracle's own gate: a gate made of its distance needs it close)
+        gate = max(2.0 * d_ora, SOLVE_NOISE * max(float(np.abs(x).max()), float(np.abs(exp).max())))
+        err = float(np.abs(out[first:first + n] - exp).max())
+        worst.append((err / gate, k, n, err, gate))
+        by_size[n] = max(by_size.get(n, 0.0), err / gate)
+        first += n
+    for n, ratio in by_size.items():
+        record("golden_shape_projection[%s]" % variant, "error_over_gate_size_%d" % n, ratio, 1.0)
+    worst.sort(reverse=True)
+    print("shape matching [%s]: largest error / gate:" % variant, ["%.2f (record %d, n = %d)" % w[:3] for w in worst[:5]])
+    assert worst[0][0] <= 1.0, worst[:5]
+
+
+def build_pd_groups_shuffled(s, d, hid):
+    """build_pd_groups with the node ids of the two bodies shuffled together (fixture node i is host node hid[i]): the box from
+    raw nodes and containers, since createTetBox numbers its own"""
+    gm = golden_module()
+    W, Hh, D = (int(v) for v in d["dims"])
+    box, tets, _ = gm.lattice(W, Hh, D, d["translation"], 1.0)
+    rest = np.concatenate([box.astype(np.float32), d["loose"]])
+    n = len(rest)
+    at = np.empty_like(rest)
+    at[hid] = rest
+    im = np.empty(n, np.float32)
+    im[hid] = d["invMass"]
+    s.add_nodes_raw(at, radius=0.475, invMass=im)
+    s.add_tet(hid[tets].astype(np.uint32), 1.0, 0.8, 1.0)
+    s.add_volume(hid[tets].astype(np.uint32), 1.0, 1.0, 1.0)
+    s.add_triangles(hid[gm.box_triangles(W, Hh, D)].astype(np.uint32))
+    off = d["group_offsets"]
+    for k in range(len(off) - 1):
+        s.add_shape(hid[d["group_ids"][off[k]:off[k + 1]]].astype(np.uint32), float(d["group_w"][k]))
+    s.add_goal(hid[d["goal_ids"]].astype(np.uint32), float(d["goal_w"]))
+    for name in ("pos", "vel"):
+        a = np.empty_like(d[name])
+        a[hid] = d[name]
+        (s.set_velocities if name == "vel" else s.set_positions)(a)
+        if name == "pos":
+            s.set_prev_positions(a)
+
+
+@pytest.mark.parametrize("layout", ["plain", "renumbered"])
+def test_pd_groups_tiny_scene_goldens(pies, tune, layout):
+    """pd_groups_tiny.npz: the whole PD loop with shape groups (nodes in one to four of them: the fp64 slot loop of rhs_of_node), a
+    goal whose transform is set before tick 0 and again before tick 2, and pies_write_nodes(INV_MASS) on every node before tick 3 -
+    the rebuilt system takes the new masses into K and P and keeps each group's Qinv (the rebuild starts the rotations over from
+    the identity; the iteration converges, so that cannot show).  Tick by tick against the fp64 restatement at pd_tiny's gates.
+    renumbered: the two bodies' host ids shuffled together and 64-row chunks, so that the library does renumber these 156 nodes."""
+    d = load("pd_groups_tiny.npz")
+    n = len(d["pos"])
+    g = pies.Solver(pies.Options(solver=pies.PD, iterations=int(d["iterations"])), device=0)
+    g.set_pcg(1e-7, 256)  # (the written masses spread 40 : 1, see test_live_edits_pd_gpu.test_node_write)
+    if layout == "renumbered":
+        tune("PIES_CG_CHUNK_ROWS", "64")
+        g.set_flag(pies.FLAG_RENUMBER_NODES, 1)
+        hid = np.random.default_rng(3).permutation(n)
+        build_pd_groups_shuffled(g, d, hid)
+    else:
+        hid = np.arange(n)
+        build_pd_groups(g, d)
+    g.finalize()
+    assert g.count(pies.NODES_RENUMBERED) == (1 if layout == "renumbered" else 0)
+    assert g.count(pies.SHAPE) == len(d["group_w"]) and g.count(pies.GOAL) == 1
+    for t, (p, v) in enumerate(zip(d["expected_pos"], d["expected_vel"])):
+        pd_groups_edits(g, d, t, hid)
+        g.tick()
+        ep, ev = float(np.abs(g.positions[hid] - p).max()), float(np.abs(g.velocities[hid] - v).max())
+        record("golden_pd_groups_tiny[%s]" % layout, "positions", ep, 2e-4)
+        record("golden_pd_groups_tiny[%s]" % layout, "velocities", ev, 2e-4 / 0.012)
+        print("pd_groups_tiny [%s] tick %d: |dpos| %.3g |dvel| %.3g" % (layout, t, ep, ev))
+        assert ep <= 2e-4 and ev <= 2e-4 / 0.012, (t, ep, ev)
+    assert g.pcg_health()["short_solves"] == 0 and not g.failed
+    g.close()
 
 
 # ---- point-triangle CCD ----------------------------------------------------------------------------------------------------

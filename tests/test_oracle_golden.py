@@ -154,6 +154,99 @@ def test_pd_tiny_scene_against_fp64_restatement():
     assert o.count(O.STATICS) > 0  # the floor contacts were exercised
 
 
+# ---- shape and goal matching (ShapeMatchingConstraint.cpp) ----------------------------------------
+def shape_records():
+    """shape_projection.npz as a list of records (r, x, invMass, w, expected): isolated groups, one local/global iteration"""
+    d = load("shape_projection.npz")
+    off = d["offsets"]
+    return [(d["r"][a:b], d["x"][a:b], d["invMass"][a:b], float(d["w"][k]), d["expected"][a:b]) for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+
+def shape_gate(x):
+    """the PD tolerance of test_pd_parity_gpu.tol_for, scaled by the coordinates' size"""
+    return 1e-5 * max(1.0, float(np.abs(x).max())) + 2e-5
+
+
+def shape_options(mod):
+    """no gravity, the floor far below, no damping, one local/global iteration of one substep"""
+    return mod.Options(solver=mod.PD, iterations=1, timeSubsteps=1, fixedTimestepSize=0.012, gravity=0.0, floorHeight=-1.0e6, damping=0.0)
+
+
+def build_shape_scene(s, records):
+    """Every record on a node range of its own in one scene (an oracle or a device solver): the nodes are added at r, which makes
+    r the material coordinates of the group added over them, and then moved to x, at rest."""
+    first = 0
+    for r, x, im, w, _ in records:
+        s.add_nodes_raw(r, radius=0.01, invMass=im)
+        s.add_shape(np.arange(first, first + len(r), dtype=np.uint32), w)
+        first += len(r)
+    x = np.concatenate([rec[1] for rec in records])
+    s.set_positions(x)
+    s.set_prev_positions(x)
+    s.set_velocities(np.zeros_like(x))
+
+
+def test_shape_projection_against_fp64():
+    recs = shape_records()
+    o = O.OracleSolver(shape_options(O))
+    build_shape_scene(o, recs)
+    o.tick()
+    out = o.positions
+    first = 0
+    for k, (r, x, im, w, exp) in enumerate(recs):
+        err = float(np.abs(out[first:first + len(r)] - exp).max())
+        assert err <= shape_gate(x), (k, len(r), err, shape_gate(x))
+        first += len(r)
+    assert not o.failed
+
+
+def test_shape_projection_goldens_have_teeth():
+    """From the restatement alone: nearly every record moves its nodes by far more than the gate it is held to"""
+    recs = shape_records()
+    sharp = [float(np.abs(exp - x).max()) > 50 * shape_gate(x) for r, x, im, w, exp in recs]
+    assert sum(sharp) >= 0.9 * len(recs), sharp
+    assert sorted({len(r) for r, *_ in recs}) == [4, 5, 63, 64, 65, 255, 256, 257, 600]
+
+
+def build_pd_groups(s, d):
+    """pd_groups_tiny.npz's scene on an oracle or a device solver (the same calls)"""
+    W, H, D = (int(v) for v in d["dims"])
+    s.create_tet_box(W, H, D, translation=d["translation"], w=1.0, volume=True, triangles=True)
+    s.add_nodes_raw(d["loose"], radius=0.475)
+    s.set_inv_masses(d["invMass"])  # before the groups: Q is formed with these
+    off = d["group_offsets"]
+    for k in range(len(off) - 1):
+        s.add_shape(d["group_ids"][off[k]:off[k + 1]], float(d["group_w"][k]))
+    s.add_goal(d["goal_ids"], float(d["goal_w"]))
+    s.set_positions(d["pos"]); s.set_prev_positions(d["pos"]); s.set_velocities(d["vel"])
+
+
+def pd_groups_edits(s, d, t, host_id=None):
+    """the edits the fixture schedules before tick t (host_id: fixture node i is node host_id[i] of the scene)"""
+    for k, when in enumerate(d["goal_ticks"]):
+        if t == when:
+            s.set_goal_transform(0, d["goal_transforms"][k])
+    if t == int(d["mass_tick"]):
+        im = np.empty_like(d["invMass_written"])
+        im[np.arange(len(im)) if host_id is None else host_id] = d["invMass_written"]
+        s.set_inv_masses(im)
+
+
+def test_pd_groups_tiny_scene_against_fp64_restatement():
+    """Shape groups (nodes in up to four of them), a goal whose transform changes, and a mass write on the live scene: Qinv stays
+    what the constructor made it, K and P take the new masses.  pd_tiny's gate per tick."""
+    d = load("pd_groups_tiny.npz")
+    o = O.OracleSolver(solver=O.PD, iterations=int(d["iterations"]))
+    build_pd_groups(o, d)
+    for t, (p, v) in enumerate(zip(d["expected_pos"], d["expected_vel"])):
+        pd_groups_edits(o, d, t)
+        o.tick()
+        ep, ev = float(np.abs(o.positions - p).max()), float(np.abs(o.velocities - v).max())
+        print("pd_groups_tiny tick %d: |dpos| %.3g |dvel| %.3g" % (t, ep, ev))
+        assert ep <= 2e-4 and ev <= 2e-4 / 0.012, (t, ep, ev)
+    assert o.count(O.STATICS) > 0 and not o.failed  # the floor contacts were exercised
+
+
 def test_pd_rest_state_is_a_fixed_point_without_gravity():
     o = O.OracleSolver(solver=O.PD, iterations=3, gravity=0.0)
     o.create_tet_box(3, 3, 3, translation=(0, 5, 0), w=1.0)
