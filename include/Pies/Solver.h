@@ -402,13 +402,75 @@ public:
     _ck(pies_collide_props(_handle(), n, records.data(), impulse.data(), torque.data(), hits.data(), nullptr));
     _refreshPositions();
     for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
-    std::vector<PropReaction> out(n);
-    for (size_t k = 0; k < n; ++k) {
-      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
-      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
-      out[k].hits = hits[k];
+    return _reactions(impulse, torque, hits);
+  }
+  // Extension (pies_collide_field_props in pies_hip.h states the rule): rigid colliders of any shape.  A field is a signed distance
+  // function on a lattice in a local frame, negative inside: addField takes the host's samples (sample (i, j, k) at local
+  // origin + (i, j, k) * cell, stored at (k * ny + j) * nx + i: an analytic shape, a height field), addFieldFromTriMesh builds
+  // them on the device from a closed triangle mesh (brute force, once; margin >= the largest prop radius + the largest node
+  // radius + cell).  Both return the field's id; fields survive everything but clear().  A FieldProp places a field rigidly in
+  // the world; collideFieldProps pushes the nodes out of the props in the order given and returns what collideProps returns.
+  uint32_t addField(uint32_t nx, uint32_t ny, uint32_t nz, const glm::vec3& origin, float cell, const std::vector<float>& samples) {
+    if (samples.size() != size_t(nx) * ny * nz) throw std::runtime_error("Pies::Solver::addField: samples.size() != nx * ny * nz");
+    const uint32_t dims[3] = {nx, ny, nz};
+    const float o[3] = {origin[0], origin[1], origin[2]};
+    uint32_t id = 0;
+    _ck(pies_add_field(_handle(), dims, o, cell, samples.data(), &id));
+    return id;
+  }
+  uint32_t addFieldFromTriMesh(const std::vector<glm::vec3>& vertices, const std::vector<uint32_t>& triangleIndices, float cell,
+                               float margin) {
+    std::vector<float> p = _flatten(vertices);
+    uint32_t id = 0;
+    _ck(pies_add_field_tri_mesh(_handle(), static_cast<uint32_t>(vertices.size()), p.data(),
+                                static_cast<uint32_t>(triangleIndices.size() / 3), triangleIndices.data(), cell, margin, &id));
+    return id;
+  }
+  struct FieldProp : pies_field_prop_t {
+    // centre: the world position of the field's local (0, 0, 0); the frame is the world's and pivot = centre until set otherwise
+    FieldProp(uint32_t fieldId, const glm::vec3& centreInWorld, float inflation = 0.0f) {
+      std::memset(static_cast<pies_field_prop_t*>(this), 0, sizeof(pies_field_prop_t));
+      field = fieldId;
+      radius = inflation;
+      for (int k = 0; k < 3; ++k) centre[k] = pivot[k] = centreInWorld[k];
+      axes[0] = axes[4] = axes[8] = 1.0f;
     }
-    return out;
+    // unit and orthogonal: local axis j in world coordinates
+    FieldProp& setAxes(const glm::vec3& axis0, const glm::vec3& axis1, const glm::vec3& axis2) {
+      for (int k = 0; k < 3; ++k) {
+        axes[k] = axis0[k];
+        axes[3 + k] = axis1[k];
+        axes[6 + k] = axis2[k];
+      }
+      return *this;
+    }
+    FieldProp& setMotion(const glm::vec3& linear, const glm::vec3& angularVelocity, const glm::vec3& about) {
+      for (int k = 0; k < 3; ++k) {
+        velocity[k] = linear[k];
+        angular[k] = angularVelocity[k];
+        pivot[k] = about[k];
+      }
+      return *this;
+    }
+    FieldProp& setVelocity(const glm::vec3& linear) {
+      for (int k = 0; k < 3; ++k) velocity[k] = linear[k];
+      return *this;
+    }
+    FieldProp& setFriction(float f) {
+      friction = f;
+      return *this;
+    }
+  };
+  std::vector<PropReaction> collideFieldProps(const std::vector<FieldProp>& props) {
+    const uint32_t n = static_cast<uint32_t>(props.size());
+    std::vector<pies_field_prop_t> records(props.begin(), props.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n));
+    std::vector<uint32_t> hits(n);
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_collide_field_props(_handle(), n, records.data(), impulse.data(), torque.data(), hits.data(), nullptr));
+    _refreshPositions();
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
+    return _reactions(impulse, torque, hits);
   }
   void addFixedRegions(const std::vector<glm::mat4>& regionMatrices, float w) {
     std::vector<float> m = _flattenMats(regionMatrices);
@@ -564,6 +626,17 @@ private:
       h.position = h.hit ? glm::vec3(p[0] + t[i] * q[0], p[1] + t[i] * q[1], p[2] + t[i] * q[2]) : p;
     }
     return hits;
+  }
+
+  static std::vector<PropReaction> _reactions(const std::vector<float>& impulse, const std::vector<float>& torque,
+                                              const std::vector<uint32_t>& hits) {
+    std::vector<PropReaction> out(hits.size());
+    for (size_t k = 0; k < hits.size(); ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].hits = hits[k];
+    }
+    return out;
   }
 
   std::vector<SurfacePoint> _closestPoints(int target, uint32_t skin, const std::vector<glm::vec3>& points, float maxDistance, bool winding) {

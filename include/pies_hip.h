@@ -505,6 +505,74 @@ typedef struct pies_prop {
 } pies_prop_t;
 int pies_collide_props(pies_solver_t* s, uint32_t n_props, const pies_prop_t* props, float* out_impulse, float* out_torque,
                        uint32_t* out_hits, uint32_t* out_node_prop);
+/* EXTENSION: signed distance FIELDS and FIELD PROPS - rigid colliders of any shape.  A field is a signed distance function sampled
+ * on a regular lattice in a local frame: negative inside, positive outside.  It is either built once on the device from a closed
+ * triangle mesh (pies_add_field_tri_mesh) or supplied by the host (pies_add_field: an analytic shape, a height field).  A field
+ * prop is a rigid placement of a field that the host moves every frame; pies_collide_field_props pushes the nodes out of it and
+ * returns impulse and torque exactly as pies_collide_props does for the primitive shapes.
+ * The lattice: sample (i, j, k) of the dims lattice sits at local origin + (float)index * cell per axis (the product rounded, then
+ * the sum) and is stored at (k * dims[1] + j) * dims[0] + i.  Every dim is at least 2; a lattice has at most 2^24 samples.
+ * pies_add_field takes the host's samples as they are (a NaN sample is allowed: a node in a cell with one is not touched) and
+ * works on PIES_DEVICE_NONE handles too - only colliding needs the device.  PIES_ERR_INVALID: a NULL argument, a dim below 2, a
+ * non-finite origin, cell not finite or <= 0.  PIES_ERR_UNSUPPORTED: more than 2^24 samples, more than PIES_FIELD_MAX fields.
+ * pies_add_field_tri_mesh builds the samples on the device, everything in fp32:
+ *   lo, hi = the exact minimum and maximum of the vertices;  origin_j = lo_j - margin;
+ *   dims_j = max(2, (uint32_t)ceilf(((hi_j + margin) - origin_j) / cell) + 1);
+ *   dd = the smallest dd of the pair rule of pies_closest_points over the mesh's triangles at the sample's position (its rule, its
+ *        key and its tie-breaking, max_distance = +inf), w = the winding number there in pies_closest_points' two-level order (tiles
+ *        of 256 triangles);  sample = -sqrtf(dd) if |w| > 0.5, else sqrtf(dd).
+ * The launches are pies_closest_points' own, so the bits are its bits and two builds agree bit for bit.  The build is BRUTE FORCE
+ * over samples x triangles, once per field (DESIGN.md section 8f has timings); the mesh should be closed.  The scene is neither
+ * read nor changed.  A push ends where the lattice ends: give the build a margin of at least the largest prop radius + the
+ * largest node radius + cell.  PIES_ERR_INVALID: a NULL array, no vertices or triangles, a non-finite vertex, an index out of
+ * range, cell not finite or <= 0, margin negative or not finite.  PIES_ERR_UNSUPPORTED: more than 2^24 samples or 2^24 triangles,
+ * more than PIES_FIELD_MAX fields.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first).
+ * pies_get_field returns dims, origin, cell and - when samples is given - the samples (capacity in floats; too small:
+ * PIES_ERR_INVALID); every output may be NULL.  The library keeps a host copy of every field, so this needs no device.
+ * Lifetime: `field` (may be NULL) receives 0, 1, ...  Fields are assets, not scene state: they survive pies_finalize, scene edits
+ * and ticks (a device copy dropped by pies_finalize is staged again from the host copy at the next use) and end with pies_clear or
+ * pies_destroy; after pies_clear the ids are invalid and count from 0 again.
+ * The rule for one (node, field prop) pair, in fp32 without fused multiply-adds, with pies_collide_props' conventions: dot products
+ * summed left to right, a + b * t the product rounded then the sum, every test the positive form written (a NaN anywhere is "not
+ * touched"), a node with invMass == 0 never touched, the props applied in ascending index, each to the state the previous one
+ * left.  R = prop.radius + r.  sample(i, j, k) is the prop's field.
+ *   d = p - centre;  l_j = axis_j . d;  g_j = (l_j - origin_j) / cell;
+ *   in the lattice iff g_j >= 0 && g_j < (float)(dims_j - 1) for j = 0, 1, 2;  otherwise not touched;
+ *   i_j = (uint32_t)g_j;  f_j = g_j - (float)i_j;  s_abc = sample(i_0 + a, i_1 + b, i_2 + c);
+ *   m_bc = s_0bc + (s_1bc - s_0bc) * f_0;  m_c = m_0c + (m_1c - m_0c) * f_1;  phi = m_0 + (m_1 - m_0) * f_2;
+ *   touched iff phi < R;
+ *   G_0: the four differences s_1bc - s_0bc, interpolated over b by f_1, then over c by f_2 (the same x + (y - x) * f form);
+ *   G_1: s_a1c - s_a0c over a by f_0, then over c by f_2;  G_2: s_ab1 - s_ab0 over a by f_0, then over b by f_1;
+ *   GG = G.G;  nl = G / sqrtf(GG) if GG > 0, else (0, 1, 0);
+ *   n = (axis_0 * nl_0 + axis_1 * nl_1) + axis_2 * nl_2;  q = p + n * (R - phi).
+ * A touch is word for word pies_collide_props' touch (p = q, the previous position = q, then u, rel, vn, tang, v', the impulse j
+ * and its torque about pivot).  The push is ONE STEP along the gradient of the trilinear interpolant, not an exact projection: for a
+ * true distance field it lands on the R level set to first order (DESIGN.md section 8f has the measured error).  The outputs and
+ * their fixed two-level order of summation (tiles of 256 consecutive HOST node ids from 0.0f, then the tiles in ascending index,
+ * also under PIES_FLAG_RENUMBER_NODES; no atomics) are pies_collide_props'; so is everything else: the call runs on the handle's
+ * stream behind queued ticks, finalizes a changed scene first, synchronises before it returns, marks the host mirror stale and
+ * uploads no node state; captured graphs and pies_launch_counts are left as they were.
+ * PIES_ERR_INVALID: NULL props with n_props > 0, an unknown field id, a negative or non-finite radius, friction outside [0, 1], any
+ * non-finite member of the record.  PIES_ERR_UNSUPPORTED: n_props > PIES_FIELD_PROP_MAX.  n_props == 0 returns PIES_OK and touches
+ * nothing (out_node_prop is all PIES_PROP_NONE).  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first). */
+#define PIES_FIELD_MAX 64      /* fields per handle */
+#define PIES_FIELD_PROP_MAX 64 /* field props per call (one 64-bit word per tile, as for props) */
+int pies_add_field(pies_solver_t* s, const uint32_t dims[3], const float origin[3], float cell, const float* samples, uint32_t* field);
+int pies_add_field_tri_mesh(pies_solver_t* s, uint32_t n_vertices, const float* positions, uint32_t n_triangles,
+                            const uint32_t* tri_ids, float cell, float margin, uint32_t* field);
+int pies_get_field(pies_solver_t* s, uint32_t field, uint32_t dims[3], float origin[3], float* cell, float* samples, uint64_t capacity);
+typedef struct pies_field_prop {
+  uint32_t field;    /* id of pies_add_field / pies_add_field_tri_mesh */
+  float radius;      /* inflation of the zero level set, >= 0 */
+  float centre[3];   /* world position of the field's local (0, 0, 0) */
+  float axes[9];     /* local frame: axis j = axes[3 j .. 3 j + 2], unit and orthogonal (the host's duty) */
+  float velocity[3]; /* velocity of the pivot */
+  float angular[3];  /* angular velocity about the pivot */
+  float pivot[3];    /* point the angular velocity and the returned torque refer to */
+  float friction;    /* 0 .. 1: share of the tangential relative velocity a touch removes */
+} pies_field_prop_t;
+int pies_collide_field_props(pies_solver_t* s, uint32_t n_props, const pies_field_prop_t* props, float* out_impulse,
+                             float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:

@@ -49,6 +49,8 @@ NEAR_NONE = 0xFFFFFFFF  # PIES_NEAR_NONE: pies_closest_points found no candidate
 PROP_SPHERE, PROP_CAPSULE, PROP_BOX = 0, 1, 2  # pies_prop_t.shape
 PROP_NONE = 0xFFFFFFFF  # PIES_PROP_NONE: no prop touched the node
 PROP_MAX = 64  # PIES_PROP_MAX
+FIELD_MAX = 64  # PIES_FIELD_MAX: fields per handle
+FIELD_PROP_MAX = 64  # PIES_FIELD_PROP_MAX: field props per call
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -70,6 +72,7 @@ SYMBOLS = [
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
+    "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -163,6 +166,27 @@ class Prop(C.Structure):
         return p
 
 
+class FieldProp(C.Structure):
+    """pies_field_prop_t field for field: a rigid placement of a signed distance field (pies_collide_field_props)."""
+    _fields_ = [
+        ("field", C.c_uint32), ("radius", C.c_float), ("centre", C.c_float * 3), ("axes", C.c_float * 9),
+        ("velocity", C.c_float * 3), ("angular", C.c_float * 3), ("pivot", C.c_float * 3), ("friction", C.c_float),
+    ]
+
+    @classmethod
+    def make(cls, field, centre, axes=None, radius=0.0, velocity=(0, 0, 0), angular=(0, 0, 0), pivot=None, friction=0.0):
+        """centre: the world position of the field's local origin (0, 0, 0); axes: 3 x 3, row j the unit axis j of the local frame
+        (None: the world's); radius: inflation of the zero level set; pivot None: the centre"""
+        p = cls()
+        p.field, p.radius, p.friction = field, radius, friction
+        p.centre[:] = [float(x) for x in centre]
+        p.axes[:] = [float(x) for x in np.asarray(np.eye(3) if axes is None else axes, dtype=np.float32).reshape(9)]
+        p.velocity[:] = [float(x) for x in velocity]
+        p.angular[:] = [float(x) for x in angular]
+        p.pivot[:] = [float(x) for x in (centre if pivot is None else pivot)]
+        return p
+
+
 _lib = None
 
 
@@ -246,6 +270,10 @@ def load():
     sig["pies_raycast"] = [vp, i32, u32, u32, pf, pf, f32, u32, pu, pf, pf]
     sig["pies_closest_points"] = [vp, i32, u32, u32, pf, f32, pu, pf, pf, pf, pf]
     sig["pies_collide_props"] = [vp, u32, C.POINTER(Prop), pf, pf, pu, pu]
+    sig["pies_add_field"] = [vp, pu, pf, f32, pf, pu]
+    sig["pies_add_field_tri_mesh"] = [vp, u32, pf, u32, pu, f32, f32, pu]
+    sig["pies_get_field"] = [vp, u32, pu, pf, pf, pf, C.c_uint64]
+    sig["pies_collide_field_props"] = [vp, u32, C.POINTER(FieldProp), pf, pf, pu, pu]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -523,6 +551,49 @@ class Solver:
         self._ck(self._L.pies_collide_props(self._h, k, arr if k else None, _pf(imp) if reaction else None,
                                             _pf(tor) if reaction else None, _pu(hits) if reaction else None,
                                             _pu(who) if node_prop else None))
+        out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
+        return out or None
+
+    def add_field(self, samples, origin, cell):
+        """pies_add_field: a signed distance field from host samples shaped (nz, ny, nx) - sample [k, j, i] sits at the local
+        position origin + (i, j, k) * cell -, negative inside.  Returns the field id."""
+        v = np.ascontiguousarray(samples, dtype=np.float32)
+        if v.ndim != 3:
+            raise ValueError("add_field: samples must be shaped (nz, ny, nx)")
+        dims = _u32(v.shape[::-1])
+        o, out = _f32(origin).reshape(3), C.c_uint32()
+        self._ck(self._L.pies_add_field(self._h, _pu(dims), _pf(o), cell, _pf(v), C.byref(out)))
+        return out.value
+
+    def add_field_tri_mesh(self, vertices, triangles, cell, margin):
+        """pies_add_field_tri_mesh: the signed distance field of a closed triangle mesh, built on the device (brute force, once)
+        on a lattice that covers the mesh's bounding box grown by margin.  Returns the field id."""
+        v = _f32(vertices).reshape(-1, 3)
+        tri = _u32(triangles).reshape(-1, 3)
+        out = C.c_uint32()
+        self._ck(self._L.pies_add_field_tri_mesh(self._h, len(v), _pf(v), len(tri), _pu(tri), cell, margin, C.byref(out)))
+        return out.value
+
+    def get_field(self, field):
+        """pies_get_field: (samples float32 (nz, ny, nx), origin float32 (3), cell) of a field, from the library's host copy"""
+        dims, o, cell = np.zeros(3, np.uint32), np.zeros(3, np.float32), C.c_float()
+        self._ck(self._L.pies_get_field(self._h, field, _pu(dims), _pf(o), C.byref(cell), None, 0))
+        v = np.empty(tuple(int(x) for x in dims[::-1]), np.float32)
+        self._ck(self._L.pies_get_field(self._h, field, None, None, None, _pf(v), v.size))
+        return v, o, cell.value
+
+    def collide_field_props(self, props, reaction=True, node_prop=False):
+        """pies_collide_field_props: pushes the nodes out of the field props (a sequence of FieldProp, applied in order) where the
+        device holds them.  Returns what collide_props returns: (impulse, torque, hits) with reaction=True, followed by the last
+        prop that touched every node with node_prop=True; None when neither is asked for."""
+        props = list(props)
+        k = len(props)
+        arr = (FieldProp * max(k, 1))(*props)
+        imp, tor, hits = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)) if reaction else (None,) * 3
+        who = np.empty(self.count(NODES), np.uint32) if node_prop else None
+        self._ck(self._L.pies_collide_field_props(self._h, k, arr if k else None, _pf(imp) if reaction else None,
+                                                  _pf(tor) if reaction else None, _pu(hits) if reaction else None,
+                                                  _pu(who) if node_prop else None))
         out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
         return out or None
 

@@ -125,6 +125,7 @@ int pies_clear(pies_solver_t* s) {
   if (!s) return PIES_ERR_INVALID;
   s->h_skins.clear();
   s->skinDirty = false;
+  s->h_fields.clear();  // (their device copies go with free_device below)
   if (s->device != PIES_DEVICE_NONE) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);

@@ -36,6 +36,20 @@ template <class T> int upload(pies_solver* s, const std::vector<T>& h, T** d) {
   return PIES_OK;
 }
 
+// Frees the temporaries dev_alloc / upload have listed in s->dev.allocations since construction (trimesh.cpp, fields.cpp).
+struct Temporaries {
+  pies_solver* s;
+  size_t mark;
+  explicit Temporaries(pies_solver* solver) : s(solver), mark(solver->dev.allocations.size()) {}
+  ~Temporaries() {
+    if (s->dev.allocations.size() > mark) (void)hipStreamSynchronize(s->stream);
+    while (s->dev.allocations.size() > mark) {
+      (void)hipFree(s->dev.allocations.back());
+      s->dev.allocations.pop_back();
+    }
+  }
+};
+
 // The PD system matrix as CSR (pd_setup.cpp), in the numbering the host containers hold
 struct PdSystem {
   std::vector<uint32_t> rowptr, col;

@@ -32,6 +32,76 @@ int no_candidates(uint32_t n, const float* points, uint32_t* outTriangle, float*
 
 }  // namespace
 
+namespace pies {
+
+// The distance pass (any of dTri, dDistance, dUv, dPoint) and the winding pass (dWinding) of n points in HBM against target T: the
+// choice of the kernel variant, the shared buffers of s->ray (staged records, partial keys / tile sums) and the launches, batch
+// after batch on the handle's stream.  No synchronisation.  Shared with fields.cpp, whose lattice points never leave the device.
+int near_launch(pies_solver* s, const RayTarget& T, const float* dPoints, uint32_t n_points, float max_distance, uint32_t* dTri,
+                float* dDistance, float* dUv, float* dPoint, float* dWinding) {
+  RayBuffers& B = s->ray;
+  const bool distancePass = dTri || dDistance || dUv || dPoint;
+  if (!n_points || !T.nTris || (!distancePass && !dWinding)) return PIES_OK;
+
+  // ---- the variant of the distance pass ----
+  bool narrow = n_points <= kNearNarrowMaxDefault;
+  if (const char* e = tuning_env("PIES_NEAR_NARROW_MAX")) narrow = n_points <= static_cast<uint32_t>(std::max(0l, std::atol(e)));
+  if (const char* e = tuning_env("PIES_NEAR_VARIANT")) {
+    if (std::strcmp(e, "wide") == 0) narrow = false;
+    else if (std::strcmp(e, "narrow") == 0) narrow = true;
+    else return fail(s, PIES_ERR_INVALID, "pies_closest_points: PIES_NEAR_VARIANT must be wide or narrow");
+  }
+  const uint32_t nTiles = near_tiles(T.nTris);
+  uint32_t parts;
+  if (narrow) {
+    parts = ray_narrow_parts(T.nTris);
+  } else {
+    const uint32_t pointBlocks = (n_points + kNearBlock - 1) / kNearBlock;
+    parts = std::min(nTiles, std::max(1u, kNearWorkgroupsWanted / pointBlocks));
+    if (const char* e = tuning_env("PIES_NEAR_CHUNKS")) {
+      const long v = std::atol(e);
+      if (v < 1 || v > static_cast<long>(kNearMaxChunks)) return fail(s, PIES_ERR_INVALID, "pies_closest_points: PIES_NEAR_CHUNKS must be 1 .. 1024");
+      parts = static_cast<uint32_t>(v);  // (chunks beyond the last tile are empty: no candidate)
+    }
+  }
+  // points per batch: a multiple of the workgroup, its partial keys (8 bytes per part) and its tile sums (4 bytes per tile) bounded
+  const size_t perPoint = std::max<size_t>(distancePass ? sizeof(uint64_t) * parts : 0, dWinding ? sizeof(float) * nTiles : 0);
+  const uint32_t batch = static_cast<uint32_t>(
+      std::min<uint64_t>(n_points, std::max<uint64_t>(kNearBlock, kNearBatchBytes / perPoint / kNearBlock * kNearBlock)));
+
+  // ---- buffers ----
+  const size_t keys = (static_cast<size_t>(batch) * perPoint + sizeof(uint64_t) - 1) / sizeof(uint64_t);
+  if (B.partialCap < keys) {
+    B.partialCap = 0;
+    if (int rc = ray_grow(s, keys, &B.partial)) return rc;
+    B.partialCap = keys;
+  }
+  if (distancePass && !narrow && B.recordCap < T.nTris) {
+    B.recordCap = 0;
+    if (int rc = ray_grow(s, 3ull * T.nTris, &B.records)) return rc;
+    B.recordCap = T.nTris;
+  }
+
+  // ---- the launches: per batch the distance pass, then the winding pass (the stream orders their use of `partial`) ----
+  if (distancePass && !narrow) launch_ray_stage(s->stream, T, B.records);
+  for (uint32_t first = 0; first < n_points; first += batch) {
+    NearBatch P;
+    P.points = dPoints + 3ull * first;
+    P.n = std::min(batch, n_points - first);
+    P.maxDistance2 = max_distance * max_distance;
+    if (distancePass) {
+      if (narrow) launch_near_narrow(s->stream, T, P, B.partial);
+      else launch_near_wide(s->stream, B.records, T.nTris, P, parts, B.partial);
+      launch_near_resolve(s->stream, T, P, B.partial, parts, dTri ? dTri + first : nullptr, dDistance ? dDistance + first : nullptr,
+                          dUv ? dUv + 2ull * first : nullptr, dPoint ? dPoint + 3ull * first : nullptr);
+    }
+    if (dWinding) launch_near_winding(s->stream, T, P, reinterpret_cast<float*>(B.partial), dWinding + first);
+  }
+  return PIES_OK;
+}
+
+}  // namespace pies
+
 extern "C" {
 
 int pies_closest_points(pies_solver_t* s, int target, uint32_t skin, uint32_t n_points, const float* points, float max_distance,
@@ -58,34 +128,6 @@ int pies_closest_points(pies_solver_t* s, int target, uint32_t skin, uint32_t n_
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     return PIES_OK;
   }
-
-  // ---- the variant of the distance pass ----
-  bool narrow = n_points <= kNearNarrowMaxDefault;
-  if (const char* e = tuning_env("PIES_NEAR_NARROW_MAX")) narrow = n_points <= static_cast<uint32_t>(std::max(0l, std::atol(e)));
-  if (const char* e = tuning_env("PIES_NEAR_VARIANT")) {
-    if (std::strcmp(e, "wide") == 0) narrow = false;
-    else if (std::strcmp(e, "narrow") == 0) narrow = true;
-    else return fail(s, PIES_ERR_INVALID, "pies_closest_points: PIES_NEAR_VARIANT must be wide or narrow");
-  }
-  const uint32_t nTiles = near_tiles(T.nTris);
-  uint32_t parts;
-  if (narrow) {
-    parts = ray_narrow_parts(T.nTris);
-  } else {
-    const uint32_t pointBlocks = (n_points + kNearBlock - 1) / kNearBlock;
-    parts = std::min(nTiles, std::max(1u, kNearWorkgroupsWanted / pointBlocks));
-    if (const char* e = tuning_env("PIES_NEAR_CHUNKS")) {
-      const long v = std::atol(e);
-      if (v < 1 || v > static_cast<long>(kNearMaxChunks)) return fail(s, PIES_ERR_INVALID, "pies_closest_points: PIES_NEAR_CHUNKS must be 1 .. 1024");
-      parts = static_cast<uint32_t>(v);  // (chunks beyond the last tile are empty: no candidate)
-    }
-  }
-  // points per batch: a multiple of the workgroup, its partial keys (8 bytes per part) and its tile sums (4 bytes per tile) bounded
-  const size_t perPoint = std::max<size_t>(distancePass ? sizeof(uint64_t) * parts : 0, out_winding ? sizeof(float) * nTiles : 0);
-  const uint32_t batch = static_cast<uint32_t>(
-      std::min<uint64_t>(n_points, std::max<uint64_t>(kNearBlock, kNearBatchBytes / perPoint / kNearBlock * kNearBlock)));
-
-  // ---- buffers ----
   if (B.nearCap < n_points) {
     B.nearCap = 0;
     if (int rc = ray_grow(s, 3ull * n_points, &B.nearPoints)) return rc;
@@ -96,34 +138,11 @@ int pies_closest_points(pies_solver_t* s, int target, uint32_t skin, uint32_t n_
     if (int rc = ray_grow(s, n_points, &B.nearWinding)) return rc;
     B.nearCap = n_points;
   }
-  const size_t keys = (static_cast<size_t>(batch) * perPoint + sizeof(uint64_t) - 1) / sizeof(uint64_t);
-  if (B.partialCap < keys) {
-    B.partialCap = 0;
-    if (int rc = ray_grow(s, keys, &B.partial)) return rc;
-    B.partialCap = keys;
-  }
-  if (distancePass && !narrow && B.recordCap < T.nTris) {
-    B.recordCap = 0;
-    if (int rc = ray_grow(s, 3ull * T.nTris, &B.records)) return rc;
-    B.recordCap = T.nTris;
-  }
   HIP_TRY(s, hipMemcpyAsync(B.nearPoints, points, 3ull * n_points * sizeof(float), hipMemcpyHostToDevice, s->stream));
-
-  // ---- the launches: per batch the distance pass, then the winding pass (the stream orders their use of `partial`) ----
-  if (distancePass && !narrow) launch_ray_stage(s->stream, T, B.records);
-  for (uint32_t first = 0; first < n_points; first += batch) {
-    NearBatch P;
-    P.points = B.nearPoints + 3ull * first;
-    P.n = std::min(batch, n_points - first);
-    P.maxDistance2 = max_distance * max_distance;
-    if (distancePass) {
-      if (narrow) launch_near_narrow(s->stream, T, P, B.partial);
-      else launch_near_wide(s->stream, B.records, T.nTris, P, parts, B.partial);
-      launch_near_resolve(s->stream, T, P, B.partial, parts, B.nearTri + first, B.nearDistance + first, B.nearUv + 2ull * first,
-                          B.nearPoint + 3ull * first);
-    }
-    if (out_winding) launch_near_winding(s->stream, T, P, reinterpret_cast<float*>(B.partial), B.nearWinding + first);
-  }
+  if (int rc = near_launch(s, T, B.nearPoints, n_points, max_distance, distancePass ? B.nearTri : nullptr,
+                           distancePass ? B.nearDistance : nullptr, distancePass ? B.nearUv : nullptr,
+                           distancePass ? B.nearPoint : nullptr, out_winding ? B.nearWinding : nullptr))
+    return rc;
   HIP_TRY(s, hipGetLastError());
   if (out_triangle) HIP_TRY(s, hipMemcpyAsync(out_triangle, B.nearTri, n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
   if (out_distance) HIP_TRY(s, hipMemcpyAsync(out_distance, B.nearDistance, n_points * sizeof(float), hipMemcpyDeviceToHost, s->stream));

@@ -8,27 +8,25 @@
 //                  the workgroup): the touched lanes walk their touches again from the state they loaded - the same functions on
 //                  the same operands, the same bits - and for every prop that touched the tile the impulses and torques go through
 //                  LDS to six lanes, each of which adds one component in ascending node id (the touched lanes from the waves'
-//                  ballots: an untouched node would add 0, which changes no bit of a sum that started at +0).  No atomics.
+//                  ballots: an untouched node would add 0, which changes no bit of a sum that started at +0).  No atomics.  The
+//                  second pass is prop_tile_sums.h's, shared with k_field_collide.
 //  k_prop_fold     one workgroup per prop: the tile records, 256 tiles at a time through LDS, added in ascending tile index by six
 //                  lanes (a tile outside a prop's set adds 0; 256 tiles without one are passed over); a seventh adds the hit counts.
 // Built with -ffp-contract=off like the rest of the library: the arithmetic is the IEEE sequence written in prop_rule.h.
 #include "prop_kernels.h"
 
-#include "prop_rule.h"
+#include "prop_tile_sums.h"
 
 namespace pies {
 namespace {
 
-constexpr uint32_t kPropWaves = kPropTile / 64;
 constexpr uint32_t kPropWords = sizeof(pies_prop_t) / sizeof(uint32_t);
 static_assert(sizeof(pies_prop_t) == 120 && sizeof(pies_prop_t) % sizeof(uint32_t) == 0, "pies_prop_t is 30 words without padding");
 
 __global__ void __launch_bounds__(kPropTile) k_prop_collide(PropPass P) {
   __shared__ pies_prop_t props[PIES_PROP_MAX];
-  __shared__ uint64_t waveSet[kPropWaves];     // props that touched a node of the wave
-  __shared__ uint64_t waveBallot[kPropWaves];  // second pass: the wave's lanes the current prop touched
-  __shared__ float stage[6][kPropTile];        // ... and their impulse and torque
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x;
+  __shared__ PropTileLds lds;  // second pass
+  const uint32_t tid = threadIdx.x, tile = blockIdx.x;
   const uint32_t h = tile * kPropTile + tid;  // host id
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(P.props);
@@ -77,45 +75,13 @@ __global__ void __launch_bounds__(kPropTile) k_prop_collide(PropPass P) {
   if (P.nodeProp && live) P.nodeProp[h] = last;
   if (!P.tileMask) return;  // (uniform: a kernel argument)
 
-  // ---- the tile's set of props ----
-  uint64_t set = touchedBy;
-  for (int offset = 32; offset > 0; offset >>= 1) set |= __shfl_xor(set, offset);
-  if ((tid & 63u) == 0) waveSet[wave] = set;
-  __syncthreads();
-  set = 0;
-  for (uint32_t w = 0; w < kPropWaves; ++w) set |= waveSet[w];
-  if (tid == 0) P.tileMask[tile] = set;
-  if (!set) return;  // (uniform: every lane read the same words)
-
-  // ---- second pass: the tile's sums, prop after prop in the set ----
+  // ---- second pass: the tile's set of props and its sums (prop_tile_sums.h) ----
   PropNode N = N0;
-  for (uint32_t k = 0; k < P.nProps; ++k) {
-    if (!((set >> k) & 1ull)) continue;  // (uniform)
-    const bool touched = (touchedBy >> k) & 1ull;
-    if (touched) {
-      V3 n, q;
-      PropTouch T;
-      (void)prop_contact(props[k], N.p, N.r, n, q);  // the touch of the first pass, once more
-      prop_respond(props[k], n, q, N, T);
-      stage[0][tid] = T.impulse.x, stage[1][tid] = T.impulse.y, stage[2][tid] = T.impulse.z;
-      stage[3][tid] = T.torque.x, stage[4][tid] = T.torque.y, stage[5][tid] = T.torque.z;
-    }
-    const uint64_t ballot = __builtin_amdgcn_ballot_w64(touched);
-    if ((tid & 63u) == 0) waveBallot[wave] = ballot;
-    __syncthreads();
-    float* record = P.tileSums + (static_cast<size_t>(tile) * P.nProps + k) * kPropSumWords;
-    if (tid < 6) {
-      float sum = 0.0f;
-      for (uint32_t w = 0; w < kPropWaves; ++w)
-        for (uint64_t m = waveBallot[w]; m; m &= m - 1) sum = sum + stage[tid][w * 64 + __builtin_ctzll(m)];
-      record[tid] = sum;
-    } else if (tid == 6) {
-      uint32_t hits = 0;
-      for (uint32_t w = 0; w < kPropWaves; ++w) hits += __builtin_popcountll(waveBallot[w]);
-      reinterpret_cast<uint32_t*>(record)[6] = hits;
-    }
-    __syncthreads();  // the stage and the ballots are free for the next prop
-  }
+  prop_tile_sums(lds, P.tileMask, P.tileSums, P.nProps, touchedBy, [&](uint32_t k, PropTouch& T) {
+    V3 n, q;
+    (void)prop_contact(props[k], N.p, N.r, n, q);  // the touch of the first pass, once more
+    prop_respond(props[k], n, q, N, T);
+  });
 }
 
 __global__ void __launch_bounds__(kPropTile) k_prop_fold(const uint64_t* __restrict__ tileMask, const float* __restrict__ tileSums,

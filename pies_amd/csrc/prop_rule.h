@@ -1,6 +1,6 @@
 // The rule of pies_collide_props for one (node, prop) pair, as include/pies_hip.h states it and tests/test_props.py restates it in
-// numpy.  Included by prop_kernels.hip only; everything is the IEEE sequence written (-ffp-contract=off), every test the positive
-// form, so a NaN anywhere is "not touched".
+// numpy.  Included by .hip files only (prop_respond also answers for the field props, field_rule.h); everything is the IEEE
+// sequence written (-ffp-contract=off), every test the positive form, so a NaN anywhere is "not touched".
 #pragma once
 #include "../../include/pies_hip.h"
 #include "dev_math.h"

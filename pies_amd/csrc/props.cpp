@@ -2,6 +2,8 @@
 // them and hand back the reaction per prop.  Host side only: argument checks, the buffers (RayBuffers, solver_state.h) and the two
 // launches (prop_kernels.h).  The edit goes to dev.nd.pos / prev / vel - the state every schedule and both solvers start a substep
 // from - outside the captured substep: no graph, no schedule and no launch count changes.
+// prop_open_pass / prop_close_pass - the reaction's buffers, the fold, the stale marks and the copies out - are shared with
+// pies_collide_field_props (fields.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -38,6 +40,64 @@ const char* prop_fault(const pies_prop_t& p) {
 
 }  // namespace
 
+namespace pies {
+
+// The part of a pass over the nodes that does not depend on what the props are: node arrays, numbering and the reaction's buffers.
+int prop_open_pass(pies_solver* s, uint32_t nProps, bool reaction, bool nodeProp, PropPass* out) {
+  RayBuffers& B = s->ray;
+  const uint32_t n = s->dev.nd.n, tiles = prop_tiles(n);
+  if (!B.propOut)
+    if (int rc = ray_grow(s, static_cast<size_t>(PIES_PROP_MAX) * kPropSumWords, &B.propOut)) return rc;
+  if (reaction && B.propTileCap < tiles) {
+    B.propTileCap = 0;
+    if (int rc = ray_grow(s, tiles, &B.propTileMask)) return rc;
+    B.propTileCap = tiles;
+  }
+  const size_t records = static_cast<size_t>(tiles) * nProps;
+  if (reaction && B.propSumCap < records) {
+    B.propSumCap = 0;
+    if (int rc = ray_grow(s, records * kPropSumWords, &B.propTileSums)) return rc;
+    B.propSumCap = records;
+  }
+  if (nodeProp && B.propNodeCap < n) {
+    B.propNodeCap = 0;
+    if (int rc = ray_grow(s, n, &B.propNodeProp)) return rc;
+    B.propNodeCap = n;
+  }
+  PropPass P;
+  P.nd = s->dev.nd;
+  P.inv = s->dev.d_nodeInv;
+  P.nProps = nProps;
+  P.tileMask = reaction ? B.propTileMask : nullptr;
+  P.tileSums = reaction ? B.propTileSums : nullptr;
+  P.nodeProp = nodeProp ? B.propNodeProp : nullptr;
+  *out = P;
+  return PIES_OK;
+}
+
+// After the collide launch of pass P: the fold, the stale marks, the copies out and the synchronisation.
+int prop_close_pass(pies_solver* s, const PropPass& P, float* out_impulse, float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop) {
+  RayBuffers& B = s->ray;
+  const bool reaction = P.tileMask != nullptr;
+  const uint32_t n = P.nd.n, n_props = P.nProps;
+  if (reaction) launch_prop_fold(s->stream, P, B.propOut);
+  HIP_TRY(s, hipGetLastError());
+  s->stale |= 7u;  // positions, previous positions and velocities: the host mirror is older than HBM (nothing is uploaded)
+  float folded[PIES_PROP_MAX * kPropSumWords];
+  if (reaction) HIP_TRY(s, hipMemcpyAsync(folded, B.propOut, n_props * kPropSumWords * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  if (out_node_prop) HIP_TRY(s, hipMemcpyAsync(out_node_prop, B.propNodeProp, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  for (uint32_t k = 0; reaction && k < n_props; ++k) {
+    const float* f = folded + k * kPropSumWords;
+    if (out_impulse) std::memcpy(out_impulse + 3ull * k, f, 3 * sizeof(float));
+    if (out_torque) std::memcpy(out_torque + 3ull * k, f + 3, 3 * sizeof(float));
+    if (out_hits) std::memcpy(out_hits + k, f + 6, sizeof(uint32_t));
+  }
+  return PIES_OK;
+}
+
+}  // namespace pies
+
 extern "C" {
 
 int pies_collide_props(pies_solver_t* s, uint32_t n_props, const pies_prop_t* props, float* out_impulse, float* out_torque,
@@ -65,55 +125,15 @@ int pies_collide_props(pies_solver_t* s, uint32_t n_props, const pies_prop_t* pr
     return PIES_OK;
   }
 
-  // ---- buffers ----
-  RayBuffers& B = s->ray;
-  const uint32_t tiles = prop_tiles(n);
-  if (!B.propRecords) {
-    if (int rc = ray_grow(s, PIES_PROP_MAX, &B.propRecords)) return rc;
-    if (int rc = ray_grow(s, static_cast<size_t>(PIES_PROP_MAX) * kPropSumWords, &B.propOut)) return rc;
-  }
-  if (reaction && B.propTileCap < tiles) {
-    B.propTileCap = 0;
-    if (int rc = ray_grow(s, tiles, &B.propTileMask)) return rc;
-    B.propTileCap = tiles;
-  }
-  const size_t records = static_cast<size_t>(tiles) * n_props;
-  if (reaction && B.propSumCap < records) {
-    B.propSumCap = 0;
-    if (int rc = ray_grow(s, records * kPropSumWords, &B.propTileSums)) return rc;
-    B.propSumCap = records;
-  }
-  if (out_node_prop && B.propNodeCap < n) {
-    B.propNodeCap = 0;
-    if (int rc = ray_grow(s, n, &B.propNodeProp)) return rc;
-    B.propNodeCap = n;
-  }
-  HIP_TRY(s, hipMemcpyAsync(B.propRecords, props, n_props * sizeof(pies_prop_t), hipMemcpyHostToDevice, s->stream));
-
-  // ---- the launches ----
   PropPass P;
-  P.nd = s->dev.nd;
-  P.inv = s->dev.d_nodeInv;
+  if (int rc = prop_open_pass(s, n_props, reaction, out_node_prop != nullptr, &P)) return rc;
+  RayBuffers& B = s->ray;
+  if (!B.propRecords)
+    if (int rc = ray_grow(s, PIES_PROP_MAX, &B.propRecords)) return rc;
+  HIP_TRY(s, hipMemcpyAsync(B.propRecords, props, n_props * sizeof(pies_prop_t), hipMemcpyHostToDevice, s->stream));
   P.props = B.propRecords;
-  P.nProps = n_props;
-  P.tileMask = reaction ? B.propTileMask : nullptr;
-  P.tileSums = reaction ? B.propTileSums : nullptr;
-  P.nodeProp = out_node_prop ? B.propNodeProp : nullptr;
   launch_prop_collide(s->stream, P);
-  if (reaction) launch_prop_fold(s->stream, P, B.propOut);
-  HIP_TRY(s, hipGetLastError());
-  s->stale |= 7u;  // positions, previous positions and velocities: the host mirror is older than HBM (nothing is uploaded)
-  float folded[PIES_PROP_MAX * kPropSumWords];
-  if (reaction) HIP_TRY(s, hipMemcpyAsync(folded, B.propOut, n_props * kPropSumWords * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  if (out_node_prop) HIP_TRY(s, hipMemcpyAsync(out_node_prop, B.propNodeProp, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  for (uint32_t k = 0; reaction && k < n_props; ++k) {
-    const float* f = folded + k * kPropSumWords;
-    if (out_impulse) std::memcpy(out_impulse + 3ull * k, f, 3 * sizeof(float));
-    if (out_torque) std::memcpy(out_torque + 3ull * k, f + 3, 3 * sizeof(float));
-    if (out_hits) std::memcpy(out_hits + k, f + 6, sizeof(uint32_t));
-  }
-  return PIES_OK;
+  return prop_close_pass(s, P, out_impulse, out_torque, out_hits, out_node_prop);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "pair_kernels.h"
 #include "skin_kernels.h"
 #include "ray_kernels.h"
+#include "field_kernels.h"
 
 namespace pies {
 
@@ -178,6 +179,15 @@ struct NodeOrder {
   bool active() const { return !order.empty(); }
 };
 
+// A signed distance field (pies_add_field, pies_add_field_tri_mesh): the host copy pies_get_field reads and the device copy is
+// staged from.  Sample (i, j, k) at (k * dims[1] + j) * dims[0] + i.
+struct HostField {
+  uint32_t dims[3];
+  float origin[3];
+  float cell;
+  std::vector<float> samples;
+};
+
 // Device buffers of pies_raycast.  free_device drops them, so the triangle list never outlives the scene or the node numbering
 // it was built from; every buffer grows on demand and a handle that never casts a ray holds none.
 struct RayBuffers {
@@ -208,6 +218,10 @@ struct RayBuffers {
   size_t propSumCap = 0;               // (tile, prop) records
   uint32_t* propNodeProp = nullptr;    // per host id: the last prop that touched the node
   size_t propNodeCap = 0;              // nodes
+  // pies_collide_field_props (fields.cpp) shares the reaction's buffers above; its records and the device copies of the fields
+  // it has met (nullptr: not staged - the host copy in pies_solver::h_fields is staged again at the next use)
+  FieldPropRecord* fieldRecords = nullptr;    // PIES_FIELD_PROP_MAX records
+  float* fieldSamples[PIES_FIELD_MAX] = {};
 };
 
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
@@ -308,6 +322,7 @@ struct pies_solver {
   std::vector<uint32_t> h_triangles;  // 3 per triangle
   std::vector<uint32_t> h_lines;
   std::vector<pies::HostSkin> h_skins;  // extension: embedded surface meshes (pies_add_skin)
+  std::vector<pies::HostField> h_fields;  // extension: signed distance fields (pies_add_field*); assets: only pies_clear drops them
   uint32_t constraintId = 0;
 
   bool sceneDirty = true;    // topology/rest data changed: rebuild plans + upload everything
@@ -405,7 +420,8 @@ bool build_layer_plan(pies_solver* s);
 // skin.cpp : device records of the skins (no-ops without skins); skin_free_device forgets them (free_device, pies_clear)
 int skin_upload(pies_solver* s);
 void skin_free_device(pies_solver* s);
-// raycast.cpp : forgets the buffers of pies_raycast, pies_closest_points and pies_collide_props (free_device)
+// raycast.cpp : forgets the buffers of pies_raycast, pies_closest_points, pies_collide_props and pies_collide_field_props, the
+// fields' device copies included (free_device)
 void ray_free_device(pies_solver* s);
 // raycast.cpp, shared with nearest.cpp : replaces a buffer of s->ray (ray_free_device frees it); the triangles of a checked
 // (target, skin) of pies_raycast at the positions the device holds, a skin's vertices evaluated on the stream first
@@ -417,6 +433,14 @@ template <class T> int ray_grow(pies_solver* s, size_t count, T** d) {
   return rc;
 }
 int ray_open_target(pies_solver* s, int target, uint32_t skin, pies::RayTarget* out);
+// nearest.cpp, shared with fields.cpp : the distance and winding launches of pies_closest_points for n points in HBM (each output
+// may be nullptr); no synchronisation
+int near_launch(pies_solver* s, const pies::RayTarget& T, const float* dPoints, uint32_t n, float maxDistance, uint32_t* dTri,
+                float* dDistance, float* dUv, float* dPoint, float* dWinding);
+// props.cpp, shared with fields.cpp : the reaction's buffers of s->ray for n nodes and nProps props, filled into P; then, after the
+// collide launch, the fold, the stale marks, the copies out, the synchronisation
+int prop_open_pass(pies_solver* s, uint32_t nProps, bool reaction, bool nodeProp, pies::PropPass* P);
+int prop_close_pass(pies_solver* s, const pies::PropPass& P, float* outImpulse, float* outTorque, uint32_t* outHits, uint32_t* outNodeProp);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of

@@ -29,20 +29,6 @@ const char* check_mesh(uint32_t nv, const float* positions, uint32_t nt, const u
   return nullptr;
 }
 
-// Frees the temporaries dev_alloc / upload (device_util.h) have listed in s->dev.allocations since construction.
-struct Temporaries {
-  pies_solver* s;
-  size_t mark;
-  explicit Temporaries(pies_solver* solver) : s(solver), mark(solver->dev.allocations.size()) {}
-  ~Temporaries() {
-    if (s->dev.allocations.size() > mark) (void)hipStreamSynchronize(s->stream);
-    while (s->dev.allocations.size() > mark) {
-      (void)hipFree(s->dev.allocations.back());
-      s->dev.allocations.pop_back();
-    }
-  }
-};
-
 // The winding numbers of lattice L's cell centres; the mesh has passed check_mesh, the handle has a device.
 int winding_on_device(pies_solver* s, uint32_t nv, const float* positions, uint32_t nt, const uint32_t* tri, const VoxelLattice& L,
                       float* winding, uint8_t* inside) {
