@@ -134,7 +134,7 @@ def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-_IDS_PER = {POSITION: 1, DISTANCE: 2, TET: 4, VOLUME: 4, BEND: 4, TRIANGLES: 3, LINES: 1}
+_IDS_PER = {POSITION: 1, DISTANCE: 2, TET: 4, VOLUME: 4, BEND: 4, TRIANGLES: 3, LINES: 1, STATICS: 1}
 _REST_PER = {DISTANCE: 1, TET: 9, VOLUME: 9, BEND: 1}
 
 

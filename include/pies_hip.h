@@ -586,8 +586,8 @@ int pies_get_tri_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, ui
  * cells of the class), out[5..7] = triangles listed per class. */
 int pies_get_tri_grid_stats(pies_solver_t* s, uint32_t out[8]);
 /* PIES_FLAG_PD_NODE_CONTACTS: the node-node contacts of the last PD substep as (i, j) pairs of host ids (ids: 2 x count), in the
- * order the friction loop ran them (ascending pair key).  ids may be NULL to query the count; synchronises.  The reference keeps
- * them in Solver::_collisions (Solver.h), filled by _parallelComputeCollisions (Solver.cpp:509-637). */
+ * order the friction loop ran them (ascending pair key, taken over host ids).  ids may be NULL to query the count; synchronises.
+ * The reference keeps them in Solver::_collisions (Solver.h), filled by _parallelComputeCollisions (Solver.cpp:509-637). */
 int pies_get_node_contacts(pies_solver_t* s, uint32_t* ids, uint32_t capacity, uint32_t* count);
 /* Node-node pairs resolved by the PBD collision pass since the last call (statistics). */
 int pies_collision_pairs(pies_solver_t* s, uint64_t* pairs);

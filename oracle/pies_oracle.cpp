@@ -1994,7 +1994,7 @@ void ora_set(ora_solver* s, int what, const float* in) {
     else { n.invMass = in[i]; s->pdDirty = true; }
   }
 }
-// constraint node ids, flattened; type as in ora_permute, 7 = triangles, 8 = lines
+// constraint node ids, flattened; type as in ora_permute, 7 = triangles, 8 = lines, 10 = floor contacts
 void ora_get_ids(ora_solver* s, int type, uint32_t* out) {
   size_t k = 0;
   auto dump = [&](auto& v) { for (auto& c : v) for (uint32_t id : c.nodeIds) out[k++] = id; };
@@ -2006,6 +2006,7 @@ void ora_get_ids(ora_solver* s, int type, uint32_t* out) {
     case 4: dump(s->bendCons); break;
     case 7: for (auto& t : s->triangles) for (uint32_t id : t) out[k++] = id; break;
     case 8: for (uint32_t id : s->lines) out[k++] = id; break;
+    case 10: for (auto& c : s->staticCollisions) out[k++] = c.nodeId; break;  // the last substep's floor contacts, in list order
   }
 }
 // per-constraint rest data: distance -> target (1), tet/volume -> Qinv as glm column-major (9)

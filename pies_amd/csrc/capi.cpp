@@ -261,9 +261,12 @@ int pies_get_pcg_health(pies_solver_t* s, uint64_t* short_solves, uint64_t* solv
   return PIES_OK;
 }
 
-// The contacts of the last substep as (a, b) pairs of device ids, a < b, in the order the friction pass ran them (ascending pair key)
+// The contacts of the last substep as (a, b) pairs of device ids, a < b, in the order the friction pass ran them (ascending pair key
+// of the host's ids)
 static int nc_download(pies_solver* s, std::vector<uint32_t>* pairs, uint32_t* count) {
   const NodeContactArrays& C = s->dev.nc;
+  const bool perm = C.hostId != nullptr && s->nodeOrder.order.size() == C.n;
+  auto host = [&](uint32_t i) { return perm ? s->nodeOrder.order[i] : i; };
   std::vector<uint32_t> cnt(C.n);
   HIP_TRY(s, hipSetDevice(s->device));
   HIP_TRY(s, hipMemcpyAsync(cnt.data(), C.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
@@ -279,7 +282,7 @@ static int nc_download(pies_solver* s, std::vector<uint32_t>* pairs, uint32_t* c
   for (uint32_t i = 0; i < C.n; ++i)
     for (uint32_t k = 0; k < std::min(cnt[i], C.cap); ++k) {
       const uint32_t j = part[static_cast<size_t>(i) * C.cap + k];
-      if (i < j) list.push_back({pair_mix(i, j), static_cast<uint64_t>(i) << 32 | j});
+      if (i < j) list.push_back({pair_mix(host(i), host(j)), static_cast<uint64_t>(i) << 32 | j});
     }
   std::sort(list.begin(), list.end());
   pairs->resize(2 * list.size());

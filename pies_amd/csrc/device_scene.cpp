@@ -468,6 +468,12 @@ int nc_build(pies_solver* s) {
   if (int rc = upload(s, adj, &adjD)) return rc;
   C.adjPtr = adjPtrD;
   C.adj = adjD;
+  C.hostId = nullptr;
+  if (s->nodeOrder.active() && s->nodeOrder.order.size() == n) {  // renumbered: the pair key stays the host's (pd_contact_kernels.h)
+    uint32_t* hostIdD = nullptr;
+    if (int rc = upload(s, s->nodeOrder.order, &hostIdD)) return rc;
+    C.hostId = hostIdD;
+  }
   if (int rc = dev_alloc(s, static_cast<size_t>(n) * C.cap, &C.part)) return rc;
   if (int rc = dev_alloc(s, n, &C.cnt, true)) return rc;
   for (int b = 0; b < 2; ++b)

@@ -2,7 +2,7 @@
 //
 // Once per substep, after k_pd_predict: the node grid of the PBD pass is built from the predicted positions (launch_hash_build)
 // and every node's lane lists its contact partners - nodes that share a cell, overlap, are not both pinned and are not joined by
-// an element - in ascending order of the pair key (pair_mix below).  The list feeds the diagonal of the system (w once per
+// an element - in ascending order of the pair key (pair_mix below, over the host's ids).  The list feeds the diagonal of the system (w once per
 // contact), the right-hand side of every local step (w * projected, summed in list order) and the friction loop of
 // Solver.cpp:398-428, executed in ascending pair-key order by rounds: a pair runs when it is the next unprocessed pair of both its
 // nodes.  No float atomics anywhere: the results are the same bit for bit from run to run.
@@ -33,10 +33,12 @@ struct NodeContactArrays {
   uint32_t* cur[2];           // n: the friction pass's cursors into the lists (ping-pong between rounds)
   uint32_t* ctl;              // [r]: round r - 1 left a pair unprocessed; [kNcDeepest]
   const uint32_t* flags;      // the node grid's failure word (kNcOverflowFlag: a list was cut short, the friction pass is skipped)
+  const uint32_t* hostId;     // n: the host's id of device node i (nullptr: the device holds the host's numbering)
 };
 
 // 64-bit mix of the pair {i < j} (murmur3's finaliser over i << 32 | j, the mix of the PBD pair order's key): a bijection, so no
-// two pairs tie
+// two pairs tie.  Always taken over the HOST's ids (NodeContactArrays::hostId): the friction order, and with it the velocities, do
+// not depend on whether pies_finalize renumbered the nodes
 __host__ __device__ inline uint64_t pair_mix(uint32_t i, uint32_t j) {
   uint64_t k = (static_cast<uint64_t>(i < j ? i : j) << 32) | (i < j ? j : i);
   k ^= k >> 33; k *= 0xff51afd7ed558ccdull;

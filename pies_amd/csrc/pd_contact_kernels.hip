@@ -16,6 +16,9 @@ namespace pies {
 
 constexpr int kNcBlock = 256;
 
+// the host's id of device node i < C.n (the pair key and the roles a, b of a pair are the host's: pd_contact_kernels.h)
+PIES_DEV uint32_t nc_host(const NodeContactArrays& C, uint32_t i) { return C.hostId ? C.hostId[i] : i; }
+
 PIES_DEV bool nc_joined(const NodeContactArrays& C, uint32_t i, uint32_t j) {  // binary search of node i's element neighbours
   uint32_t lo = C.adjPtr[i], hi = C.adjPtr[i + 1];
   while (lo < hi) {
@@ -76,11 +79,12 @@ __global__ void __launch_bounds__(kNcBlock) k_nc_detect(HashArrays H, NodeContac
       atomicOr(&H.counters[kCounterFlags], kNcOverflowFlag);
       c = C.cap;
     }
-    for (uint32_t a = 1; a < c; ++a) {  // ascending pair key (insertion sort: a handful of partners)
+    const uint32_t hi = nc_host(C, i);
+    for (uint32_t a = 1; a < c; ++a) {  // ascending pair key of the host's ids (insertion sort: a handful of partners)
       const uint32_t v = list[a];
-      const uint64_t kv = pair_mix(i, v);
+      const uint64_t kv = pair_mix(hi, nc_host(C, v));
       uint32_t b = a;
-      while (b > 0 && pair_mix(i, list[b - 1]) > kv) { list[b] = list[b - 1]; --b; }
+      while (b > 0 && pair_mix(hi, nc_host(C, list[b - 1])) > kv) { list[b] = list[b - 1]; --b; }
       list[b] = v;
     }
     if (c) {
@@ -127,7 +131,7 @@ __global__ void __launch_bounds__(kNcBlock) k_nc_rhs(NodeContactArrays C, const 
     const float4 pj = pos[j];
     const float rj = radius[j];
     float px, py, pz;
-    if (i < j) nc_project(pi, pj, ri, rj, true, px, py, pz);
+    if (nc_host(C, i) < nc_host(C, j)) nc_project(pi, pj, ri, rj, true, px, py, pz);  // (a is the node with the lower host id)
     else nc_project(pj, pi, rj, ri, false, px, py, pz);
     sx += kNodePairW * px; sy += kNodePairW * py; sz += kNodePairW * pz;
   }

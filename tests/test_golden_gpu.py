@@ -16,6 +16,12 @@ pies_set_rest), one tick - and is compared with the fp64 expectation at the tole
   against the fp64 decisions;
 * PD group constraints (Src/ShapeMatchingConstraint.cpp:6-177): isolated shape groups (shape_projection.npz), one scalar equation
   per node with the projection on the right-hand side, through k_pd_local_shape and the fp64 contribution slots;
+* PD contacts (Src/Solver.cpp:240-262, 367-484, 680-875; Src/CollisionConstraint.cpp): the ordered contact list with the reference's
+  duplicates, the node-pair list, the contact rows of the global step, the stabilisation passes (they shift prevPosition) and the
+  three friction loops in the reference's order - isolated records (pd_contact_response.npz) in every variant of the contact
+  rows, the sequential passes, the launch path, the CG and the right-hand side, and a whole loop with all three contact families
+  (pd_contacts_tiny.npz), also renumbered.  Before these the contact response was held to the oracle alone, which shares its
+  algorithms - and, for the node contacts, was fed the device's own list;
 * the whole-loop PBD restatement (pbd_tiny_coll{0,1}.npz) tick by tick under schedule EXACT, pd_tiny.npz under PD
   (test_pd_parity_gpu.py), pd_groups_tiny.npz - shape groups, a goal and a mass write on the live scene - under PD.
 """
@@ -25,7 +31,9 @@ import os
 import numpy as np
 import pytest
 
-from test_oracle_golden import build_pd_groups, build_shape_scene, pd_groups_edits, shape_gate, shape_options, shape_records
+from test_oracle_golden import (build_contact_scene, build_pd_contacts_tiny, build_pd_groups, build_shape_scene, contact_options, contact_records,
+                                contact_tick_lists, pd_groups_edits, run_contact_response_oracle, set_contact_tick, shape_gate, shape_options,
+                                shape_records)
 from test_pd_parity_gpu import record
 
 pytestmark = pytest.mark.gpu
@@ -380,6 +388,174 @@ def test_pd_groups_tiny_scene_goldens(pies, tune, layout):
         record("golden_pd_groups_tiny[%s]" % layout, "velocities", ev, 2e-4 / 0.012)
         print("pd_groups_tiny [%s] tick %d: |dpos| %.3g |dvel| %.3g" % (layout, t, ep, ev))
         assert ep <= 2e-4 and ev <= 2e-4 / 0.012, (t, ep, ev)
+    assert g.pcg_health()["short_solves"] == 0 and not g.failed
+    g.close()
+
+
+# ---- PD contacts: lists and response -------------------------------------------------------------------------------------------
+CONTACT_VARIANTS = {"default": {}, "rows_inline": {"PIES_TRI_FAST_ROWS": "0"}, "rows_pass": {"PIES_TRI_FAST_ROWS": "1"},
+                    "rows_pass_unmerged": {"PIES_TRI_FAST_ROWS": "1", "PIES_ROW_MAX_UNIQUE": "4"}, "sequential_l2": {"PIES_TRI_LDS": "0"},
+                    "no_graph": {"PIES_NO_GRAPH": "1"}, "cg_two_launch": {"PIES_PD_CG_SINGLE": "0"}, "rhs_kernel": {"PIES_PD_FUSE_RHS": "0"}}
+
+
+@pytest.fixture(scope="module")
+def contact_reference(oracle):
+    """pd_contact_response.npz and what the oracle makes of its two scenes (one tick each, shared by the variants below)"""
+    out = {}
+    for which in ("pt", "nn"):
+        d, o = run_contact_response_oracle(oracle, which)
+        out[which] = (d, o.positions, o.prev_positions, o.velocities)
+    return out
+
+
+def contact_gates(test, d, which, ora, dev, records):
+    """Per record and state array: the oracle's own distance from the restatement within shape_gate (velocities: over h), the
+    device within max(twice that distance, the solve's fp32 noise on the record's coordinates); recorded, then asserted."""
+    worst = []
+    for label, a, b in records:
+        x = d[which + "_pos"][a:b]
+        size = max(float(np.abs(x).max()), float(np.abs(d[which + "_expected_pos"][a:b]).max()))
+        for k, (name, key, per) in enumerate((("positions", "pos", 1.0), ("prev_positions", "prev", 1.0), ("velocities", "vel", float(H)))):
+            exp = d[which + "_expected_" + key][a:b]
+            d_ora = float(np.abs(ora[k][a:b] - exp).max())
+            assert d_ora <= shape_gate(x) / per, (label, name, d_ora)  # (a gate made of the oracle's distance needs it close)
+            gate = max(2.0 * d_ora, SOLVE_NOISE * size / per)
+            err = float(np.abs(dev[k][a:b] - exp).max())
+            print("%s %-14s %-62s device %.3g oracle %.3g gate %.3g" % (test, name, label, err, d_ora, gate))
+            record(test, name, err / gate, 1.0)
+            worst.append((err / gate, label, name, err, gate))
+    worst.sort(reverse=True)
+    assert worst[0][0] <= 1.0, worst[:5]
+
+
+@pytest.mark.parametrize("variant", list(CONTACT_VARIANTS))
+def test_pd_contact_response_goldens(pies, tune, contact_reference, variant):
+    """pd_contact_response.npz through the device, one tick per variant of the global step's contact rows (summed inline, in a
+    pass of their own, unmerged), of the order-dependent stabilisation and friction passes (on the LDS copy or through L2), of
+    the launch path, the CG form and the right-hand side.  Point-triangle scene: pies_get_tri_contacts equals the restatement's
+    ordered list - the device keeps a triangle once per bucket walk and multiplies by the cells two ranges share, the reference
+    lists a hit once per shared cell: 1, 2, 4 and 8 copies here, and none for the target that lies exactly in an integer plane.
+    Node-node scene (PIES_FLAG_PD_NODE_CONTACTS): the pair list in its order.  Positions, previous positions (the stabilisation
+    shifts them) and velocities (three friction loops in the reference's order) per record at twice the oracle's own distance
+    from fp64 or the solve's noise.  These scenes' passes run level by level; the single-wavefront walk needs more than 2048
+    levels and has no fp64 scene - test_chain_deeper_than_the_level_cap_takes_the_walk holds it bit for bit to the level form,
+    and this test holds the level form to fp64."""
+    for name, value in CONTACT_VARIANTS[variant].items():
+        tune(name, value)
+    for which in ("pt", "nn"):
+        d, *ora = contact_reference[which]
+        g = pies.Solver(contact_options(pies, d), device=0)
+        g.set_pcg(1e-7, 256)
+        if which == "nn":
+            g.set_flag(pies.FLAG_PD_NODE_CONTACTS, 1)
+        build_contact_scene(g, d, which)
+        g.tick(1)
+        dev = (g.positions, g.prev_positions, g.velocities)
+        tri, pairs = g.tri_collisions.reshape(-1, 4), g.node_contacts().reshape(-1, 2)
+        health, failed = g.pcg_health(), g.failed
+        g.close()
+        assert not failed and health["short_solves"] == 0 and all(np.isfinite(a).all() for a in dev)
+        if which == "pt":
+            assert np.array_equal(tri, d["pt_contacts"]), (len(tri), len(d["pt_contacts"]))
+            assert len(pairs) == 0
+        else:
+            assert len(tri) == 0
+            assert [tuple(sorted(p)) for p in pairs.tolist()] == [tuple(p) for p in d["nn_pairs"].tolist()]
+        contact_gates("golden_pd_contact_response[%s,%s]" % (variant, which), d, which, ora, dev, contact_records(d, which))
+
+
+BYSTANDERS = 37  # loose nodes far from the scene: with them the system has more rows than one 64-row chunk, so a numbering can gain
+
+
+def build_pd_contacts_tiny_shuffled(s, d, hid):
+    """build_pd_contacts_tiny with the host ids of all bodies shuffled together (fixture node i is host node hid[i]), built like
+    build_pd_groups_shuffled: the boxes from raw nodes and containers, since createTetBox numbers its own.  The host ids that hid
+    leaves out are bystanders: single nodes 40 units away that touch nothing.  Returns the bystanders' state arrays."""
+    gm = golden_module()
+    W, Hh, D = (int(v) for v in d["dims"])
+    nb = W * Hh * D
+    n = len(d["radius"])
+    total = n + BYSTANDERS
+    rest = d["pos"][0].copy()
+    tets, tris = [], []
+    for k, tr in enumerate(d["translations"]):
+        box, t, _ = gm.lattice(W, Hh, D, tr.astype(np.float64), float(d["spacing"]))
+        rest[k * nb:(k + 1) * nb] = box.astype(np.float32)  # the elements' rest state is where the nodes are added
+        tets.append(t + k * nb)
+        tris.append(gm.box_triangles(W, Hh, D) + k * nb)
+    tets, tris = np.concatenate(tets), np.concatenate(tris + [d["loose_triangles"].astype(np.int64)])
+    far = np.float32([[40.0 + 3.0 * (k % 7), 5.0 + 3.0 * (k // 7), 40.0] for k in range(total)])
+    at, radius, im = far.copy(), np.full(total, 0.2, np.float32), np.ones(total, np.float32)
+    at[hid], radius[hid], im[hid] = rest, d["radius"], d["invMass"]
+    s.add_nodes_raw(at, radius=radius, invMass=im)
+    s.add_tet(hid[tets].astype(np.uint32), 1.0, 0.8, 1.0)
+    s.add_volume(hid[tets].astype(np.uint32), 1.0, 1.0, 1.0)
+    s.add_triangles(hid[tris].astype(np.uint32))
+    return dict(pos=far, prev=far, vel=np.zeros_like(far))
+
+
+def pairs_per_node(pairs):
+    """node -> its pairs in list order: what the sequential friction loop's result depends on (pairs without a common node commute)"""
+    out = {}
+    for p in pairs:
+        for v in p:
+            out.setdefault(v, []).append(p)
+    return out
+
+
+TINY_CONTACT_VARIANTS = {"default": {}, "rows_pass": {"PIES_TRI_FAST_ROWS": "1"}, "sequential_l2": {"PIES_TRI_LDS": "0"}, "no_graph": {"PIES_NO_GRAPH": "1"},
+                         "renumbered": {"PIES_CG_CHUNK_ROWS": "64"}}
+
+
+@pytest.mark.parametrize("variant", list(TINY_CONTACT_VARIANTS))
+def test_pd_contacts_tiny_scene_goldens(pies, tune, variant):
+    """pd_contacts_tiny.npz: two tet boxes, one landing on the other, and loose spheres - point-triangle contacts both ways (listed
+    up to eighteen times each), floor contacts and node pairs in one system, nodes on which two and all three friction loops meet.
+    Tick by tick from the stored fp32 state against the fp64 restatement: the contact list in its order with its duplicates, the
+    node-pair set, the state at pd_tiny's gates.  (The floor contacts have no getter on the device; the oracle's list is held to
+    the restatement's in test_oracle_golden.py, and a wrong one shows in the positions of the bottom layer.)  renumbered: the host
+    ids of all bodies shuffled together (and 37 bystanders, so that there is more than one 64-row chunk): the library renumbers,
+    the lists come back in host ids, and the pair key is the host ids' whatever the device's numbering - a friction loop in the
+    order of the device's ids, as it ran before this test existed, missed the velocity gate of tick 2 by a factor of three under
+    the shuffle first tried."""
+    d = load("pd_contacts_tiny.npz")
+    for name, value in TINY_CONTACT_VARIANTS[variant].items():
+        tune(name, value)
+    n = len(d["radius"])
+    g = pies.Solver(contact_options(pies, d), device=0)
+    g.set_pcg(1e-7, 256)
+    g.set_flag(pies.FLAG_PD_NODE_CONTACTS, 1)
+    if variant == "renumbered":
+        g.set_flag(pies.FLAG_RENUMBER_NODES, 1)
+        # (the pair key is taken over the host's ids, so a shuffle of them reorders the friction loop: this one - most do not -
+        # keeps the order of every node's pairs in all six ticks, which is all the loop's result depends on; asserted below)
+        hid = np.random.default_rng(0).permutation(n + BYSTANDERS)[:n]
+        others = build_pd_contacts_tiny_shuffled(g, d, hid)
+    else:
+        hid, others = np.arange(n), None
+        build_pd_contacts_tiny(g, d)
+    g.finalize()
+    assert g.count(pies.NODES_RENUMBERED) == (1 if variant == "renumbered" else 0)
+    back = {int(h): i for i, h in enumerate(hid)}
+    test = "golden_pd_contacts_tiny[%s]" % variant
+    for t in range(len(d["pos"])):
+        tri, floor, pairs = contact_tick_lists(d, t)
+        set_contact_tick(g, d, t, hid, others)
+        g.tick()
+        assert np.array_equal(g.tri_collisions.reshape(-1, 4), hid[tri]), (t, len(g.tri_collisions), len(tri))
+        listed = [tuple(sorted(int(back[v]) for v in p)) for p in g.node_contacts().reshape(-1, 2).tolist()]  # in the fixture's ids
+        want = [tuple(p) for p in pairs.tolist()]
+        assert set(listed) == set(want) and len(listed) == len(want) == g.count(pies.NODE_CONTACTS), (t, listed)
+        if variant != "renumbered":
+            assert listed == want, (t, listed)  # ascending pair key: the friction loop's order
+        assert pairs_per_node(listed) == pairs_per_node(want), (t, listed)  # every node meets its partners in the fixture's order
+        ep, eq, ev = (float(np.abs(getattr(g, name)[hid] - d["expected_" + key][t]).max())
+                      for name, key in (("positions", "pos"), ("prev_positions", "prev"), ("velocities", "vel")))
+        print("%s tick %d: |dpos| %.3g |dprev| %.3g |dvel| %.3g" % (test, t, ep, eq, ev))
+        record(test, "positions", ep, 2e-4)
+        record(test, "prev_positions", eq, 2e-4)
+        record(test, "velocities", ev, 2e-4 / 0.012)
+        assert ep <= 2e-4 and eq <= 2e-4 and ev <= 2e-4 / 0.012, (t, ep, eq, ev)
     assert g.pcg_health()["short_solves"] == 0 and not g.failed
     g.close()
 

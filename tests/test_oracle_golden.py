@@ -247,6 +247,148 @@ def test_pd_groups_tiny_scene_against_fp64_restatement():
     assert o.count(O.STATICS) > 0 and not o.failed  # the floor contacts were exercised
 
 
+# ---- PD contacts: lists and response (Solver.cpp:240-262, 298-308, 337-349, 367-484; CollisionConstraint.cpp) ----------------------
+CONTACT_H = 0.012
+
+
+def contact_options(mod, d, prefix=""):
+    """the options a contact fixture stores, on the oracle's or the device's Options"""
+    kw = {k: d[prefix + "opt_" + k].item() for k in ("fixedTimestepSize", "iterations", "collisionStabilizationIterations",
+                                                    "collisionThresholdDistance", "collisionThickness", "gravity", "damping", "friction",
+                                                    "staticFrictionThreshold", "floorHeight", "threadCount")}
+    assert abs(kw["fixedTimestepSize"] - CONTACT_H) < 1e-12
+    return mod.Options(solver=mod.PD, timeSubsteps=1, **kw)
+
+
+def build_contact_scene(s, d, which):
+    """pd_contact_response.npz's point-triangle scene ("pt") or its node-node scene ("nn") on an oracle or a device solver"""
+    s.add_nodes_raw(d[which + "_pos"], vel=d[which + "_vel"], radius=d[which + "_radius"], invMass=d[which + "_invMass"])
+    if which == "pt":
+        s.add_triangles(d["pt_triangles"])
+    s.set_prev_positions(d[which + "_prev"])
+
+
+def contact_records(d, which):
+    off = d[which + "_offsets"]
+    return [(str(d[which + "_labels"][k]), int(a), int(b)) for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+
+def contact_state_distances(s, d, which, a, b):
+    """max |state - fp64| over nodes a .. b: (positions, previous positions, velocities)"""
+    return tuple(float(np.abs(getattr(s, name)[a:b] - d[which + "_expected_" + key][a:b]).max())
+                 for name, key in (("positions", "pos"), ("prev_positions", "prev"), ("velocities", "vel")))
+
+
+def run_contact_response_oracle(mod, which):
+    d = load("pd_contact_response.npz")
+    o = mod.OracleSolver(contact_options(mod, d))
+    build_contact_scene(o, d, which)
+    if which == "nn":
+        o.add_node_pairs(d["nn_pairs"])  # the oracle has no node-node detection: the fixture's list, in its order
+    o.tick()
+    assert not o.failed
+    return d, o
+
+
+@pytest.mark.parametrize("which", ["pt", "nn"])
+def test_pd_contact_response_against_fp64_restatement(which):
+    """pd_contact_response.npz: isolated point-triangle records (one scene) and loose sphere pairs (another), one tick.  The ordered
+    contact list - the reference's duplicates included, once per cell the two triangles' ranges share - equals the restatement's
+    exactly; positions and previous positions per record within shape_gate of the record's coordinates, velocities within that
+    over h (the gates test_golden_gpu.py builds the device's gates from)."""
+    d, o = run_contact_response_oracle(O, which)
+    if which == "pt":
+        assert np.array_equal(o.tri_collisions, d["pt_contacts"]), (len(o.tri_collisions), len(d["pt_contacts"]))
+    worst = {}
+    for label, a, b in contact_records(d, which):
+        gate = shape_gate(d[which + "_pos"][a:b])
+        for name, dist, g in zip(("positions", "prev_positions", "velocities"), contact_state_distances(o, d, which, a, b), (gate, gate, gate / CONTACT_H)):
+            worst[name] = max(worst.get(name, 0.0), dist / g)
+            assert dist <= g, (label, name, dist, g)
+    print("pd_contact_response [%s]: oracle distance over gate:" % which, {k: round(v, 3) for k, v in worst.items()})
+
+
+def build_pd_contacts_tiny(s, d):
+    """pd_contacts_tiny.npz's scene on an oracle or a device solver: two createTetBox bodies, five loose spheres, a loose triangle"""
+    W, H, D = (int(v) for v in d["dims"])
+    for tr in d["translations"]:
+        s.create_tet_box(W, H, D, translation=tr, scale=float(d["spacing"]), w=1.0, volume=True, triangles=True)
+    nb = 2 * W * H * D
+    s.add_nodes_raw(d["pos"][0][nb:], radius=d["radius"][nb:])
+    s.add_triangles(d["loose_triangles"])
+    s.set_radii(d["radius"])
+    s.set_inv_masses(d["invMass"])
+
+
+def contact_tick_lists(d, t):
+    """tick t's expected lists: point-triangle contacts (ordered, with duplicates), floor nodes (ordered), node pairs (ordered)"""
+    return tuple(d[name + "_list"][d[name + "_offsets"][t]:d[name + "_offsets"][t + 1]] for name in ("tri", "floor", "pair"))
+
+
+def set_contact_tick(s, d, t, host_id=None, others=None):
+    """tick t's stored start state (host_id: fixture node i is node host_id[i] of the scene; others: the state arrays of a scene
+    that holds further nodes, which are put back as well)"""
+    for name, put in (("pos", s.set_positions), ("prev", s.set_prev_positions), ("vel", s.set_velocities)):
+        a = d[name][t]
+        if host_id is not None:
+            a = np.empty_like(a) if others is None else others[name].copy()
+            a[host_id] = d[name][t]
+        put(a)
+
+
+def pd_contacts_tiny_oracle(mod, d, t):
+    """an oracle at the start of tick t (a new one per tick: its node-pair container only grows, and it has no node-node detection
+    of its own - it is given the fixture's list of this tick, in its order)"""
+    o = mod.OracleSolver(contact_options(mod, d))
+    build_pd_contacts_tiny(o, d)
+    set_contact_tick(o, d, t)
+    o.add_node_pairs(contact_tick_lists(d, t)[2])
+    return o
+
+
+def test_pd_contacts_tiny_scene_against_fp64_restatement():
+    """Two tet boxes, one landing on the other, and loose spheres: point-triangle contacts (some listed eighteen times over),
+    floor contacts and node pairs in one system, the stabilisation passes and the three friction loops meeting on single nodes.
+    Every tick from its stored start state; the three lists exactly, the state at pd_tiny's gates."""
+    d = load("pd_contacts_tiny.npz")
+    for t in range(len(d["pos"])):
+        tri, floor, pairs = contact_tick_lists(d, t)
+        o = pd_contacts_tiny_oracle(O, d, t)
+        o.tick()
+        assert np.array_equal(o.tri_collisions, tri), (t, len(o.tri_collisions), len(tri))
+        assert np.array_equal(o.ids(O.STATICS), floor), t
+        ep, eq, ev = (float(np.abs(getattr(o, name) - d["expected_" + key][t]).max())
+                      for name, key in (("positions", "pos"), ("prev_positions", "prev"), ("velocities", "vel")))
+        print("pd_contacts_tiny tick %d: |dpos| %.3g |dprev| %.3g |dvel| %.3g (%d contacts, %d floor, %d pairs)" % (t, ep, eq, ev, len(tri), len(floor), len(pairs)))
+        assert ep <= 2e-4 and eq <= 2e-4 and ev <= 2e-4 / 0.012, (t, ep, eq, ev)
+        assert len(tri) and len(floor) and len(pairs) and not o.failed
+
+
+def test_pd_contact_response_goldens_have_teeth():
+    """From the restatement alone: the contacts move or turn the nodes of three records in four by more than ten gates, the list holds duplicates (2, 4 and 8
+    copies), the friction order of the node with three partners is not the id order, and the record whose target lies exactly in
+    the plane y = 5 is listed nowhere."""
+    d = load("pd_contact_response.npz")
+    h = CONTACT_H
+    free = d["pt_pos"].astype(np.float64) + h * d["pt_vel"].astype(np.float64)  # where the nodes end up without contacts
+    sharp = 0
+    recs = contact_records(d, "pt")
+    for label, a, b in recs:
+        gate = shape_gate(d["pt_pos"][a:b])
+        moved = float(np.abs(d["pt_expected_pos"][a:b] - free[a:b]).max()) > 10 * gate
+        turned = float(np.abs(d["pt_expected_vel"][a:b] - d["pt_vel"][a:b]).max()) > 10 * gate / h
+        sharp += moved or turned
+    assert sharp >= 0.75 * len(recs), sharp  # (two records list no contact; 100 units away ten gates are a velocity of 0.9)
+    copies = {}
+    for c in map(tuple, d["pt_contacts"]):
+        copies[c] = copies.get(c, 0) + 1
+    assert {1, 2, 4} <= set(copies.values()) and max(copies.values()) >= 8
+    flat = [k for k, (label, a, b) in enumerate(recs) if "y = 5" in label]
+    assert len(flat) == 1 and not any(recs[flat[0]][1] <= c[0] < recs[flat[0]][2] for c in d["pt_contacts"])
+    pairs = [tuple(p) for p in d["nn_pairs"]]
+    assert pairs != sorted(pairs) and len(set(pairs)) == len(pairs)
+
+
 def test_pd_rest_state_is_a_fixed_point_without_gravity():
     o = O.OracleSolver(solver=O.PD, iterations=3, gravity=0.0)
     o.create_tet_box(3, 3, 3, translation=(0, 5, 0), w=1.0)
