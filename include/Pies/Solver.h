@@ -404,6 +404,67 @@ public:
     for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
     return _reactions(impulse, torque, hits);
   }
+  // Extension (pies_apply_forces in pies_hip.h states the rule): force fields.  applyForces changes the velocities on the device
+  // by the forces acting for dt seconds - every force reads the state the call found, whatever its place in the list - and returns
+  // per force the impulse it gave, the torque of that impulse about the force's centre and the number of nodes it affected.  A
+  // force acts everywhere until within() confines it to a sphere.  Call it before tick; positions do not change.
+  struct Force : pies_force_t {
+    // an acceleration along `a` (asForce(): a force)
+    static Force directional(const glm::vec3& a) { return _type(PIES_FORCE_DIRECTIONAL, a, 0.0f, 0.0f); }
+    // away from the centre with strength > 0 (a blast), towards it with strength < 0 (an attractor)
+    static Force radial(const glm::vec3& centre, float strength) { return _type(PIES_FORCE_RADIAL, glm::vec3(0.0f, 0.0f, 0.0f), strength, 0.0f).at(centre); }
+    // cross(axis, p - centre) * strength; the axis need not be a unit vector
+    static Force vortex(const glm::vec3& centre, const glm::vec3& axis, float strength) { return _type(PIES_FORCE_VORTEX, axis, strength, 0.0f).at(centre); }
+    // a medium moving with `velocity` that takes the share min(strength * dt, 1) of the relative velocity
+    static Force drag(float strength, const glm::vec3& velocity = glm::vec3(0.0f, 0.0f, 0.0f)) { return _type(PIES_FORCE_DRAG, velocity, strength, 0.0f); }
+    // air moving with `velocity` against getTriangles(), both sides: strength for the normal part, shear for the tangential part
+    static Force wind(const glm::vec3& velocity, float strength, float shear = 0.0f) { return _type(PIES_FORCE_WIND, velocity, strength, shear); }
+    Force& within(const glm::vec3& c, float r, int fall = PIES_FALLOFF_NONE) {
+      radius = r;
+      falloff = fall;
+      return at(c);
+    }
+    Force& at(const glm::vec3& c) {
+      for (int k = 0; k < 3; ++k) centre[k] = c[k];
+      return *this;
+    }
+    Force& asForce() {
+      flags |= PIES_FORCE_IS_FORCE;
+      return *this;
+    }
+
+   private:
+    static Force _type(int type, const glm::vec3& v, float strength, float shear) {
+      Force f;
+      std::memset(static_cast<pies_force_t*>(&f), 0, sizeof(pies_force_t));
+      f.type = type;
+      f.radius = INFINITY;
+      f.falloff = PIES_FALLOFF_NONE;
+      f.strength = strength;
+      f.shear = shear;
+      for (int k = 0; k < 3; ++k) f.vector[k] = v[k];
+      return f;
+    }
+  };
+  struct ForceReaction {
+    glm::vec3 impulse, torque;
+    uint32_t nodes;
+  };
+  std::vector<ForceReaction> applyForces(const std::vector<Force>& forces, float dt) {
+    const uint32_t n = static_cast<uint32_t>(forces.size());
+    std::vector<pies_force_t> records(forces.begin(), forces.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n));
+    std::vector<uint32_t> nodes(n);
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_apply_forces(_handle(), n, records.data(), dt, impulse.data(), torque.data(), nodes.data()));
+    std::vector<ForceReaction> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].nodes = nodes[k];
+    }
+    return out;
+  }
   // Extension (pies_collide_field_props in pies_hip.h states the rule): rigid colliders of any shape.  A field is a signed distance
   // function on a lattice in a local frame, negative inside: addField takes the host's samples (sample (i, j, k) at local
   // origin + (i, j, k) * cell, stored at (k * ny + j) * nx + i: an analytic shape, a height field), addFieldFromTriMesh builds

@@ -573,6 +573,74 @@ typedef struct pies_field_prop {
 } pies_field_prop_t;
 int pies_collide_field_props(pies_solver_t* s, uint32_t n_props, const pies_field_prop_t* props, float* out_impulse,
                              float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop);
+/* EXTENSION (the reference's only external acceleration is options.gravity): FORCE FIELDS - wind on the scene's triangles, blasts
+ * and attractors, vortices, a braking medium, a plain push - applied to the velocities where HBM holds them: the second
+ * device-side edit of node state after pies_collide_props.  forces: n_forces records.  dt: the time the forces act for, in
+ * seconds (the host's choice: a frame, a substep).  The outputs may each be NULL: out_impulse, out_torque (n_forces x 3),
+ * out_nodes (n_forces).
+ * The rule, in fp32 without fused multiply-adds, with pies_collide_props' conventions: dot products summed left to right as
+ * x x + y y + z z, cross is pies_raycast's, a vector times (or divided by) a scalar is taken componentwise, fminf returns the
+ * other operand when one is a NaN, every test is the positive form written, so a NaN anywhere is "not affected".  Only + - * /
+ * sqrtf, fminf and comparisons occur.
+ * THE STATE READ IS THE STATE THE CALL FOUND: every force, whatever its index, reads the positions p and the velocities v the
+ * call found (the wind reads the velocities of a triangle's three corners).  Positions and previous positions are never written.
+ * A node with invMass w == 0 is never moved and never counted.  Per node i and force k the rule yields a velocity change
+ * dv_k(i), or "not affected".  A node affected by at least one force ends with v' = v + ((dv_k0 + dv_k1) + ...): the changes of
+ * the forces that affect it, added per component in ascending k to a sum that starts at 0.0f, and that sum added to v.  A node
+ * no force affects is not written.
+ *   The region of force k at a point x:  d = x - centre, dd = d.d;  inside iff dd < radius * radius (the product rounded;
+ *     radius = +inf: everywhere dd is finite);  fall = 1                                        PIES_FALLOFF_NONE
+ *                                                      1 - sqrtf(dd) / radius                   PIES_FALLOFF_LINEAR
+ *                                                      u * u with u = 1 - dd / (radius * radius) PIES_FALLOFF_SMOOTH
+ *   The point forces take the region at x = p; outside it the node is not affected.  g = fall * dt.
+ *   PIES_FORCE_DIRECTIONAL  a = vector.
+ *   PIES_FORCE_RADIAL       not affected unless dd > 0;  a = (d / sqrtf(dd)) * strength: a blast when strength > 0, an attractor
+ *                           when strength < 0.
+ *   PIES_FORCE_VORTEX       a = cross(vector, d) * strength: vector is the axis through centre, not normalised.
+ *   for these three:        a is an acceleration; with PIES_FORCE_IS_FORCE in flags it is a force, a = a * w.  dv = a * g.
+ *   PIES_FORCE_DRAG         a medium that moves with vector:  k = fminf(strength * dt, 1);  dv = (vector - v) * (k * fall).
+ *                           Independent of the mass; the cap keeps the explicit step from overshooting.
+ *   PIES_FORCE_WIND         acts on the triangles of the PIES_TRIANGLES container, both sides alike.  For triangle t with corners
+ *                           a, b, c (positions) and va, vb, vc (velocities):
+ *                             N = cross(b - a, c - a), nn = N.N;  no contribution unless nn > 0;
+ *                             len = sqrtf(nn), n = N / len, area = 0.5f * len;
+ *                             the region at x = ((a + b) + c) / 3.0f;  no contribution outside it;
+ *                             rel = vector - ((va + vb) + vc) / 3.0f;  vn = rel.n;
+ *                             F = (n * (strength * vn) + (rel - n * vn) * shear) * (area * fall);
+ *                           and every corner with w != 0 receives (F / 3.0f) * (dt * w) with its own w.  dv_k(i) is the sum of
+ *                           what node i receives over the (triangle, corner) entries that name it, in ascending triangle index
+ *                           from 0.0f; the node is affected by k iff at least one of them contributed.  strength: pressure
+ *                           per unit of normal relative speed and area; shear: the same for the tangential part.
+ * out_nodes[k] counts the nodes force k affected.  out_impulse[k] is the sum of j = dv_k(i) * (1 / w_i), out_torque[k] the sum
+ * of cross(p_i - centre_k, j), both in pies_collide_props' fixed two-level order: per tile of 256 consecutive HOST node ids in
+ * ascending id from 0.0f (a node not affected adds 0), then the tile sums in ascending tile index from 0.0f.  The order is a
+ * function of the node count alone - not of a kernel variant, not of PIES_FLAG_RENUMBER_NODES - and nothing is summed with
+ * atomics, so two calls agree bit for bit.  With all three outputs NULL nothing is summed and the second launch is not paid.
+ * Runs on the handle's stream behind whatever ticks and begun frames are queued, finalizes a changed scene first and
+ * synchronises once before it returns; export frames begun earlier, captured graphs and pies_launch_counts are left as they were.
+ * The edit is in HBM only: the host mirror is marked stale for the velocities alone, nothing is uploaded.  Its buffers (and the
+ * node -> triangle incidence of the wind, built at the first call with a wind after a pies_finalize) are freed by the next
+ * pies_finalize, pies_clear or pies_destroy.
+ * PIES_ERR_INVALID: NULL forces with n_forces > 0, an unknown type or falloff, a non-finite member of a record other than
+ * radius = +inf, a negative or NaN radius, a negative or non-finite dt.  PIES_ERR_UNSUPPORTED: n_forces > PIES_FORCE_MAX.
+ * n_forces == 0 returns PIES_OK and does nothing.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first).  A
+ * scene without nodes synchronises and returns zeros; a wind in a scene without triangles affects nothing. */
+enum { PIES_FORCE_DIRECTIONAL = 0, PIES_FORCE_RADIAL = 1, PIES_FORCE_VORTEX = 2, PIES_FORCE_DRAG = 3, PIES_FORCE_WIND = 4 };
+enum { PIES_FALLOFF_NONE = 0, PIES_FALLOFF_LINEAR = 1, PIES_FALLOFF_SMOOTH = 2 };
+enum { PIES_FORCE_IS_FORCE = 1 }; /* flags */
+#define PIES_FORCE_MAX 64
+typedef struct pies_force {
+  int32_t type;
+  uint32_t flags;
+  float centre[3];  /* of the region; the point radial forces and vortices refer to, and the returned torque */
+  float radius;     /* of the region, >= 0; +inf: everywhere */
+  int32_t falloff;
+  float vector[3];  /* directional: the acceleration (force); vortex: the axis; drag, wind: the medium's velocity */
+  float strength;   /* radial, vortex: the factor; drag: 1 / s; wind: the normal coefficient */
+  float shear;      /* wind: the tangential coefficient */
+} pies_force_t;
+int pies_apply_forces(pies_solver_t* s, uint32_t n_forces, const pies_force_t* forces, float dt, float* out_impulse,
+                      float* out_torque, uint32_t* out_nodes);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:
@@ -617,7 +685,10 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * PIES_RAY_NARROW_MAX rays, default 512: the measured crossover), PIES_RAY_CHUNKS (pins the triangle chunks of the wide variant, 1 .. 1 024);
  * pies_closest_points, read at every call: PIES_NEAR_VARIANT (wide: one point per lane, narrow: one triangle per lane; unset: narrow
  * up to PIES_NEAR_NARROW_MAX points, default 4 096: the end of the measured sweep), PIES_NEAR_CHUNKS
- * (pins the triangle chunks of the wide variant, 1 .. 1 024); the winding pass has one form.  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
+ * (pins the triangle chunks of the wide variant, 1 .. 1 024); the winding pass has one form;
+ * pies_apply_forces, read at every call: PIES_FORCE_VARIANT (inplace: one launch writes the velocities where they are, scratch:
+ * new velocities to a scratch array, a second launch commits them; unset: inplace; a list with a wind always takes scratch: its
+ * lanes read their neighbours' velocities).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
  * race with other API calls of the process (a handle reads the switches at different times of its life).  None of
  * them is read from the environment: the only environment variables the library looks at are PIES_SCHEDULE (default schedule
  * of new handles), PIES_PROFILER_SAFE (profiling runs) and the print-only PIES_PCG_DEBUG / PIES_LAYER_DEBUG. */

@@ -51,6 +51,10 @@ PROP_NONE = 0xFFFFFFFF  # PIES_PROP_NONE: no prop touched the node
 PROP_MAX = 64  # PIES_PROP_MAX
 FIELD_MAX = 64  # PIES_FIELD_MAX: fields per handle
 FIELD_PROP_MAX = 64  # PIES_FIELD_PROP_MAX: field props per call
+FORCE_DIRECTIONAL, FORCE_RADIAL, FORCE_VORTEX, FORCE_DRAG, FORCE_WIND = 0, 1, 2, 3, 4  # pies_force_t.type
+FALLOFF_NONE, FALLOFF_LINEAR, FALLOFF_SMOOTH = 0, 1, 2  # pies_force_t.falloff
+FORCE_IS_FORCE = 1  # pies_force_t.flags: vector / strength give a force, not an acceleration
+FORCE_MAX = 64  # PIES_FORCE_MAX
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -72,7 +76,7 @@ SYMBOLS = [
     "pies_add_node_pair_constraints", "pies_get_node_order", "pies_get_node_contacts",
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
-    "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props",
+    "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -187,6 +191,55 @@ class FieldProp(C.Structure):
         return p
 
 
+class Force(C.Structure):
+    """pies_force_t field for field: one force field of pies_apply_forces.  The builders give a force that acts everywhere;
+    within() confines it to a sphere."""
+    _fields_ = [
+        ("type", C.c_int32), ("flags", C.c_uint32), ("centre", C.c_float * 3), ("radius", C.c_float), ("falloff", C.c_int32),
+        ("vector", C.c_float * 3), ("strength", C.c_float), ("shear", C.c_float),
+    ]
+
+    @classmethod
+    def _make(cls, type, vector=(0, 0, 0), strength=0.0, shear=0.0, centre=(0, 0, 0), is_force=False):
+        f = cls()
+        f.type, f.flags, f.falloff = type, FORCE_IS_FORCE if is_force else 0, FALLOFF_NONE
+        f.radius, f.strength, f.shear = float("inf"), strength, shear
+        f.centre[:] = [float(x) for x in centre]
+        f.vector[:] = [float(x) for x in vector]
+        return f
+
+    @classmethod
+    def directional(cls, vector, is_force=False):
+        """an acceleration (is_force: a force) along vector"""
+        return cls._make(FORCE_DIRECTIONAL, vector=vector, is_force=is_force)
+
+    @classmethod
+    def radial(cls, centre, strength, is_force=False):
+        """away from centre with strength > 0 (a blast), towards it with strength < 0 (an attractor)"""
+        return cls._make(FORCE_RADIAL, strength=strength, centre=centre, is_force=is_force)
+
+    @classmethod
+    def vortex(cls, centre, axis, strength=1.0, is_force=False):
+        """cross(axis, p - centre) * strength; the axis need not be a unit vector"""
+        return cls._make(FORCE_VORTEX, vector=axis, strength=strength, centre=centre, is_force=is_force)
+
+    @classmethod
+    def drag(cls, strength, velocity=(0, 0, 0)):
+        """a medium moving with velocity that takes the share min(strength * dt, 1) of the relative velocity"""
+        return cls._make(FORCE_DRAG, vector=velocity, strength=strength)
+
+    @classmethod
+    def wind(cls, velocity, strength, shear=0.0):
+        """air moving with velocity against the scene's triangles: strength for the normal part, shear for the tangential part"""
+        return cls._make(FORCE_WIND, vector=velocity, strength=strength, shear=shear)
+
+    def within(self, centre, radius, falloff=FALLOFF_NONE):
+        """confines the force to the sphere (centre, radius); radial forces and vortices refer to the same centre"""
+        self.centre[:] = [float(x) for x in centre]
+        self.radius, self.falloff = radius, falloff
+        return self
+
+
 _lib = None
 
 
@@ -274,6 +327,7 @@ def load():
     sig["pies_add_field_tri_mesh"] = [vp, u32, pf, u32, pu, f32, f32, pu]
     sig["pies_get_field"] = [vp, u32, pu, pf, pf, pf, C.c_uint64]
     sig["pies_collide_field_props"] = [vp, u32, C.POINTER(FieldProp), pf, pf, pu, pu]
+    sig["pies_apply_forces"] = [vp, u32, C.POINTER(Force), f32, pf, pf, pu]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -596,6 +650,18 @@ class Solver:
                                                   _pu(who) if node_prop else None))
         out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
         return out or None
+
+    def apply_forces(self, forces, dt, reaction=True):
+        """pies_apply_forces: changes the velocities by the forces (a sequence of Force) acting for dt seconds, where the device
+        holds them; every force reads the state the call found.  Returns (impulse float32 (k, 3), torque float32 (k, 3) about each
+        force's centre, nodes uint32 (k)) with reaction=True, else None."""
+        forces = list(forces)
+        k = len(forces)
+        arr = (Force * max(k, 1))(*forces)
+        imp, tor, nodes = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)
+        self._ck(self._L.pies_apply_forces(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
+                                           _pf(tor) if reaction else None, _pu(nodes) if reaction else None))
+        return (imp, tor, nodes) if reaction else None
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

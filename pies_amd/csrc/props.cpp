@@ -3,7 +3,7 @@
 // launches (prop_kernels.h).  The edit goes to dev.nd.pos / prev / vel - the state every schedule and both solvers start a substep
 // from - outside the captured substep: no graph, no schedule and no launch count changes.
 // prop_open_pass / prop_close_pass - the reaction's buffers, the fold, the stale marks and the copies out - are shared with
-// pies_collide_field_props (fields.cpp).
+// pies_collide_field_props (fields.cpp) and pies_apply_forces (forces.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -75,14 +75,16 @@ int prop_open_pass(pies_solver* s, uint32_t nProps, bool reaction, bool nodeProp
   return PIES_OK;
 }
 
-// After the collide launch of pass P: the fold, the stale marks, the copies out and the synchronisation.
-int prop_close_pass(pies_solver* s, const PropPass& P, float* out_impulse, float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop) {
+// After the collide launch of pass P: the fold, the stale marks (staleBits: the node arrays the launch edited), the copies out and
+// the synchronisation.
+int prop_close_pass(pies_solver* s, const PropPass& P, float* out_impulse, float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop,
+                    uint32_t staleBits) {
   RayBuffers& B = s->ray;
   const bool reaction = P.tileMask != nullptr;
   const uint32_t n = P.nd.n, n_props = P.nProps;
   if (reaction) launch_prop_fold(s->stream, P, B.propOut);
   HIP_TRY(s, hipGetLastError());
-  s->stale |= 7u;  // positions, previous positions and velocities: the host mirror is older than HBM (nothing is uploaded)
+  s->stale |= staleBits;  // the props' 7: positions, previous positions and velocities - the host mirror is older than HBM (nothing is uploaded)
   float folded[PIES_PROP_MAX * kPropSumWords];
   if (reaction) HIP_TRY(s, hipMemcpyAsync(folded, B.propOut, n_props * kPropSumWords * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   if (out_node_prop) HIP_TRY(s, hipMemcpyAsync(out_node_prop, B.propNodeProp, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));

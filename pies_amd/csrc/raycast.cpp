@@ -58,6 +58,32 @@ int ray_build_scene_triangles(pies_solver* s) {
   return PIES_OK;
 }
 
+}  // namespace
+
+// The node -> triangle incidence of the scene's triangles for the wind of pies_apply_forces (forces.cpp): CSR by HOST node id, one
+// entry (the triangle's index) per corner that names the node, ascending triangle index within a row.  Like the triangle list it
+// is built once per pies_finalize.
+int ray_build_incidence(pies_solver* s) {
+  RayBuffers& B = s->ray;
+  if (B.incBuilt) return PIES_OK;
+  const uint32_t n = s->nodeCount();
+  const std::vector<uint32_t>& tri = s->h_triangles;  // host ids (the call is outside an InternalNumbering scope)
+  std::vector<uint32_t> ptr(static_cast<size_t>(n) + 1, 0u), inc(tri.size());
+  for (uint32_t id : tri) ++ptr[id + 1];
+  for (uint32_t h = 0; h < n; ++h) ptr[h + 1] += ptr[h];
+  std::vector<uint32_t> next(ptr.begin(), ptr.end() - 1);
+  for (size_t e = 0; e < tri.size(); ++e) inc[next[tri[e]]++] = static_cast<uint32_t>(e / 3);
+  if (int rc = ray_grow(s, ptr.size(), &B.incPtr)) return rc;
+  if (int rc = ray_grow(s, inc.size(), &B.inc)) return rc;
+  HIP_TRY(s, hipMemcpyAsync(B.incPtr, ptr.data(), ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+  if (!inc.empty()) HIP_TRY(s, hipMemcpyAsync(B.inc, inc.data(), inc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));  // the staging vectors die with this scope
+  B.incBuilt = true;
+  return PIES_OK;
+}
+
+namespace {
+
 int all_misses(uint32_t n, uint32_t* hitTriangle, float* hitT, float* hitUv) {
   for (uint32_t r = 0; r < n; ++r) {
     if (hitTriangle) hitTriangle[r] = PIES_RAY_MISS;

@@ -222,6 +222,15 @@ struct RayBuffers {
   // it has met (nullptr: not staged - the host copy in pies_solver::h_fields is staged again at the next use)
   FieldPropRecord* fieldRecords = nullptr;    // PIES_FIELD_PROP_MAX records
   float* fieldSamples[PIES_FIELD_MAX] = {};
+  // pies_apply_forces (forces.cpp) shares the reaction's buffers above (propOut, propTileMask, propTileSums); its records, the
+  // scratch variant's new velocities and affected lanes, and the wind's node -> triangle incidence over `tri` (ray_build_incidence)
+  pies_force_t* forceRecords = nullptr;  // PIES_FORCE_MAX records
+  float4* forceVel = nullptr;            // per host id
+  uint64_t* forceAffected = nullptr;     // kForceWaves words per tile of 256 host ids
+  size_t forceVelCap = 0;                // nodes both hold
+  uint32_t* incPtr = nullptr;            // nodes + 1, by host id
+  uint32_t* inc = nullptr;               // 3 x nTris triangle indices
+  bool incBuilt = false;
 };
 
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
@@ -433,14 +442,17 @@ template <class T> int ray_grow(pies_solver* s, size_t count, T** d) {
   return rc;
 }
 int ray_open_target(pies_solver* s, int target, uint32_t skin, pies::RayTarget* out);
+// raycast.cpp, for forces.cpp : the node -> triangle incidence of the scene's triangles in s->ray (built once per pies_finalize)
+int ray_build_incidence(pies_solver* s);
 // nearest.cpp, shared with fields.cpp : the distance and winding launches of pies_closest_points for n points in HBM (each output
 // may be nullptr); no synchronisation
 int near_launch(pies_solver* s, const pies::RayTarget& T, const float* dPoints, uint32_t n, float maxDistance, uint32_t* dTri,
                 float* dDistance, float* dUv, float* dPoint, float* dWinding);
-// props.cpp, shared with fields.cpp : the reaction's buffers of s->ray for n nodes and nProps props, filled into P; then, after the
-// collide launch, the fold, the stale marks, the copies out, the synchronisation
+// props.cpp, shared with fields.cpp and forces.cpp : the reaction's buffers of s->ray for n nodes and nProps props, filled into P;
+// then, after the collide launch, the fold, the stale marks (staleBits: what the launch edited), the copies out, the synchronisation
 int prop_open_pass(pies_solver* s, uint32_t nProps, bool reaction, bool nodeProp, pies::PropPass* P);
-int prop_close_pass(pies_solver* s, const pies::PropPass& P, float* outImpulse, float* outTorque, uint32_t* outHits, uint32_t* outNodeProp);
+int prop_close_pass(pies_solver* s, const pies::PropPass& P, float* outImpulse, float* outTorque, uint32_t* outHits, uint32_t* outNodeProp,
+                    uint32_t staleBits = 7u);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of
