@@ -465,6 +465,43 @@ public:
     }
     return out;
   }
+  // Extension (pies_measure_elements / pies_measure_nodes in pies_hip.h state the rules): how the body is doing, evaluated on the
+  // device without a read-back.  measureElements answers for elements [first, first + count) of the tetrahedral (PIES_TET) or the
+  // volume (PIES_VOLUME) constraints in the order they were added - stretches, det F, volume, |F|^2, the norm of the Green strain
+  // and the PIES_ELEMENT_* flags per element when `records` is given, and the range's summary; count == UINT32_MAX: to the
+  // container's end.  measureNodes sums mass, momentum, angular momentum about `about`, first moment and kinetic energy over
+  // ranges of node ids (a body is the range its create* call appended); fp32 sums in a fixed order.  Both are read-only.
+  pies_element_summary_t measureElements(int type, uint32_t first = 0, uint32_t count = UINT32_MAX,
+                                         std::vector<pies_element_measure_t>* records = nullptr) {
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    if (count == UINT32_MAX) {
+      uint32_t size = 0;
+      _ck(pies_count(_handle(), type, &size));
+      count = size >= first ? size - first : 0;
+    }
+    if (records) records->assign(count, pies_element_measure_t{});
+    pies_element_summary_t summary;
+    _ck(pies_measure_elements(_handle(), type, first, count, records && count ? records->data() : nullptr, &summary));
+    return summary;
+  }
+  struct NodeRange {
+    uint32_t first, count;
+    glm::vec3 about;
+  };
+  std::vector<pies_node_sums_t> measureNodes(const std::vector<NodeRange>& ranges) {
+    const uint32_t n = static_cast<uint32_t>(ranges.size());
+    std::vector<uint32_t> pairs(2 * size_t(n));
+    std::vector<float> about(3 * size_t(n));
+    for (size_t k = 0; k < n; ++k) {
+      pairs[2 * k] = ranges[k].first;
+      pairs[2 * k + 1] = ranges[k].count;
+      for (int c = 0; c < 3; ++c) about[3 * k + c] = ranges[k].about[c];
+    }
+    std::vector<pies_node_sums_t> out(n);
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_measure_nodes(_handle(), n, pairs.data(), about.data(), out.data()));
+    return out;
+  }
   // Extension (pies_collide_field_props in pies_hip.h states the rule): rigid colliders of any shape.  A field is a signed distance
   // function on a lattice in a local frame, negative inside: addField takes the host's samples (sample (i, j, k) at local
   // origin + (i, j, k) * cell, stored at (k * ny + j) * nx + i: an analytic shape, a height field), addFieldFromTriMesh builds

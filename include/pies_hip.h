@@ -641,6 +641,93 @@ typedef struct pies_force {
 } pies_force_t;
 int pies_apply_forces(pies_solver_t* s, uint32_t n_forces, const pies_force_t* forces, float dt, float* out_impulse,
                       float* out_torque, uint32_t* out_nodes);
+/* EXTENSION (the reference has no such query): STRAIN, VOLUME AND MOMENTUM MEASURES evaluated where HBM holds the body - how the
+ * body is doing, without a read-back.  Both calls are READ-ONLY: node state, the host mirror's stale marks, export frames begun
+ * earlier, captured graphs and pies_launch_counts are left exactly as they were.  They run on the handle's stream behind whatever
+ * ticks and begun frames are queued, finalize a changed scene first (so a pies_set_rest or an appended body between two calls is
+ * seen by the second) and synchronise once before they return.  Their buffers (the staged element records among them) are built
+ * at the first call after a pies_finalize and freed by the next pies_finalize, pies_clear or pies_destroy.
+ * Both rules are fp32 without fused multiply-adds except where svd3 writes one, with pies_collide_props' conventions: dot
+ * products summed left to right as x x + y y + z z, cross is pies_raycast's, a vector times a scalar is taken componentwise,
+ * every test is the positive form written, so a NaN fails it.
+ *
+ * pies_measure_elements: elements [first, first + n) of the PIES_TET or the PIES_VOLUME container (both hold 4 node ids, Qinv and
+ * two limits), numbered in the order the host added them - under PIES_FLAG_RENUMBER_NODES, in every schedule and under both
+ * solvers the answer is a function of host order alone.  out: n records or NULL; summary: or NULL.  For element e with nodes
+ * x1..x4 at the positions the device holds and the rest data (Qinv, lo, hi) of the call's moment:
+ *   P[i] = x(i+2) - x1 (i = 0, 1, 2: the columns);  F = P Qinv in the reference's column-major arrays, as the tetrahedral
+ *     projection forms it:  F[c][r] = (P[0][r] * Qinv[c][0] + P[1][r] * Qinv[c][1]) + P[2][r] * Qinv[c][2]   (Qinv[c][r] is
+ *     word 3 c + r of pies_get_rest);
+ *   det(M) = (M[0][0] * (M[1][1] * M[2][2] - M[2][1] * M[1][2]) - M[1][0] * (M[0][1] * M[2][2] - M[2][1] * M[0][2]))
+ *            + M[2][0] * (M[0][1] * M[1][2] - M[1][1] * M[0][2]);      j = det(F);  volume = det(P) / 6.0f, signed by the
+ *     element's node order (volume / j is the rest volume with the same sign; the lattice factories do not wind all their
+ *     elements alike, so a host that wants a body's volume adds the records' magnitudes, not the summary's signed sum);
+ *   i1 = the nine squares F[c][r] * F[c][r] added in the array's order, c outer and r inner, starting from F[0][0] * F[0][0];
+ *   (a0, a1, a2) = the singular values the projection's SVD (svd3, pies_amd/csrc/dev_math.h) returns for the array F handed over
+ *     as the projection hands it over (no transposition), sorted descending by the compare-exchanges (0, 1), (1, 2), (0, 1), each
+ *     swapping iff a < b;  s = (a0, a1, a2), and iff j < 0.0f the last is negated: s[2] = -a2 (the projection's flip,
+ *     Constraints.cpp:106-108);
+ *   g_i = s[i] * s[i] - 1.0f;  green = 0.5f * sqrtf((g0 * g0 + g1 * g1) + g2 * g2): the Frobenius norm of the Green strain, zero
+ *     at rest and invariant under rotation;
+ *   flags: PIES_ELEMENT_NONFINITE iff not every entry of F has fabsf(F[c][r]) < +inf - the record's flags are then that bit alone,
+ *     its other words are stored as computed and are unspecified, and the summary passes the element by (the call still returns:
+ *     the SVD's sweeps are bounded).  Otherwise PIES_ELEMENT_INVERTED iff j < 0.0f, and with the limits as
+ *     pies_add_tet_constraints / pies_add_volume_constraints took them
+ *       PIES_TET:     PIES_ELEMENT_OVER iff s[0] > max_strain,  PIES_ELEMENT_UNDER iff fabsf(s[2]) < min_strain;
+ *       PIES_VOLUME:  prod = (a0 * a1) * a2;  PIES_ELEMENT_OVER iff prod > stretching,  PIES_ELEMENT_UNDER iff prod < compression.
+ * The summary covers the elements of the range that are not NONFINITE (nonfinite counts the others): the counts inverted, over,
+ * under; volume: the elements' volumes in a fixed two-level order - per tile of 256 consecutive indices of the container (tile
+ * t = indices 256 t .. 256 t + 255, restricted to the range) in ascending index from 0.0f, then the tile sums in ascending tile
+ * index from 0.0f; max_stretch (of s[0]), min_stretch (of fabsf(s[2])), min_j, max_j, max_green: minima and maxima are
+ * order-free but for +-0 and a NaN from an overflow, and so that those have one answer too they walk the same two levels - the
+ * held value starts as the first one met and is replaced by x iff x < it (a maximum: x > it), over a tile's elements and then
+ * over the values of the tiles that hold one; all five are 0.0f when the range holds no element that counts.  No atomics: two
+ * calls agree bit for bit.  With out == NULL no record is
+ * written; with summary == NULL nothing is reduced; with both NULL the call validates and synchronises.
+ * PIES_ERR_INVALID: a type other than PIES_TET / PIES_VOLUME, a range that leaves the container.  n == 0: PIES_OK and a zero
+ * summary.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first).
+ *
+ * pies_measure_nodes: mass, momentum, angular momentum, first moment and kinetic energy of up to PIES_MEASURE_RANGE_MAX ranges of
+ * HOST node ids: ranges holds n_ranges (first, count) pairs - a body is the id range its create* / pies_add_nodes call returned -
+ * which may overlap and may be empty; about: 3 floats per range, the point the angular momentum refers to, or NULL: the origin.
+ * Per range over its nodes with invMass w != 0 (a node with w == 0 is counted in `fixed` and adds nothing else), with position
+ * p, velocity v and m = 1.0f / w:
+ *   mass = sum m;  momentum = sum v * m;  angular = sum cross(p - about, v * m);  moment = sum p * m (divide by mass for the
+ *   centre of mass);  kinetic = sum 0.5f * (m * (v.v));  dynamic, fixed: the node counts.
+ * Every float sum is taken in pies_collide_props' fixed two-level order: per tile of 256 consecutive HOST ids of the global
+ * tiling (tile t = ids 256 t .. 256 t + 255) the range's nodes in ascending id from 0.0f, then the tiles in ascending index from
+ * 0.0f.  The order is a function of the range alone - not of PIES_FLAG_RENUMBER_NODES, not of the other ranges of the call - so
+ * a range gives the same bits alone and in a list of 64.  THESE ARE fp32 SUMS: at 100 000 nodes the last digits of mass are
+ * rounding (a sum of n terms carries an error of the order of n 2^-24 of its magnitude at worst, sqrt(n) 2^-24 typically); a
+ * host that needs more digits sums fewer nodes per range and adds the ranges in double precision.
+ * PIES_ERR_UNSUPPORTED: n_ranges > PIES_MEASURE_RANGE_MAX.  PIES_ERR_INVALID: NULL ranges or out with n_ranges > 0, a range that
+ * leaves [0, nodes), a non-finite about.  n_ranges == 0: PIES_OK.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are
+ * checked first). */
+enum { PIES_ELEMENT_INVERTED = 1, PIES_ELEMENT_OVER = 2, PIES_ELEMENT_UNDER = 4, PIES_ELEMENT_NONFINITE = 8 };
+#define PIES_MEASURE_RANGE_MAX 64
+typedef struct pies_element_measure {
+  float s[3];      /* the stretches, descending; s[2] < 0 on an inverted element */
+  float j;         /* det F */
+  float volume;    /* current; signed by the node order: det [x2 - x1, x3 - x1, x4 - x1] / 6 */
+  float i1;        /* |F|_F^2 */
+  float green;     /* |E|_F, E = (F^T F - 1) / 2 */
+  uint32_t flags;  /* PIES_ELEMENT_* */
+} pies_element_measure_t;
+typedef struct pies_element_summary {
+  float max_stretch, min_stretch, min_j, max_j, max_green, volume;
+  uint32_t inverted, over, under, nonfinite;
+} pies_element_summary_t;
+typedef struct pies_node_sums {
+  float mass;
+  float momentum[3];
+  float angular[3];
+  float moment[3];
+  float kinetic;
+  uint32_t dynamic, fixed;
+} pies_node_sums_t;
+int pies_measure_elements(pies_solver_t* s, int type, uint32_t first, uint32_t n, pies_element_measure_t* out,
+                          pies_element_summary_t* summary);
+int pies_measure_nodes(pies_solver_t* s, uint32_t n_ranges, const uint32_t* ranges, const float* about, pies_node_sums_t* out);
 /* _simFailed latch (Solver.cpp:26-28,853-856) */
 int pies_failed(pies_solver_t* s, int* failed);
 /* Point-triangle contacts of the last PD substep (Solver::_triCollisions, Solver.h:187), in list order:

@@ -55,6 +55,8 @@ FORCE_DIRECTIONAL, FORCE_RADIAL, FORCE_VORTEX, FORCE_DRAG, FORCE_WIND = 0, 1, 2,
 FALLOFF_NONE, FALLOFF_LINEAR, FALLOFF_SMOOTH = 0, 1, 2  # pies_force_t.falloff
 FORCE_IS_FORCE = 1  # pies_force_t.flags: vector / strength give a force, not an acceleration
 FORCE_MAX = 64  # PIES_FORCE_MAX
+ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
+MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -77,6 +79,7 @@ SYMBOLS = [
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
+    "pies_measure_elements", "pies_measure_nodes",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -240,6 +243,32 @@ class Force(C.Structure):
         return self
 
 
+class ElementMeasure(C.Structure):
+    """pies_element_measure_t field for field: one element's record of pies_measure_elements (eight words)."""
+    _fields_ = [("s", C.c_float * 3), ("j", C.c_float), ("volume", C.c_float), ("i1", C.c_float), ("green", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class ElementSummary(C.Structure):
+    """pies_element_summary_t field for field: the summary of a range of elements."""
+    _fields_ = [("max_stretch", C.c_float), ("min_stretch", C.c_float), ("min_j", C.c_float), ("max_j", C.c_float),
+                ("max_green", C.c_float), ("volume", C.c_float), ("inverted", C.c_uint32), ("over", C.c_uint32),
+                ("under", C.c_uint32), ("nonfinite", C.c_uint32)]
+
+
+class NodeSums(C.Structure):
+    """pies_node_sums_t field for field: the sums of one range of pies_measure_nodes (thirteen words)."""
+    _fields_ = [("mass", C.c_float), ("momentum", C.c_float * 3), ("angular", C.c_float * 3), ("moment", C.c_float * 3),
+                ("kinetic", C.c_float), ("dynamic", C.c_uint32), ("fixed", C.c_uint32)]
+
+
+# numpy views of the two records: Solver.measure_elements / measure_nodes return structured arrays
+ELEMENT_MEASURE_DTYPE = np.dtype([("s", np.float32, 3), ("j", np.float32), ("volume", np.float32), ("i1", np.float32),
+                                  ("green", np.float32), ("flags", np.uint32)])
+NODE_SUMS_DTYPE = np.dtype([("mass", np.float32), ("momentum", np.float32, 3), ("angular", np.float32, 3),
+                            ("moment", np.float32, 3), ("kinetic", np.float32), ("dynamic", np.uint32), ("fixed", np.uint32)])
+
+
 _lib = None
 
 
@@ -328,6 +357,8 @@ def load():
     sig["pies_get_field"] = [vp, u32, pu, pf, pf, pf, C.c_uint64]
     sig["pies_collide_field_props"] = [vp, u32, C.POINTER(FieldProp), pf, pf, pu, pu]
     sig["pies_apply_forces"] = [vp, u32, C.POINTER(Force), f32, pf, pf, pu]
+    sig["pies_measure_elements"] = [vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
+    sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -662,6 +693,31 @@ class Solver:
         self._ck(self._L.pies_apply_forces(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
                                            _pf(tor) if reaction else None, _pu(nodes) if reaction else None))
         return (imp, tor, nodes) if reaction else None
+
+    def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
+        """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at
+        the positions the device holds.  Returns (records, summary): a structured array of ELEMENT_MEASURE_DTYPE (s, j, volume,
+        i1, green, flags) or None, and an ElementSummary or None."""
+        if n is None:
+            n = self.count(ctype) - first
+        rec = np.zeros(n, ELEMENT_MEASURE_DTYPE) if records else None
+        summ = ElementSummary() if summary else None
+        self._ck(self._L.pies_measure_elements(self._h, ctype, first, n,
+                                               rec.ctypes.data_as(C.POINTER(ElementMeasure)) if records else None,
+                                               C.byref(summ) if summary else None))
+        return rec, summ
+
+    def measure_nodes(self, ranges, about=None):
+        """pies_measure_nodes: mass, momentum, angular momentum about `about` (one point per range; None: the origin), first
+        moment, kinetic energy and node counts of up to MEASURE_RANGE_MAX (first, count) ranges of host node ids, summed where
+        the device holds the nodes.  Returns a structured array of NODE_SUMS_DTYPE, one entry per range."""
+        r = np.ascontiguousarray(ranges, np.uint32).reshape(-1, 2)
+        k = len(r)
+        a = None if about is None else np.ascontiguousarray(about, np.float32).reshape(k, 3)
+        out = np.zeros(k, NODE_SUMS_DTYPE)
+        self._ck(self._L.pies_measure_nodes(self._h, k, _pu(r) if k else None, None if a is None or not k else _pf(a),
+                                            out.ctypes.data_as(C.POINTER(NodeSums)) if k else None))
+        return out
 
     def clear(self):
         self._ck(self._L.pies_clear(self._h))

@@ -18,6 +18,7 @@
 #include "skin_kernels.h"
 #include "ray_kernels.h"
 #include "field_kernels.h"
+#include "measure_kernels.h"
 
 namespace pies {
 
@@ -231,6 +232,21 @@ struct RayBuffers {
   uint32_t* incPtr = nullptr;            // nodes + 1, by host id
   uint32_t* inc = nullptr;               // 3 x nTris triangle indices
   bool incBuilt = false;
+  // pies_measure_elements / pies_measure_nodes (measure.cpp) have their buffers to themselves.  Per container (0: PIES_TET, 1:
+  // PIES_VOLUME) the elements staged in HOST order with node ids in DEVICE numbering, upload_tets' layout - the scene's own
+  // tetrahedral records are in plan order and PBD stages no volume records
+  uint4* measureIds[2] = {nullptr, nullptr};
+  float4* measureQ[2][3] = {};
+  bool measureStaged[2] = {false, false};
+  pies_element_measure_t* measureOut = nullptr;  // the records of a call
+  size_t measureOutCap = 0;                      // elements
+  uint32_t* measureTileRecords = nullptr;        // per tile of 256 element indices: kMeasureTileWords words
+  size_t measureTileCap = 0;                     // tiles
+  uint32_t* measureSummary = nullptr;            // kMeasureTileWords words: the folded summary
+  MeasureRange* measureRanges = nullptr;         // PIES_MEASURE_RANGE_MAX records
+  float* measureNodeOut = nullptr;               // PIES_MEASURE_RANGE_MAX x kNodeSumWords: the folded sums
+  float* measureNodeTileSums = nullptr;          // per (tile of 256 host ids, range): kNodeSumWords words
+  size_t measureNodeTileCap = 0;                 // (tile, range) records
 };
 
 // What one pies_finalize builds in HBM for the scene as it stands.  free_device frees `allocations` and puts a fresh DeviceScene in
