@@ -465,6 +465,82 @@ public:
     }
     return out;
   }
+  // Extension (pies_apply_surface_loads in pies_hip.h states the rule): loads that know a triangle's side and a surface's volume.
+  // applySurfaceLoads changes the velocities on the device by the loads acting for dt seconds on ranges of getTriangles() - every
+  // load reads the state the call found - and returns per load the impulse it gave, its torque about the load's point, the nodes
+  // it affected and the volume and area of its range (also for a load of strength 0: that is how to learn a balloon's volume
+  // before choosing gas()'s restVolume).  A range covers every triangle until on() confines it.  Call it before tick.
+  struct SurfaceLoad : pies_surface_load_t {
+    // the pressure p along every triangle's normal
+    static SurfaceLoad pressure(float p) { return _type(PIES_LOAD_PRESSURE, p); }
+    // an isothermal gas inside the closed range: ambient * (restVolume / V - 1) along every normal
+    static SurfaceLoad gas(float ambient, float restVolume) {
+      SurfaceLoad l = _type(PIES_LOAD_GAS, ambient);
+      l.rest_volume = restVolume;
+      return l;
+    }
+    // a fluid of `weight` per unit volume (density x gravity) whose surface holds surfacePoint and faces `up`
+    static SurfaceLoad fluid(float weight, const glm::vec3& surfacePoint, const glm::vec3& up = glm::vec3(0.0f, 1.0f, 0.0f)) {
+      SurfaceLoad l = _type(PIES_LOAD_FLUID, weight).about(surfacePoint);
+      for (int k = 0; k < 3; ++k) l.up[k] = up[k];
+      return l;
+    }
+    // a fluid's drag per unit of relative speed and submerged area, the fluid moving with `v`
+    SurfaceLoad& withDrag(float d, const glm::vec3& v = glm::vec3(0.0f, 0.0f, 0.0f)) {
+      drag = d;
+      for (int k = 0; k < 3; ++k) velocity[k] = v[k];
+      return *this;
+    }
+    // the range's triangles are wound with their normals pointing into the body
+    SurfaceLoad& inward() {
+      flags |= PIES_LOAD_INWARD;
+      return *this;
+    }
+    // triangles [firstTriangle, firstTriangle + triangleCount) of getTriangles()
+    SurfaceLoad& on(uint32_t firstTriangle, uint32_t triangleCount = UINT32_MAX) {
+      first = firstTriangle;
+      count = triangleCount;
+      return *this;
+    }
+    // the point the returned torque refers to (a fluid: a point of its surface)
+    SurfaceLoad& about(const glm::vec3& c) {
+      for (int k = 0; k < 3; ++k) point[k] = c[k];
+      return *this;
+    }
+
+   private:
+    static SurfaceLoad _type(int type, float strength) {
+      SurfaceLoad l;
+      std::memset(static_cast<pies_surface_load_t*>(&l), 0, sizeof(pies_surface_load_t));
+      l.type = type;
+      l.count = UINT32_MAX;
+      l.strength = strength;
+      l.up[1] = 1.0f;
+      return l;
+    }
+  };
+  struct SurfaceReaction {
+    glm::vec3 impulse, torque;
+    uint32_t nodes;
+    float volume, area;
+  };
+  std::vector<SurfaceReaction> applySurfaceLoads(const std::vector<SurfaceLoad>& loads, float dt) {
+    const uint32_t n = static_cast<uint32_t>(loads.size());
+    std::vector<pies_surface_load_t> records(loads.begin(), loads.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n)), volume(n), area(n);
+    std::vector<uint32_t> nodes(n);
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_apply_surface_loads(_handle(), n, records.data(), dt, impulse.data(), torque.data(), nodes.data(), volume.data(), area.data()));
+    std::vector<SurfaceReaction> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].nodes = nodes[k];
+      out[k].volume = volume[k];
+      out[k].area = area[k];
+    }
+    return out;
+  }
   // Extension (pies_measure_elements / pies_measure_nodes in pies_hip.h state the rules): how the body is doing, evaluated on the
   // device without a read-back.  measureElements answers for elements [first, first + count) of the tetrahedral (PIES_TET) or the
   // volume (PIES_VOLUME) constraints in the order they were added - stretches, det F, volume, |F|^2, the norm of the Green strain

@@ -641,6 +641,72 @@ typedef struct pies_force {
 } pies_force_t;
 int pies_apply_forces(pies_solver_t* s, uint32_t n_forces, const pies_force_t* forces, float dt, float* out_impulse,
                       float* out_torque, uint32_t* out_nodes);
+/* EXTENSION (the reference has no such loads): SURFACE LOADS - a constant pressure, the pressure of an enclosed gas, the hydrostatic
+ * pressure and the drag of a fluid - on ranges of the PIES_TRIANGLES container, applied to the velocities where HBM holds them:
+ * the third device-side edit of node state after pies_collide_props and pies_apply_forces.  These are the loads that need a
+ * triangle's ORIENTATION (the wind of pies_apply_forces is quadratic in the normal and treats both sides alike) or a GLOBAL
+ * quantity of a body (the volume its surface encloses).  loads: n_loads records.  dt: the time the loads act for, in seconds.  The
+ * outputs may each be NULL: out_impulse, out_torque (n_loads x 3), out_nodes, out_volume, out_area (n_loads).
+ * The rule, in fp32 without fused multiply-adds, with pies_apply_forces' conventions: dot products summed left to right as
+ * x x + y y + z z, cross is pies_raycast's, a vector times (or divided by) a scalar is taken componentwise, every test is the
+ * positive form written, so a NaN anywhere is "not affected".  Only + - * / sqrtf and comparisons occur.
+ * THE STATE READ IS THE STATE THE CALL FOUND: every load, whatever its index, reads the positions and the velocities the call
+ * found.  Positions and previous positions are never written.  A node with invMass w == 0 is never moved and never counted.
+ * A load's range is the triangles [first, first + count) of the container in the order the host added them (count == UINT32_MAX:
+ * to the container's end).  A triangle's corners are a, b, c as the container names them - with PIES_LOAD_INWARD (the range's
+ * triangles are wound with their normals pointing into the body) a, c, b - and va, vb, vc their velocities.  Per load k:
+ *   VOLUME AND AREA of the range, evaluated whatever the type:  o = corner a of triangle `first`;  per triangle
+ *     six_t = (a - o) . cross(b - o, c - o);   N = cross(b - a, c - a), nn = N.N, area_t = 0.5f * sqrtf(nn);
+ *     V_k = (sum of six_t) / 6.0f,  A_k = sum of area_t;  both sums in a fixed two-level order: per tile of 256 consecutive
+ *     container indices of the global tiling (tile u = indices 256 u .. 256 u + 255, restricted to the range) in ascending index
+ *     from 0.0f, then the tile sums in ascending tile index from 0.0f.  The shift by o keeps a body far from the world's origin
+ *     from cancelling its volume away.  An empty range gives zeros.  V_k > 0 for a closed surface wound outward (after the flag).
+ *   THE PRESSURE p on triangle t:
+ *     PIES_LOAD_PRESSURE  p = strength.
+ *     PIES_LOAD_GAS       an isothermal gas that is at the ambient pressure `strength` when it fills rest_volume: the load acts iff
+ *                         V_k > 0.0f, and then p = strength * (rest_volume / V_k - 1.0f) on every triangle of the range.
+ *     PIES_LOAD_FLUID     x = ((a + b) + c) / 3.0f, depth = (point - x) . up; the triangle contributes nothing unless
+ *                         depth > 0.0f;  p = -(strength * depth).  A triangle the fluid's surface cuts is in or out by its
+ *                         centroid: triangles are not clipped.  On a flat triangle a pressure linear in space integrates to its
+ *                         value at the centroid times the area, so a closed submerged surface receives strength * V * up in sum:
+ *                         Archimedes.
+ *   THE TRIANGLE'S FORCE:  no contribution unless nn > 0.0f;  F = N * (0.5f * p);  PIES_LOAD_FLUID with drag != 0.0f on a
+ *     contributing triangle adds  rel = velocity - ((va + vb) + vc) / 3.0f,  F = F + rel * (drag * area_t).  Every corner with
+ *     w != 0 receives (F / 3.0f) * (dt * w) with its own w.
+ *   THE CHANGE FOR A NODE:  dv_k(i) is the sum of what node i receives over the (triangle, corner) entries of the range that name
+ *     it, in ascending triangle index from 0.0f; the node is affected by k iff at least one of them contributed.  A node affected
+ *     by at least one load ends with v' = v + ((dv_k0 + dv_k1) + ...): the changes of the loads that affect it, added per
+ *     component in ascending k to a sum that starts at 0.0f, and that sum added to v.  A node no load affects is not written.
+ * out_nodes[k] counts the nodes load k affected.  out_impulse[k] is the sum of j = dv_k(i) * (1 / w_i), out_torque[k] the sum of
+ * cross(p_i - point_k, j), both in pies_collide_props' fixed two-level order: per tile of 256 consecutive HOST node ids in
+ * ascending id from 0.0f, then the tile sums in ascending tile index from 0.0f.  Nothing is summed with atomics, so two calls
+ * agree bit for bit; neither a kernel variant nor PIES_FLAG_RENUMBER_NODES changes a bit.  out_volume[k] = V_k and out_area[k] =
+ * A_k, also for a load whose strength is 0: that is how a host learns a surface's volume before it chooses rest_volume.
+ * Runs on the handle's stream behind whatever ticks and begun frames are queued, finalizes a changed scene first and
+ * synchronises ONCE, before it returns: volume, gas pressure and the edit are chained on the device.  Export frames begun earlier,
+ * captured graphs and pies_launch_counts are left as they were.  The edit is in HBM only: the host mirror is marked stale for
+ * the velocities alone, nothing is uploaded.  Its buffers (and the node -> triangle incidence, shared with the wind) are freed
+ * by the next pies_finalize, pies_clear or pies_destroy.
+ * PIES_ERR_INVALID: NULL loads with n_loads > 0, an unknown type or flag bit, a range that leaves the container, a non-finite
+ * member, PIES_LOAD_GAS with rest_volume not > 0, drag < 0, a negative or non-finite dt.  PIES_ERR_UNSUPPORTED: n_loads >
+ * PIES_LOAD_MAX.  n_loads == 0 returns PIES_OK and does nothing.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are
+ * checked first).  A scene without nodes or without triangles synchronises and returns zeros. */
+enum { PIES_LOAD_PRESSURE = 0, PIES_LOAD_GAS = 1, PIES_LOAD_FLUID = 2 };
+enum { PIES_LOAD_INWARD = 1 }; /* flags: the range's triangles are wound with their normals inward; each is read as (a, c, b) */
+#define PIES_LOAD_MAX 64
+typedef struct pies_surface_load { /* 16 words, no padding */
+  int32_t type;
+  uint32_t flags;
+  uint32_t first, count; /* triangles [first, first + count) of the PIES_TRIANGLES container; count == UINT32_MAX: to its end */
+  float strength;        /* PRESSURE: the pressure p.  GAS: the ambient pressure p0.  FLUID: weight per unit volume (density x gravity) */
+  float rest_volume;     /* GAS: the volume at which the inside is at p0 (> 0) */
+  float point[3];        /* FLUID: a point of the fluid's surface.  All types: the point the returned torque refers to */
+  float up[3];           /* FLUID: the direction out of the fluid, used as given (a unit vector is the host's business) */
+  float velocity[3];     /* FLUID: the fluid's velocity */
+  float drag;            /* FLUID: drag per unit of relative speed and submerged area, >= 0; 0: none */
+} pies_surface_load_t;
+int pies_apply_surface_loads(pies_solver_t* s, uint32_t n_loads, const pies_surface_load_t* loads, float dt, float* out_impulse,
+                             float* out_torque, uint32_t* out_nodes, float* out_volume, float* out_area);
 /* EXTENSION (the reference has no such query): STRAIN, VOLUME AND MOMENTUM MEASURES evaluated where HBM holds the body - how the
  * body is doing, without a read-back.  Both calls are READ-ONLY: node state, the host mirror's stale marks, export frames begun
  * earlier, captured graphs and pies_launch_counts are left exactly as they were.  They run on the handle's stream behind whatever
@@ -775,7 +841,9 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * (pins the triangle chunks of the wide variant, 1 .. 1 024); the winding pass has one form;
  * pies_apply_forces, read at every call: PIES_FORCE_VARIANT (inplace: one launch writes the velocities where they are, scratch:
  * new velocities to a scratch array, a second launch commits them; unset: inplace; a list with a wind always takes scratch: its
- * lanes read their neighbours' velocities).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
+ * lanes read their neighbours' velocities);
+ * pies_apply_surface_loads, read at every call: PIES_LOAD_VARIANT (inplace / scratch as above; unset: inplace; a list with a
+ * fluid drag always takes scratch).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
  * race with other API calls of the process (a handle reads the switches at different times of its life).  None of
  * them is read from the environment: the only environment variables the library looks at are PIES_SCHEDULE (default schedule
  * of new handles), PIES_PROFILER_SAFE (profiling runs) and the print-only PIES_PCG_DEBUG / PIES_LAYER_DEBUG. */

@@ -55,6 +55,10 @@ FORCE_DIRECTIONAL, FORCE_RADIAL, FORCE_VORTEX, FORCE_DRAG, FORCE_WIND = 0, 1, 2,
 FALLOFF_NONE, FALLOFF_LINEAR, FALLOFF_SMOOTH = 0, 1, 2  # pies_force_t.falloff
 FORCE_IS_FORCE = 1  # pies_force_t.flags: vector / strength give a force, not an acceleration
 FORCE_MAX = 64  # PIES_FORCE_MAX
+LOAD_PRESSURE, LOAD_GAS, LOAD_FLUID = 0, 1, 2  # pies_surface_load_t.type
+LOAD_INWARD = 1  # pies_surface_load_t.flags: the range's triangles are wound with their normals inward
+LOAD_MAX = 64  # PIES_LOAD_MAX
+LOAD_TO_END = 0xFFFFFFFF  # pies_surface_load_t.count: to the container's end
 ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
 MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
@@ -79,6 +83,7 @@ SYMBOLS = [
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
+    "pies_apply_surface_loads",
     "pies_measure_elements", "pies_measure_nodes",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
@@ -243,6 +248,53 @@ class Force(C.Structure):
         return self
 
 
+class SurfaceLoad(C.Structure):
+    """pies_surface_load_t field for field: one load of pies_apply_surface_loads on the triangles [first, first + count) of the
+    TRIANGLES container (count None: to the container's end)."""
+    _fields_ = [
+        ("type", C.c_int32), ("flags", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("strength", C.c_float),
+        ("rest_volume", C.c_float), ("point", C.c_float * 3), ("up", C.c_float * 3), ("velocity", C.c_float * 3), ("drag", C.c_float),
+    ]
+
+    @classmethod
+    def _make(cls, type, strength, first, count, about=(0, 0, 0)):
+        f = cls()
+        f.type, f.strength, f.first, f.count = type, strength, first, LOAD_TO_END if count is None else count
+        f.point[:] = [float(x) for x in about]
+        f.up[:] = [0.0, 1.0, 0.0]
+        return f
+
+    @classmethod
+    def pressure(cls, p, first=0, count=None, about=(0, 0, 0)):
+        """the pressure p along every triangle's normal; about: the point the returned torque refers to"""
+        return cls._make(LOAD_PRESSURE, p, first, count, about)
+
+    @classmethod
+    def gas(cls, ambient, rest_volume, first=0, count=None, about=(0, 0, 0)):
+        """an isothermal gas inside the closed range: ambient * (rest_volume / V - 1) along every normal"""
+        f = cls._make(LOAD_GAS, ambient, first, count, about)
+        f.rest_volume = rest_volume
+        return f
+
+    @classmethod
+    def fluid(cls, weight, surface_point, up=(0, 1, 0), first=0, count=None):
+        """a fluid of `weight` per unit volume (density x gravity) whose surface holds surface_point and faces up"""
+        f = cls._make(LOAD_FLUID, weight, first, count, surface_point)
+        f.up[:] = [float(x) for x in up]
+        return f
+
+    def with_drag(self, drag, velocity=(0, 0, 0)):
+        """a fluid's drag per unit of relative speed and submerged area, the fluid moving with velocity"""
+        self.drag = drag
+        self.velocity[:] = [float(x) for x in velocity]
+        return self
+
+    def inward(self):
+        """the range's triangles are wound with their normals pointing into the body"""
+        self.flags |= LOAD_INWARD
+        return self
+
+
 class ElementMeasure(C.Structure):
     """pies_element_measure_t field for field: one element's record of pies_measure_elements (eight words)."""
     _fields_ = [("s", C.c_float * 3), ("j", C.c_float), ("volume", C.c_float), ("i1", C.c_float), ("green", C.c_float),
@@ -357,6 +409,7 @@ def load():
     sig["pies_get_field"] = [vp, u32, pu, pf, pf, pf, C.c_uint64]
     sig["pies_collide_field_props"] = [vp, u32, C.POINTER(FieldProp), pf, pf, pu, pu]
     sig["pies_apply_forces"] = [vp, u32, C.POINTER(Force), f32, pf, pf, pu]
+    sig["pies_apply_surface_loads"] = [vp, u32, C.POINTER(SurfaceLoad), f32, pf, pf, pu, pf, pf]
     sig["pies_measure_elements"] = [vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
     sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
@@ -693,6 +746,20 @@ class Solver:
         self._ck(self._L.pies_apply_forces(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
                                            _pf(tor) if reaction else None, _pu(nodes) if reaction else None))
         return (imp, tor, nodes) if reaction else None
+
+    def apply_surface_loads(self, loads, dt, reaction=True):
+        """pies_apply_surface_loads: changes the velocities by the loads (a sequence of SurfaceLoad) acting for dt seconds, where
+        the device holds them; every load reads the state the call found.  Returns (impulse float32 (k, 3), torque float32 (k, 3)
+        about each load's point, nodes uint32 (k), volume float32 (k), area float32 (k)) with reaction=True, else None."""
+        loads = list(loads)
+        k = len(loads)
+        arr = (SurfaceLoad * max(k, 1))(*loads)
+        imp, tor, nodes = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)
+        vol, area = np.zeros(k, np.float32), np.zeros(k, np.float32)
+        self._ck(self._L.pies_apply_surface_loads(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
+                                                  _pf(tor) if reaction else None, _pu(nodes) if reaction else None,
+                                                  _pf(vol) if reaction else None, _pf(area) if reaction else None))
+        return (imp, tor, nodes, vol, area) if reaction else None
 
     def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
         """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at

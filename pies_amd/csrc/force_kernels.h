@@ -31,5 +31,7 @@ struct ForcePass {
 void launch_force_evaluate(hipStream_t st, const ForcePass& P);
 // the scratch variant's second launch: newVel -> nd.vel for the affected nodes
 void launch_force_commit(hipStream_t st, const ForcePass& P);
+// the same launch for any pass that filled newVel and affected like the scratch variant does (load_kernels.hip)
+void launch_velocity_commit(hipStream_t st, const NodeArrays& nd, const uint32_t* inv, const float4* newVel, const uint64_t* affected);
 
 }  // namespace pies

@@ -142,7 +142,12 @@ void launch_force_evaluate(hipStream_t st, const ForcePass& P) {
 
 void launch_force_commit(hipStream_t st, const ForcePass& P) {
   if (!launchable(P) || !P.newVel) return;
-  hipLaunchKernelGGL(k_force_commit, dim3(prop_tiles(P.base.nd.n)), dim3(kPropTile), 0, st, P.base.nd, P.base.inv, P.newVel, P.affected);
+  launch_velocity_commit(st, P.base.nd, P.base.inv, P.newVel, P.affected);
+}
+
+void launch_velocity_commit(hipStream_t st, const NodeArrays& nd, const uint32_t* inv, const float4* newVel, const uint64_t* affected) {
+  if (!nd.n) return;
+  hipLaunchKernelGGL(k_force_commit, dim3(prop_tiles(nd.n)), dim3(kPropTile), 0, st, nd, inv, newVel, affected);
 }
 
 }  // namespace pies

@@ -232,6 +232,15 @@ struct RayBuffers {
   uint32_t* incPtr = nullptr;            // nodes + 1, by host id
   uint32_t* inc = nullptr;               // 3 x nTris triangle indices
   bool incBuilt = false;
+  // pies_apply_surface_loads (loads.cpp) shares the reaction's buffers, forceVel / forceAffected and the incidence above; its
+  // records, what the fold leaves per load, the tiles of 256 triangles the call's ranges meet and their sums per (slot, load)
+  pies_surface_load_t* loadRecords = nullptr;  // PIES_LOAD_MAX records
+  void* loadState = nullptr;                   // PIES_LOAD_MAX LoadState records (load_kernels.h)
+  uint32_t* loadTiles = nullptr;               // tile indices, ascending
+  size_t loadTileCap = 0;                      // slots
+  float2* loadTileSums = nullptr;
+  size_t loadSumCap = 0;                       // (slot, load) records
+  std::vector<uint32_t> loadTilesHost;         // the staging copy of loadTiles: alive until the call has synchronised
   // pies_measure_elements / pies_measure_nodes (measure.cpp) have their buffers to themselves.  Per container (0: PIES_TET, 1:
   // PIES_VOLUME) the elements staged in HOST order with node ids in DEVICE numbering, upload_tets' layout - the scene's own
   // tetrahedral records are in plan order and PBD stages no volume records
