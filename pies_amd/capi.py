@@ -681,15 +681,29 @@ class Solver:
         them; the velocity response is relative to the moving prop.  Returns (impulse float32 (k, 3), torque float32 (k, 3), hits
         uint32 (k)) with reaction=True - the host applies -impulse and -torque (about the prop's pivot) to its own body -, followed by
         the last prop that touched every node (uint32 (n), PROP_NONE: none) with node_prop=True; None when neither is asked for."""
-        props = list(props)
-        k = len(props)
-        arr = (Prop * max(k, 1))(*props)
-        imp, tor, hits = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)) if reaction else (None,) * 3
-        who = np.empty(self.count(NODES), np.uint32) if node_prop else None
-        self._ck(self._L.pies_collide_props(self._h, k, arr if k else None, _pf(imp) if reaction else None,
-                                            _pf(tor) if reaction else None, _pu(hits) if reaction else None,
-                                            _pu(who) if node_prop else None))
-        out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
+        return self._node_edit(self._L.pies_collide_props, Prop, props, (), reaction, node_prop)
+
+    def _node_edit(self, call, ctype, records, dt, reaction, node_prop=None, extras=0):
+        """One between-tick edit of node state through its entry point: the records as an array of ctype, dt as () or (dt,), the
+        reaction outputs (impulse (k, 3), torque (k, 3), counts uint32 (k), then `extras` float32 (k) arrays; NULL without
+        reaction) and, for a call that has the output (node_prop not None), the last record that touched every node.  Returns what
+        was asked for as one tuple, None when nothing was."""
+        records = list(records)
+        k = len(records)
+        arr = (ctype * max(k, 1))(*records)
+        out, args = (), (None,) * (3 + extras)
+        if reaction:
+            out = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32))
+            args = (_pf(out[0]), _pf(out[1]), _pu(out[2]))
+            for _ in range(extras):
+                out += (np.zeros(k, np.float32),)
+                args += (_pf(out[-1]),)
+        if node_prop:
+            out += (np.empty(self.count(NODES), np.uint32),)
+            args += (_pu(out[-1]),)
+        elif node_prop is not None:
+            args += (None,)
+        self._ck(call(self._h, k, arr if k else None, *dt, *args))
         return out or None
 
     def add_field(self, samples, origin, cell):
@@ -724,42 +738,19 @@ class Solver:
         """pies_collide_field_props: pushes the nodes out of the field props (a sequence of FieldProp, applied in order) where the
         device holds them.  Returns what collide_props returns: (impulse, torque, hits) with reaction=True, followed by the last
         prop that touched every node with node_prop=True; None when neither is asked for."""
-        props = list(props)
-        k = len(props)
-        arr = (FieldProp * max(k, 1))(*props)
-        imp, tor, hits = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)) if reaction else (None,) * 3
-        who = np.empty(self.count(NODES), np.uint32) if node_prop else None
-        self._ck(self._L.pies_collide_field_props(self._h, k, arr if k else None, _pf(imp) if reaction else None,
-                                                  _pf(tor) if reaction else None, _pu(hits) if reaction else None,
-                                                  _pu(who) if node_prop else None))
-        out = ((imp, tor, hits) if reaction else ()) + ((who,) if node_prop else ())
-        return out or None
+        return self._node_edit(self._L.pies_collide_field_props, FieldProp, props, (), reaction, node_prop)
 
     def apply_forces(self, forces, dt, reaction=True):
         """pies_apply_forces: changes the velocities by the forces (a sequence of Force) acting for dt seconds, where the device
         holds them; every force reads the state the call found.  Returns (impulse float32 (k, 3), torque float32 (k, 3) about each
         force's centre, nodes uint32 (k)) with reaction=True, else None."""
-        forces = list(forces)
-        k = len(forces)
-        arr = (Force * max(k, 1))(*forces)
-        imp, tor, nodes = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)
-        self._ck(self._L.pies_apply_forces(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
-                                           _pf(tor) if reaction else None, _pu(nodes) if reaction else None))
-        return (imp, tor, nodes) if reaction else None
+        return self._node_edit(self._L.pies_apply_forces, Force, forces, (dt,), reaction)
 
     def apply_surface_loads(self, loads, dt, reaction=True):
         """pies_apply_surface_loads: changes the velocities by the loads (a sequence of SurfaceLoad) acting for dt seconds, where
         the device holds them; every load reads the state the call found.  Returns (impulse float32 (k, 3), torque float32 (k, 3)
         about each load's point, nodes uint32 (k), volume float32 (k), area float32 (k)) with reaction=True, else None."""
-        loads = list(loads)
-        k = len(loads)
-        arr = (SurfaceLoad * max(k, 1))(*loads)
-        imp, tor, nodes = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32)
-        vol, area = np.zeros(k, np.float32), np.zeros(k, np.float32)
-        self._ck(self._L.pies_apply_surface_loads(self._h, k, arr if k else None, dt, _pf(imp) if reaction else None,
-                                                  _pf(tor) if reaction else None, _pu(nodes) if reaction else None,
-                                                  _pf(vol) if reaction else None, _pf(area) if reaction else None))
-        return (imp, tor, nodes, vol, area) if reaction else None
+        return self._node_edit(self._L.pies_apply_surface_loads, SurfaceLoad, loads, (dt,), reaction, extras=2)
 
     def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
         """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at

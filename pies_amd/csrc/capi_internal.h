@@ -3,11 +3,19 @@
 // substep_graph.cpp: the substep as a launch sequence, graph capture, the adaptations that follow the scene; profiling.cpp: the
 // timing passes; tuning.cpp: the registry of pies_set_tuning).
 #pragma once
+#include <cmath>
 #include <vector>
 
 #include "device_util.h"
 
 namespace pies {
+
+// argument checks: every one of n floats is finite
+inline bool finite_all(const float* v, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
 
 // ---- substep_graph.cpp ----
 bool under_profiler();              // PIES_PROFILER_SAFE=1

@@ -371,4 +371,14 @@ PIES_DEV float det3_cm(const float m[3][3]) {
          m[2][0] * (m[0][1] * m[1][2] - m[1][1] * m[0][2]);
 }
 
+// n records of whole words from HBM to LDS, by every lane of a workgroup of kBlock lanes; the caller's barrier follows
+template <uint32_t kBlock = 256, class T>
+PIES_DEV void stage_records(T* dst, const T* src, uint32_t n) {
+  static_assert(sizeof(T) % sizeof(uint32_t) == 0, "a record is whole words without padding at its end");
+  constexpr uint32_t kWords = sizeof(T) / sizeof(uint32_t);
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+  for (uint32_t k = threadIdx.x; k < n * kWords; k += kBlock) d[k] = s[k];
+}
+
 }  // namespace pies

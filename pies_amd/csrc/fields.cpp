@@ -15,12 +15,6 @@ using namespace pies;
 
 namespace {
 
-bool finite_all(const float* v, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return false;
-  return true;
-}
-
 // nullptr, or what is wrong with the record
 const char* field_prop_fault(const pies_solver* s, const pies_field_prop_t& p) {
   if (p.field >= s->h_fields.size()) return "unknown field id";
@@ -160,27 +154,12 @@ int pies_get_field(pies_solver_t* s, uint32_t field, uint32_t dims[3], float ori
 int pies_collide_field_props(pies_solver_t* s, uint32_t n_props, const pies_field_prop_t* props, float* out_impulse,
                              float* out_torque, uint32_t* out_hits, uint32_t* out_node_prop) {
   if (!s) return PIES_ERR_INVALID;
-  if (n_props && !props) return fail(s, PIES_ERR_INVALID, "pies_collide_field_props: props is NULL");
-  if (n_props > PIES_FIELD_PROP_MAX)
-    return fail(s, PIES_ERR_UNSUPPORTED, "pies_collide_field_props: more than PIES_FIELD_PROP_MAX (64) props");
-  for (uint32_t k = 0; k < n_props; ++k)
-    if (const char* what = field_prop_fault(s, props[k]))
-      return fail(s, PIES_ERR_INVALID, "pies_collide_field_props: prop " + std::to_string(k) + ": " + what);
-  if (n_props == 0) {
-    if (out_node_prop) std::fill(out_node_prop, out_node_prop + s->nodeCount(), PIES_PROP_NONE);
-    return PIES_OK;
-  }
-  if (s->device == PIES_DEVICE_NONE)
-    return fail(s, PIES_ERR_HIP, "host-only handle (PIES_DEVICE_NONE): field props meet the nodes on the device");
-  if (int rc = pies_internal_ensure_ready(s)) return rc;
+  if (int rc = edit_prelude(s, {"pies_collide_field_props", "prop", "field props", PIES_FIELD_PROP_MAX, "PIES_FIELD_PROP_MAX"},
+                            n_props, props, [&](uint32_t k) { return field_prop_fault(s, props[k]); }, nullptr, false,
+                            {out_impulse, out_torque, out_hits, out_node_prop});
+      rc != kEditGo)
+    return rc;
   const bool reaction = out_impulse || out_torque || out_hits;
-  if (s->dev.nd.n == 0) {  // no nodes: the call still waits for the queued work
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-    if (out_impulse) std::fill(out_impulse, out_impulse + 3ull * n_props, 0.0f);
-    if (out_torque) std::fill(out_torque, out_torque + 3ull * n_props, 0.0f);
-    if (out_hits) std::fill(out_hits, out_hits + n_props, 0u);
-    return PIES_OK;
-  }
 
   FieldPass P;
   if (int rc = prop_open_pass(s, n_props, reaction, out_node_prop != nullptr, &P.base)) return rc;

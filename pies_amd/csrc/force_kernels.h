@@ -9,29 +9,39 @@
 
 namespace pies {
 
-constexpr uint32_t kForceWaves = kPropTile / 64;  // words of ForcePass::affected per tile
+constexpr uint32_t kForceWaves = kPropTile / 64;  // words of VelocityScratch::affected per tile
+
+// What a velocity edit that reads triangles walks (forces with a wind, surface loads): the scene's triangles in DEVICE numbering
+// and the node -> triangle incidence by HOST node id, CSR, one entry per (triangle, corner) that names the node, ascending triangle
+// index within a row
+struct SurfaceIncidence {
+  const uint32_t* tri = nullptr;
+  uint32_t nTris = 0;
+  const uint32_t* incPtr = nullptr;  // nd.n + 1
+  const uint32_t* inc = nullptr;
+};
+
+// The scratch variant of a velocity edit (newVel nullptr: the evaluate launch writes nd.vel in place, which a list whose lanes
+// read other nodes' velocities must not): the new velocity per HOST node id, written for affected nodes only, and per wavefront of
+// the evaluate launch the lanes it affected
+struct VelocityScratch {
+  float4* newVel = nullptr;
+  uint64_t* affected = nullptr;  // kForceWaves words per tile
+};
 
 struct ForcePass {
   PropPass base;                         // nd, inv, nProps = the force count, the reaction's buffers (props and nodeProp unused)
   const pies_force_t* forces = nullptr;  // base.nProps records in HBM
   float dt = 0.0f;
-  // the wind (nullptr without one): the scene's triangles in DEVICE numbering and the node -> triangle incidence by HOST node id,
-  // CSR, one entry per (triangle, corner) that names the node, ascending triangle index within a row
-  const uint32_t* tri = nullptr;
-  const uint32_t* incPtr = nullptr;  // nd.n + 1
-  const uint32_t* inc = nullptr;
-  // the scratch variant (nullptr: the evaluate launch writes nd.vel in place, which a list with a wind must not): the new
-  // velocity per HOST node id, written for affected nodes only, and per wavefront of the evaluate launch the lanes it affected
-  float4* newVel = nullptr;
-  uint64_t* affected = nullptr;  // kForceWaves words per tile
+  SurfaceIncidence surface;  // the wind's (unset without one)
+  VelocityScratch scratch;   // a list with a wind must use it
 };
 
 // One lane per host node id, one workgroup per tile: the forces staged in LDS once, the node's position read, its velocity at the
 // first force that affects it; the reaction's tile sums when P.base.tileMask is set.
 void launch_force_evaluate(hipStream_t st, const ForcePass& P);
-// the scratch variant's second launch: newVel -> nd.vel for the affected nodes
-void launch_force_commit(hipStream_t st, const ForcePass& P);
-// the same launch for any pass that filled newVel and affected like the scratch variant does (load_kernels.hip)
-void launch_velocity_commit(hipStream_t st, const NodeArrays& nd, const uint32_t* inv, const float4* newVel, const uint64_t* affected);
+// The second launch of any velocity edit's scratch variant (forces, surface loads): newVel -> nd.vel for the affected nodes.
+// Nothing without a scratch array.
+void launch_velocity_commit(hipStream_t st, const NodeArrays& nd, const uint32_t* inv, const VelocityScratch& scratch);
 
 }  // namespace pies

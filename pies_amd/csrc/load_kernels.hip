@@ -9,37 +9,28 @@
 //  k_load_fold      one workgroup per load: the records of the tiles its range meets, 256 slots at a time through LDS, added in
 //                   ascending tile index by two lanes; then V, A and the pressure (load_state) to HBM, where the evaluate launch
 //                   reads them - the gas pressure never visits the host.
-//  k_load_evaluate  k_force_evaluate's shape: one lane per HOST node id, one workgroup per tile of 256 ids, records and states
-//                   staged in LDS and read as wave-wide broadcasts.  A lane walks its row of the node -> triangle incidence once
-//                   per load whose range the row reaches, skips the entries outside the range and recomputes each incident
-//                   triangle's F: the same F on the same operands in every lane that shares the triangle, no atomics and no
-//                   per-triangle buffer.  Positions are never written, so a list without a fluid drag reads nothing another lane
-//                   writes and stores in place; a drag reads the corners' velocities, and its list writes newVel[host id] and
-//                   the wave's ballot, which k_force_commit (force_kernels.hip) commits.  Second pass, only when the host asked
-//                   for the reaction: prop_tile_sums.h, shared with the props and the forces.
+//  k_load_evaluate  a velocity edit (node_edit_device.h: velocity_edit_pass) with records and states staged in LDS; only a node
+//                   with a row in the node -> triangle incidence is movable.  A lane walks its row once per load whose range
+//                   the row reaches, skips the entries outside the range and recomputes each incident triangle's F: the same F
+//                   on the same operands in every lane that shares the triangle, no atomics and no per-triangle buffer.
+//                   Positions are never written, so a list without a fluid drag reads nothing another lane writes and stores
+//                   in place; a drag reads the corners' velocities, and its list takes the scratch variant, which
+//                   k_force_commit (force_kernels.hip) commits.
 // Built with -ffp-contract=off like the rest of the library: the arithmetic is the IEEE sequence written in load_rule.h.
 #include "load_kernels.h"
 
 #include "load_rule.h"
-#include "prop_tile_sums.h"
+#include "node_edit_device.h"
 
 namespace pies {
 namespace {
 
-constexpr uint32_t kLoadWords = sizeof(pies_surface_load_t) / sizeof(uint32_t);
 constexpr uint32_t kLoadBatch = 8;  // loads per trip through LDS in k_load_measure
 static_assert(sizeof(pies_surface_load_t) == 64, "pies_surface_load_t is 16 words without padding");
 static_assert(sizeof(LoadState) == 16, "LoadState is 4 words");
+static_assert(kLoadTile == kPropTile, "k_load_measure stages its records like the edit kernels");
 static_assert(PIES_LOAD_MAX <= PIES_PROP_MAX, "the reaction's buffers and the 64-bit tile word are the props'");
 static_assert(PIES_LOAD_MAX % kLoadBatch == 0 && 2 * kLoadBatch <= 64, "one wavefront adds a batch's columns");
-
-PIES_DEV V3 xyz(const float4& a) { return V3{a.x, a.y, a.z}; }
-
-PIES_DEV void stage_loads(pies_surface_load_t* dst, const pies_surface_load_t* src, uint32_t n) {
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
-  uint32_t* d = reinterpret_cast<uint32_t*>(dst);
-  for (uint32_t k = threadIdx.x; k < n * kLoadWords; k += blockDim.x) d[k] = s[k];
-}
 
 // whether triangle t is of L's range / whether the tile is met by it (count is resolved: first + count <= the container's size)
 PIES_DEV bool load_holds(const pies_surface_load_t& L, uint32_t t) { return t >= L.first && t - L.first < L.count; }
@@ -55,16 +46,16 @@ __global__ void __launch_bounds__(kLoadTile) k_load_measure(LoadPass P) {
   const uint32_t tid = threadIdx.x, slot = blockIdx.x, n = P.base.nProps;
   const uint32_t tile = P.tiles[slot];
   const uint32_t t = tile * kLoadTile + tid;
-  stage_loads(loads, P.loads, n);
+  stage_records(loads, P.loads, n);
   __syncthreads();
   if (tid < n && loads[tid].count) {  // (an empty range names no triangle)
-    const float4 o = P.base.nd.pos[P.tri[3ull * loads[tid].first]];
+    const float4 o = P.base.nd.pos[P.surface.tri[3ull * loads[tid].first]];
     origin[tid][0] = o.x, origin[tid][1] = o.y, origin[tid][2] = o.z;
   }
-  const bool live = t < P.nTris;
+  const bool live = t < P.surface.nTris;
   V3 a{}, b{}, c{};
   if (live) {
-    const uint32_t* id = P.tri + 3ull * t;
+    const uint32_t* id = P.surface.tri + 3ull * t;
     a = xyz(P.base.nd.pos[id[0]]);
     b = xyz(P.base.nd.pos[id[1]]);
     c = xyz(P.base.nd.pos[id[2]]);
@@ -128,36 +119,17 @@ __global__ void __launch_bounds__(kPropTile) k_load_evaluate(LoadPass F) {
   __shared__ LoadState states[PIES_LOAD_MAX];
   __shared__ PropTileLds lds;  // second pass
   const PropPass& P = F.base;
-  const uint32_t tid = threadIdx.x, tile = blockIdx.x;
-  const uint32_t h = tile * kPropTile + tid;  // host id
-  stage_loads(loads, F.loads, P.nProps);
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(F.state);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(states);
-    for (uint32_t k = tid; k < P.nProps * 4u; k += kPropTile) dst[k] = src[k];
-  }
+  const SurfaceIncidence& I = F.surface;
+  stage_records(loads, F.loads, P.nProps);
+  stage_records(states, F.state, P.nProps);
   __syncthreads();
-  const bool live = h < P.nd.n;  // (no early return: every lane meets the barriers)
-  uint32_t i = 0, rowBegin = 0, rowEnd = 0, rowFirst = 0, rowLast = 0;
-  V3 p{}, v{};
-  float w = 0.0f, velW = 0.0f;
-  bool movable = false, haveVel = false;
-  if (live) {
-    i = P.inv ? P.inv[h] : h;
-    const float4 p4 = P.nd.pos[i];
-    p = xyz(p4);
-    w = p4.w;
-    rowBegin = F.incPtr[h], rowEnd = F.incPtr[h + 1];
-    movable = !(w == 0.0f) && rowBegin < rowEnd;
-    if (movable) rowFirst = F.inc[rowBegin], rowLast = F.inc[rowEnd - 1];  // (a row ascends)
+  EditLane lane = edit_lane(P);
+  uint32_t rowBegin = 0, rowEnd = 0, rowFirst = 0, rowLast = 0;
+  if (lane.live) {
+    rowBegin = I.incPtr[lane.h], rowEnd = I.incPtr[lane.h + 1];
+    lane.movable = lane.movable && rowBegin < rowEnd;  // (a node of no triangle bears no load)
+    if (lane.movable) rowFirst = I.inc[rowBegin], rowLast = I.inc[rowEnd - 1];  // (a row ascends)
   }
-  auto need_velocity = [&]() {
-    if (haveVel) return;
-    const float4 v4 = P.nd.vel[i];
-    v = xyz(v4);
-    velW = v4.w;
-    haveVel = true;
-  };
   // dv of load k on this lane's (movable) node from the state the call found; false: not affected
   auto evaluate = [&](uint32_t k, V3& dv) -> bool {
     const pies_surface_load_t& L = loads[k];
@@ -168,55 +140,27 @@ __global__ void __launch_bounds__(kPropTile) k_load_evaluate(LoadPass F) {
     bool hit = false;
     dv = V3{0.0f, 0.0f, 0.0f};
     for (uint32_t e = rowBegin; e < rowEnd; ++e) {
-      const uint32_t t = F.inc[e];
+      const uint32_t t = I.inc[e];
       if (!load_holds(L, t)) continue;
       uint32_t ia, ib, ic;
-      load_corners(L, F.tri + 3ull * t, ia, ib, ic);
+      load_corners(L, I.tri + 3ull * t, ia, ib, ic);
       V3 N;
       float nn, pressure;
       if (!load_face(L, S, xyz(P.nd.pos[ia]), xyz(P.nd.pos[ib]), xyz(P.nd.pos[ic]), N, nn, pressure)) continue;
       V3 force = load_force(N, pressure);
       if (drag) force = load_force_drag(L, force, nn, xyz(P.nd.vel[ia]), xyz(P.nd.vel[ib]), xyz(P.nd.vel[ic]));
-      dv = add(dv, load_share(force, F.dt, w));
+      dv = add(dv, load_share(force, F.dt, lane.w));
       hit = true;
     }
-    if (hit) need_velocity();
+    if (hit) need_velocity(P, lane);
     return hit;
   };
-
-  // ---- first pass: the edit ----
-  uint64_t affectedBy = 0;
-  if (movable) {
-    V3 sum{0.0f, 0.0f, 0.0f};
-    for (uint32_t k = 0; k < P.nProps; ++k) {
-      V3 dv;
-      if (!evaluate(k, dv)) continue;
-      sum = add(sum, dv);
-      affectedBy |= 1ull << k;
-    }
-    if (affectedBy) {
-      const V3 v1 = add(v, sum);
-      if (kScratch) F.newVel[h] = make_float4(v1.x, v1.y, v1.z, velW);
-      else P.nd.vel[i] = make_float4(v1.x, v1.y, v1.z, velW);
-    }
-  }
-  if (kScratch) {
-    const uint64_t ballot = __builtin_amdgcn_ballot_w64(affectedBy != 0);
-    if ((tid & 63u) == 0) F.affected[tile * kForceWaves + (tid >> 6)] = ballot;
-  }
-  if (!P.tileMask) return;  // (uniform: a kernel argument)
-
-  // ---- second pass: the tile's set of loads and its sums (prop_tile_sums.h) ----
-  prop_tile_sums(lds, P.tileMask, P.tileSums, P.nProps, affectedBy, [&](uint32_t k, PropTouch& T) {
-    V3 dv{};
-    (void)evaluate(k, dv);  // the change of the first pass, once more
-    T.impulse = scale(dv, 1.0f / w);
-    T.torque = cross(sub(p, load3(loads[k].point)), T.impulse);
-  });
+  velocity_edit_pass<kScratch>(P, F.scratch, lds, lane, evaluate, [&](uint32_t k) { return load3(loads[k].point); });
 }
 
 bool launchable(const LoadPass& P) {
-  return P.base.nd.n && P.nTris && P.base.nProps && P.base.nProps <= PIES_LOAD_MAX && P.loads && P.tri && P.incPtr && P.inc && P.state;
+  const SurfaceIncidence& I = P.surface;
+  return P.base.nd.n && I.nTris && P.base.nProps && P.base.nProps <= PIES_LOAD_MAX && P.loads && I.tri && I.incPtr && I.inc && P.state;
 }
 
 }  // namespace
@@ -234,13 +178,8 @@ void launch_load_fold(hipStream_t st, const LoadPass& P) {
 void launch_load_evaluate(hipStream_t st, const LoadPass& P) {
   if (!launchable(P)) return;
   const dim3 grid(prop_tiles(P.base.nd.n)), block(kPropTile);
-  if (P.newVel) hipLaunchKernelGGL(k_load_evaluate<true>, grid, block, 0, st, P);
+  if (P.scratch.newVel) hipLaunchKernelGGL(k_load_evaluate<true>, grid, block, 0, st, P);
   else hipLaunchKernelGGL(k_load_evaluate<false>, grid, block, 0, st, P);
-}
-
-void launch_load_commit(hipStream_t st, const LoadPass& P) {
-  if (!launchable(P) || !P.newVel) return;
-  launch_velocity_commit(st, P.base.nd, P.base.inv, P.newVel, P.affected);
 }
 
 }  // namespace pies

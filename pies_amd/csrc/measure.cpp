@@ -70,16 +70,10 @@ int pies_measure_elements(pies_solver_t* s, int type, uint32_t first, uint32_t n
   if (int rc = measure_stage(s, which)) return rc;
   RayBuffers& B = s->ray;
   const uint32_t tiles = measure_tiles(first, n);
-  if (out && B.measureOutCap < n) {
-    B.measureOutCap = 0;
-    if (int rc = ray_grow(s, n, &B.measureOut)) return rc;
-    B.measureOutCap = n;
-  }
-  if (summary && B.measureTileCap < tiles) {
-    B.measureTileCap = 0;
-    if (int rc = ray_grow(s, static_cast<size_t>(tiles) * kMeasureTileWords, &B.measureTileRecords)) return rc;
-    B.measureTileCap = tiles;
-  }
+  if (out)
+    if (int rc = ray_reserve(s, n, &B.measureOut, &B.measureOutCap)) return rc;
+  if (summary)
+    if (int rc = ray_reserve(s, tiles, &B.measureTileRecords, &B.measureTileCap, kMeasureTileWords)) return rc;
   if (summary && !B.measureSummary)
     if (int rc = ray_grow(s, kMeasureTileWords, &B.measureSummary)) return rc;
 
@@ -146,11 +140,7 @@ int pies_measure_nodes(pies_solver_t* s, uint32_t n_ranges, const uint32_t* rang
   if (!B.measureNodeOut)
     if (int rc = ray_grow(s, static_cast<size_t>(PIES_MEASURE_RANGE_MAX) * kNodeSumWords, &B.measureNodeOut)) return rc;
   const size_t tileRecords = static_cast<size_t>(prop_tiles(n)) * n_ranges;
-  if (B.measureNodeTileCap < tileRecords) {
-    B.measureNodeTileCap = 0;
-    if (int rc = ray_grow(s, tileRecords * kNodeSumWords, &B.measureNodeTileSums)) return rc;
-    B.measureNodeTileCap = tileRecords;
-  }
+  if (int rc = ray_reserve(s, tileRecords, &B.measureNodeTileSums, &B.measureNodeTileCap, kNodeSumWords)) return rc;
   HIP_TRY(s, hipMemcpyAsync(B.measureRanges, records, n_ranges * sizeof(MeasureRange), hipMemcpyHostToDevice, s->stream));
   NodeSumPass P;
   P.nd = s->dev.nd;

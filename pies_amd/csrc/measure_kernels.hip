@@ -193,11 +193,7 @@ __global__ void __launch_bounds__(kPropTile) k_measure_nodes(NodeSumPass P) {
   __shared__ NodeTileLds lds;
   const uint32_t tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x;
   const uint32_t h = tile * kPropTile + tid;  // host id
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(P.ranges);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(lds.ranges);
-    for (uint32_t k = tid; k < P.nRanges * (sizeof(MeasureRange) / sizeof(uint32_t)); k += kPropTile) dst[k] = src[k];
-  }
+  stage_records(lds.ranges, P.ranges, P.nRanges);
   __syncthreads();
   const bool live = h < P.nd.n;  // (no early return: every lane meets the barriers)
   float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v = p;

@@ -71,16 +71,9 @@ int near_launch(pies_solver* s, const RayTarget& T, const float* dPoints, uint32
 
   // ---- buffers ----
   const size_t keys = (static_cast<size_t>(batch) * perPoint + sizeof(uint64_t) - 1) / sizeof(uint64_t);
-  if (B.partialCap < keys) {
-    B.partialCap = 0;
-    if (int rc = ray_grow(s, keys, &B.partial)) return rc;
-    B.partialCap = keys;
-  }
-  if (distancePass && !narrow && B.recordCap < T.nTris) {
-    B.recordCap = 0;
-    if (int rc = ray_grow(s, 3ull * T.nTris, &B.records)) return rc;
-    B.recordCap = T.nTris;
-  }
+  if (int rc = ray_reserve(s, keys, &B.partial, &B.partialCap)) return rc;
+  if (distancePass && !narrow)
+    if (int rc = ray_reserve(s, T.nTris, &B.records, &B.recordCap, 3)) return rc;
 
   // ---- the launches: per batch the distance pass, then the winding pass (the stream orders their use of `partial`) ----
   if (distancePass && !narrow) launch_ray_stage(s->stream, T, B.records);

@@ -175,16 +175,9 @@ int pies_raycast(pies_solver_t* s, int target, uint32_t skin, uint32_t n_rays, c
     B.rayCap = n_rays;
   }
   const size_t keys = static_cast<size_t>(batch) * parts;
-  if (B.partialCap < keys) {
-    B.partialCap = 0;
-    if (int rc = ray_grow(s, keys, &B.partial)) return rc;
-    B.partialCap = keys;
-  }
-  if (!narrow && B.recordCap < T.nTris) {
-    B.recordCap = 0;
-    if (int rc = ray_grow(s, 3ull * T.nTris, &B.records)) return rc;
-    B.recordCap = T.nTris;
-  }
+  if (int rc = ray_reserve(s, keys, &B.partial, &B.partialCap)) return rc;
+  if (!narrow)
+    if (int rc = ray_reserve(s, T.nTris, &B.records, &B.recordCap, 3)) return rc;
   float *dOrigins = B.rays, *dDirections = B.rays + 3ull * n_rays;
   HIP_TRY(s, hipMemcpyAsync(dOrigins, origins, 3ull * n_rays * sizeof(float), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(s, hipMemcpyAsync(dDirections, directions, 3ull * n_rays * sizeof(float), hipMemcpyHostToDevice, s->stream));

@@ -22,6 +22,8 @@
 
 namespace pies {
 
+struct VelocityScratch;  // force_kernels.h
+
 struct HostPosition {
   uint32_t id;
   float target[3];
@@ -466,6 +468,14 @@ template <class T> int ray_grow(pies_solver* s, size_t count, T** d) {
   *d = static_cast<T*>(p);
   return rc;
 }
+// ... when its capacity *cap (in items of `each` elements) is below count; the capacity is 0 while the buffer is being replaced
+template <class T> int ray_reserve(pies_solver* s, size_t count, T** d, size_t* cap, size_t each = 1) {
+  if (*cap >= count) return PIES_OK;
+  *cap = 0;
+  if (int rc = ray_grow(s, count * each, d)) return rc;
+  *cap = count;
+  return PIES_OK;
+}
 int ray_open_target(pies_solver* s, int target, uint32_t skin, pies::RayTarget* out);
 // raycast.cpp, for forces.cpp : the node -> triangle incidence of the scene's triangles in s->ray (built once per pies_finalize)
 int ray_build_incidence(pies_solver* s);
@@ -478,6 +488,40 @@ int near_launch(pies_solver* s, const pies::RayTarget& T, const float* dPoints, 
 int prop_open_pass(pies_solver* s, uint32_t nProps, bool reaction, bool nodeProp, pies::PropPass* P);
 int prop_close_pass(pies_solver* s, const pies::PropPass& P, float* outImpulse, float* outTorque, uint32_t* outHits, uint32_t* outNodeProp,
                     uint32_t staleBits = 7u);
+// props.cpp : what every between-tick edit of node state (props.cpp, fields.cpp, forces.cpp, loads.cpp) does before its own work,
+// in this order: the list is not NULL and has at most max (maxName) records, no record has a fault (fault(k): nullptr, or what is
+// wrong with record k), dt (when given) is finite and >= 0; an empty list returns - nodeProp, when given, filled with
+// PIES_PROP_NONE -; the handle has a device and HBM holds the scene; in a scene without nodes, or `idle` (it lacks what else the
+// records act on), the call waits for the queued work and zeroes its outputs.  Returns kEditGo when the caller has work to do,
+// else what the entry point returns.  Nothing is formatted or allocated on the way to kEditGo.
+struct EditNames {
+  const char *call, *noun, *subject;  // the entry point; a record in messages ("prop"); what meets the nodes ("field props")
+  uint32_t max;
+  const char* maxName;
+};
+struct EditOutputs {  // each may be nullptr
+  float *impulse, *torque;  // 3 per record
+  uint32_t* counts;         // 1 per record
+  uint32_t* nodeProp = nullptr;                // 1 per node
+  float *volume = nullptr, *area = nullptr;    // 1 per record
+};
+constexpr int kEditGo = -1;
+// (the part after the records' own checks: record `bad` has the fault `what`, or what == nullptr)
+int edit_prelude_checked(pies_solver* s, const EditNames& names, uint32_t count, const void* records, uint32_t bad, const char* what,
+                         const float* dt, bool idle, const EditOutputs& out);
+template <class Fault>
+int edit_prelude(pies_solver* s, const EditNames& names, uint32_t count, const void* records, Fault&& fault, const float* dt, bool idle,
+                 const EditOutputs& out) {
+  uint32_t bad = 0;
+  const char* what = nullptr;
+  if (records && count <= names.max)  // (else the list itself is refused first)
+    for (; bad < count && !(what = fault(bad)); ++bad) {}
+  return edit_prelude_checked(s, names, count, records, bad, what, dt, idle, out);
+}
+// ... `*scratch = true` when the tuning variable says "scratch"; "inplace" leaves the choice to the list, anything else is an error
+int edit_variant(pies_solver* s, const char* variable, const char* call, bool* scratch);
+// ... the scratch variant's arrays of s->ray for the scene's nodes (forces and loads share them: one call runs at a time)
+int edit_velocity_scratch(pies_solver* s, pies::VelocityScratch* out);
 // node_order.cpp : decides s->nodeOrder for the scene as it stands (host logic of pies_finalize, device handles and host-only ones)
 void decide_node_order(pies_solver* s);
 // For its lifetime the host containers of `s` (node arrays, constraint ids, groups, triangles) hold the internal numbering of

@@ -101,6 +101,18 @@ def test_single_triangle(pies):
     assert out[2].tolist() == [0] and not out[0].any() and same_bits(bare.velocities, vel)
 
 
+def test_a_scene_without_nodes(pies):
+    """a finalised handle without nodes: OK, and every reaction output the host hands in is zeroed (no kernel runs)"""
+    empty = pies.Solver(pies.Options(solver=pies.PBD))
+    forces = [pies.Force.radial((0.0, 1.0, 0.0), 2.0), pies.Force.directional((0.0, 0.0, 3.0))]
+    impulse, torque, nodes = np.full((2, 3), 7, F), np.full((2, 3), 7, F), np.full(2, 7, np.uint32)
+    pf, pu = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    rc = pies.load().pies_apply_forces(empty._h, 2, (pies.Force * 2)(*forces), DT, impulse.ctypes.data_as(pf), torque.ctypes.data_as(pf),
+                                       nodes.ctypes.data_as(pu))
+    assert rc == pies.OK and not impulse.any() and not torque.any() and not nodes.any()
+    assert all(not x.any() for x in empty.apply_forces(forces, DT))
+
+
 def test_outputs_are_optional_and_calls_repeat(pies, tune):
     pos, vel, inv_mass, forces = make_scene(600, 64)
     full, bare, again, some = (loose(pies, pos, vel, inv_mass) for _ in range(4))

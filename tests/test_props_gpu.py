@@ -86,6 +86,19 @@ def test_outputs_are_optional_and_calls_repeat(pies):
     assert same_bits(got[0], want[3]) and same_bits(got[1], want[4]) and np.array_equal(got[2], want[5]) and np.array_equal(got[3], want[6])
 
 
+def test_a_scene_without_nodes(pies):
+    """a finalised handle without nodes: OK, and every reaction output the host hands in is zeroed (no kernel runs)"""
+    empty = pies.Solver(pies.Options(solver=pies.PBD))
+    props = make_props(2, 0)
+    impulse, torque, hits = np.full((2, 3), 7, F), np.full((2, 3), 7, F), np.full(2, 7, np.uint32)
+    pf, pu = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    rc = pies.load().pies_collide_props(empty._h, 2, (pies.Prop * 2)(*props), impulse.ctypes.data_as(pf), torque.ctypes.data_as(pf),
+                                        hits.ctypes.data_as(pu), None)
+    assert rc == pies.OK and not impulse.any() and not torque.any() and not hits.any()
+    out = empty.collide_props(props, node_prop=True)
+    assert all(not x.any() for x in out[:3]) and out[3].shape == (0,)
+
+
 def tet_box(pies, solver, schedule=None):
     g = pies.Solver(pies.Options(solver=solver))
     if schedule is not None:
