@@ -659,9 +659,9 @@ int pies_collision_pairs(pies_solver_t* s, uint64_t* pairs) {
   if (!s->dev.hash.counters) return PIES_OK;
   uint32_t v = 0;
   HIP_TRY(s, hipSetDevice(s->device));
-  HIP_TRY(s, hipMemcpyAsync(&v, s->dev.hash.counters + 31, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipMemcpyAsync(&v, s->dev.hash.counters + kCounterPairs, sizeof(v), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  HIP_TRY(s, hipMemsetAsync(s->dev.hash.counters + 31, 0, sizeof(v), s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dev.hash.counters + kCounterPairs, 0, sizeof(v), s->stream));
   *pairs = v;
   return PIES_OK;
 }

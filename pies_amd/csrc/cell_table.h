@@ -1,4 +1,4 @@
-// Exact-key open-addressing cell table shared by the node grid (hash_kernels.hip) and the triangle grid
+// Exact-key open-addressing cell table shared by the node grid (grid_build.hip) and the triangle grid
 // (tri_lists.hip): a cell id (three signed 21-bit coordinates) is packed into 63 bits and compared in
 // full, so two different cells never alias -- the reference's hash map is exact as well.
 #pragma once

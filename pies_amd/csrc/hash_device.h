@@ -1,5 +1,6 @@
-// Device-side helpers of the node grid shared by hash_kernels.hip (grid build, group-ordered and reference-ordered
-// resolve) and pair_lists.hip / pair_levels.hip / pair_turns.hip (resolve by dependency levels, through pair_device.h).
+// Device-side helpers of the node grid shared by grid_build.hip (the build), group_resolve.hip (group-ordered and
+// reference-ordered resolve) and pair_lists.hip / pair_levels.hip / pair_turns.hip (resolve by dependency levels, through
+// pair_device.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,7 @@ struct GridBox {
   bool empty;
 };
 constexpr uint32_t kRadixMaxDigit = 11;  // bits per pass at most (2048 bins)
+PIES_DEV uint32_t axis_bits(uint32_t ext) { return ext ? 32u - static_cast<uint32_t>(__builtin_clz(ext)) : 0u; }  // key bits of an axis from its extent (max - min)
 PIES_DEV GridBox grid_box(const uint32_t* __restrict__ counters) {
   GridBox B;
   B.empty = false;
@@ -35,11 +37,11 @@ PIES_DEV GridBox grid_box(const uint32_t* __restrict__ counters) {
     const int mx = static_cast<int>(counters[kCounterBoxMax + a]);
     if (mx < B.mn[a]) B.empty = true;
     B.ext[a] = B.empty ? 0u : static_cast<uint32_t>(mx - B.mn[a]);
-    B.bits[a] = B.ext[a] ? 32u - static_cast<uint32_t>(__builtin_clz(B.ext[a])) : 0u;
+    B.bits[a] = axis_bits(B.ext[a]);
   }
   // The key's bits are dealt evenly to the passes the host captured (launch_hash_build): a box of 17 key bits is sorted in two
   // passes of 9 bits, not in three of 8 with five more launches that find nothing to do.  More bits than kRadixMaxDigit per
-  // captured pass is latched by k_grid_box (the host follows the box at its synchronisations, with bits to spare).
+  // captured pass is latched by grid_box_reduce (grid_build.hip; the host follows the box at its synchronisations, with bits to spare).
   B.passes = counters[kCounterSortPasses];
   const uint32_t total = B.bits[0] + B.bits[1] + B.bits[2];
   B.digit = B.passes ? min(kRadixMaxDigit, (total + B.passes - 1u) / B.passes) : 0u;

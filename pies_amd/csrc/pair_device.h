@@ -1,13 +1,14 @@
 // Device code shared by the files of the node-node resolve by dependency levels (pair_lists.hip: what both orders share;
 // pair_levels.hip: the pair order; pair_turns.hip: the reference's order by turns): the pair key, a node's record and the protocol
-// by which the lanes of a level read and move it, the forms of one visit, excursions, the frontier and its appends, the opening of
-// a level, the grid barrier and the loop that finishes the remaining levels of a pass in one launch.
+// by which the lanes of a level read and move it, excursions, the frontier and its appends, the opening of a level, the grid barrier
+// and the loop that finishes the remaining levels of a pass in one launch.  (One visit, in every lane layout: pair_rule.h.)
 #pragma once
 #include <cstdint>
 
 #include "dev_math.h"
 #include "hash_device.h"
 #include "pair_kernels.h"
+#include "pair_rule.h"
 
 namespace pies {
 
@@ -53,56 +54,6 @@ PIES_DEV uint64_t pair_key_of(uint32_t i, uint32_t j, float pix, float piy, floa
   return pair_key(low ? i : j, low ? j : i, low ? pix : pjx, low ? piy : pjy, low ? piz : pjz, low ? pjx : pix, low ? pjy : piy, low ? pjz : piz);
 }
 
-PIES_DEV float lane_value(float v, uint32_t srcLane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), static_cast<int>(srcLane))); }
-
-// ---- one visit (Solver.cpp:88-126), all of it in one lane -------------------------------------------------------------
-struct NodeState {
-  float px, py, pz, w, vx, vy, vz, r;
-};
-// node a visits node b (a != b).  Returns whether the pair was resolved.
-PIES_DEV bool visit(NodeState& a, NodeState& b, float friction, float staticThreshold) {
-  const float dx = b.px - a.px, dy = b.py - a.py, dz = b.pz - a.pz;
-  const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-  const float disp = a.r + b.r - dist;
-  if (!(disp > 0.0f)) return false;
-  float ux = 1.0f, uy = 0.0f, uz = 0.0f;
-  if (dist > 0.00001f) { ux = dx / dist; uy = dy / dist; uz = dz / dist; }
-  const float wSum = a.w + b.w;
-  const float sa = 0.85f * -disp, sb = 0.85f * disp;
-  const float rx = b.vx - a.vx, ry = b.vy - a.vy, rz = b.vz - a.vz;
-  const float rd = rx * ux + ry * uy + rz * uz;
-  const float qx = rx - rd * ux, qy = ry - rd * uy, qz = rz - rd * uz;
-  float fr = friction;
-  if (staticThreshold > 0.0f)  // sqrt(x) < t is false for every t <= 0
-    if (sqrtf(qx * qx + qy * qy + qz * qz) < staticThreshold) fr = 1.0f;
-  a.px += ((sa * ux) * a.w) / wSum; a.py += ((sa * uy) * a.w) / wSum; a.pz += ((sa * uz) * a.w) / wSum;
-  b.px += ((sb * ux) * b.w) / wSum; b.py += ((sb * uy) * b.w) / wSum; b.pz += ((sb * uz) * b.w) / wSum;
-  a.vx += ((-fr * qx) * a.w) / wSum; a.vy += ((-fr * qy) * a.w) / wSum; a.vz += ((-fr * qz) * a.w) / wSum;
-  b.vx += ((fr * qx) * b.w) / wSum; b.vy += ((fr * qy) * b.w) / wSum; b.vz += ((fr * qz) * b.w) / wSum;
-  return true;
-}
-// a node meets itself (quirk Q3): `other` aliases `node`, so the second update of each line sees the first
-PIES_DEV bool visit_self(NodeState& a, float friction, float staticThreshold) {
-  const float dx = a.px - a.px, dy = a.py - a.py, dz = a.pz - a.pz;
-  const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-  const float disp = a.r + a.r - dist;
-  if (!(disp > 0.0f)) return false;
-  float ux = 1.0f, uy = 0.0f, uz = 0.0f;
-  if (dist > 0.00001f) { ux = dx / dist; uy = dy / dist; uz = dz / dist; }
-  const float wSum = a.w + a.w;
-  const float sa = 0.85f * -disp, sb = 0.85f * disp;
-  const float rx = a.vx - a.vx, ry = a.vy - a.vy, rz = a.vz - a.vz;
-  const float rd = rx * ux + ry * uy + rz * uz;
-  const float qx = rx - rd * ux, qy = ry - rd * uy, qz = rz - rd * uz;
-  float fr = friction;
-  if (staticThreshold > 0.0f)
-    if (sqrtf(qx * qx + qy * qy + qz * qz) < staticThreshold) fr = 1.0f;
-  a.px += ((sa * ux) * a.w) / wSum; a.py += ((sa * uy) * a.w) / wSum; a.pz += ((sa * uz) * a.w) / wSum;
-  a.px += ((sb * ux) * a.w) / wSum; a.py += ((sb * uy) * a.w) / wSum; a.pz += ((sb * uz) * a.w) / wSum;
-  a.vx += ((-fr * qx) * a.w) / wSum; a.vy += ((-fr * qy) * a.w) / wSum; a.vz += ((-fr * qz) * a.w) / wSum;
-  a.vx += ((fr * qx) * a.w) / wSum; a.vy += ((fr * qy) * a.w) / wSum; a.vz += ((fr * qz) * a.w) / wSum;
-  return true;
-}
 // ---- the pass's own node records: 64 bytes = one cache line per node ------------------------------------------------------
 //   [0] x, y, z, invMass          [1] vx, vy, vz, radius          [2] position when the grid was built (x, y, z), slack
 //   [3] first list entry, entries, current entry | round in which the node got there << 16, the current entry itself
@@ -167,90 +118,7 @@ PIES_DEV bool move_on(float4* node, uint32_t i, const uint4 r, uint32_t nextEntr
   return (r.z & 0xffffu) + 1u < r.y;
 }
 
-// ---- one visit with FOUR LANES PER PAIR (pair_levels.hip: pair_level4) -----------------------------------------------------
-PIES_DEV float quad_lane(float v, int j) {  // the value of lane j (0-3) of the lane's quad
-  switch (j) {
-    case 0: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xf, 0xf, false));
-    case 1: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x55, 0xf, 0xf, false));
-    case 2: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xaa, 0xf, 0xf, false));
-    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xff, 0xf, 0xf, false));
-  }
-}
-PIES_DEV float quad_sum3(float t) { return (quad_lane(t, 0) + quad_lane(t, 1)) + quad_lane(t, 2); }  // x + y + z in visit()'s order
-struct QuadNode {
-  float p, v;  // component k of position and velocity
-  float w, r;  // inverse mass, radius (every lane)
-};
-// node a visits node b (visit(), one component per lane; the result of the overlap test is the same in the quad's lanes)
-PIES_DEV bool visit_quad(QuadNode& a, QuadNode& b, int k, float friction, float staticThreshold) {
-  const float d = b.p - a.p;
-  const float dist = sqrtf(quad_sum3(d * d));
-  const float disp = a.r + b.r - dist;
-  if (!(disp > 0.0f)) return false;
-  float u = k == 0 ? 1.0f : 0.0f;
-  if (dist > 0.00001f) u = d / dist;
-  const float wSum = a.w + b.w;
-  const float sa = 0.85f * -disp, sb = 0.85f * disp;
-  const float r = b.v - a.v;
-  const float rd = quad_sum3(r * u);
-  const float q = r - rd * u;
-  float fr = friction;
-  if (staticThreshold > 0.0f)  // sqrt(x) < t is false for every t <= 0
-    if (sqrtf(quad_sum3(q * q)) < staticThreshold) fr = 1.0f;
-  a.p += ((sa * u) * a.w) / wSum;
-  b.p += ((sb * u) * b.w) / wSum;
-  a.v += ((-fr * q) * a.w) / wSum;
-  b.v += ((fr * q) * b.w) / wSum;
-  return true;
-}
-PIES_DEV float comp4(const float4 v, int k) { return k == 1 ? v.y : (k == 2 ? v.z : v.x); }  // (lane 3: a copy of component 0)
-
-// ---- one visit ACROSS A WAVEFRONT (pair_turns.hip: turn_cell) ---------------------------------------------------------------
-// One resolved visit of a turn (Solver.cpp:92-125) with its fifteen divisions dealt to the lanes: `a` (wave uniform) visits the node
-// held by lane `src` (self: itself).  visit() runs all of it in one lane - ~350 instructions, a turn of config 4 resolves ~20 visits
-// one after the other: 15 us of a 45-us level.  Here lane t computes ONE quotient (the three components of the direction on lanes
-// 0-2, then the twelve corrections ((coef * vec_k) * mass) / wSum on lanes 0-11) and the quotients are broadcast: the same operations
-// on the same operands in the same order as visit() / visit_self(), so the same bits (k_collide_reference's resolve_pair does the
-// same).  The overlap is known (the caller's test): the visit resolves.
-PIES_DEV float pick3(int k, float x, float y, float z) { return k == 0 ? x : (k == 1 ? y : z); }
-PIES_DEV void visit_wide(NodeState& a, NodeState& b, uint32_t src, bool self, float friction, float staticThreshold, int lane) {
-  NodeState o = a;
-  if (!self) o = NodeState{lane_value(b.px, src), lane_value(b.py, src), lane_value(b.pz, src), lane_value(b.w, src),
-                           lane_value(b.vx, src), lane_value(b.vy, src), lane_value(b.vz, src), lane_value(b.r, src)};
-  const float dx = o.px - a.px, dy = o.py - a.py, dz = o.pz - a.pz;
-  const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-  const float disp = a.r + o.r - dist;
-  const int k3 = lane % 3, kind = (lane / 3) & 3;
-  float ux = 1.0f, uy = 0.0f, uz = 0.0f;
-  if (dist > 0.00001f) {
-    const float quot = pick3(k3, dx, dy, dz) / dist;
-    ux = lane_value(quot, 0); uy = lane_value(quot, 1); uz = lane_value(quot, 2);
-  }
-  const float wSum = a.w + o.w;
-  const float sa = 0.85f * -disp, sb = 0.85f * disp;
-  const float rx = o.vx - a.vx, ry = o.vy - a.vy, rz = o.vz - a.vz;
-  const float rd = rx * ux + ry * uy + rz * uz;
-  const float qx = rx - rd * ux, qy = ry - rd * uy, qz = rz - rd * uz;
-  float fr = friction;
-  if (staticThreshold > 0.0f)  // sqrt(x) < t is false for every t <= 0
-    if (sqrtf(qx * qx + qy * qy + qz * qz) < staticThreshold) fr = 1.0f;
-  const float vec = kind < 2 ? pick3(k3, ux, uy, uz) : pick3(k3, qx, qy, qz);
-  const float coef = kind == 0 ? sa : (kind == 1 ? sb : (kind == 2 ? -fr : fr));
-  const float mass = (kind & 1) ? o.w : a.w;
-  const float corr = ((coef * vec) * mass) / wSum;
-  if (self) {  // (visit_self: the second update of each line sees the first)
-    a.px += lane_value(corr, 0); a.py += lane_value(corr, 1); a.pz += lane_value(corr, 2);
-    a.px += lane_value(corr, 3); a.py += lane_value(corr, 4); a.pz += lane_value(corr, 5);
-    a.vx += lane_value(corr, 6); a.vy += lane_value(corr, 7); a.vz += lane_value(corr, 8);
-    a.vx += lane_value(corr, 9); a.vy += lane_value(corr, 10); a.vz += lane_value(corr, 11);
-    return;
-  }
-  a.px += lane_value(corr, 0); a.py += lane_value(corr, 1); a.pz += lane_value(corr, 2);
-  o.px += lane_value(corr, 3); o.py += lane_value(corr, 4); o.pz += lane_value(corr, 5);
-  a.vx += lane_value(corr, 6); a.vy += lane_value(corr, 7); a.vz += lane_value(corr, 8);
-  o.vx += lane_value(corr, 9); o.vy += lane_value(corr, 10); o.vz += lane_value(corr, 11);
-  if (lane == static_cast<int>(src)) b = o;
-}
+PIES_DEV float comp4(const float4 v, int k) { return k == 1 ? v.y : (k == 2 ? v.z : v.x); }  // (a quad's lane 3: a copy of component 0)
 
 // The frontier of a round is kept as kPairLists sub-lists.  A wavefront works on chunks of 64 consecutive positions of their
 // concatenation and appends to the sub-list its chunk is dealt to (chunk index modulo kPairLists).

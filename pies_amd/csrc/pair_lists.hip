@@ -44,7 +44,7 @@ PIES_DEV uint32_t self_visits(const HashArrays& H, const PairArrays& P, uint32_t
   const int4 rg = H.rng[i];
   const uint32_t m = (rg.w & 0xff) * ((rg.w >> 8) & 0xff) * ((rg.w >> 16) & 0xff);
   uint32_t hits = 0;
-  for (uint32_t q = 0; q < m; ++q) hits += visit_self(a, friction, staticThreshold) ? 1u : 0u;
+  for (uint32_t q = 0; q < m; ++q) hits += visit(a, a, friction, staticThreshold) ? 1u : 0u;
   if (hits) note_excursion(P, i, a, p0);
   return hits;
 }

@@ -3,7 +3,7 @@
 // ======================================================================================================================
 // The reference's loop gives every node its turn in ascending index: the node's cell range is looked up from its LIVE position
 // (SpatialHash.h:101-106), the buckets of that range are walked in dx, dy, dz order and their nodes in ascending index, and every
-// overlapping visit is resolved at once.  k_collide_reference (hash_kernels.hip) runs that as one chain on one wavefront: 20 us
+// overlapping visit is resolved at once.  k_collide_reference (group_resolve.hip) runs that as one chain on one wavefront: 20 us
 // per node.  Here the same turns run by dependency levels:
 //   * who a turn can touch: the node's partners within reach when the grid was built (the pair order's filtered lists, sorted by
 //     INDEX here; a visit to anybody else is a miss as long as every node stays within its slack - the pair order's proof obligation,
@@ -52,8 +52,9 @@ PIES_DEV void turn_cell(NodeState& a, NodeState& b, bool inCell, uint32_t selfAt
     const unsigned long long hm = __ballot(hit);
     const uint32_t first = hm ? static_cast<uint32_t>(__builtin_ctzll(hm)) : 64u;
     if (selfAt != kTurnDone && selfAt <= first) {  // everything below the node's own place has missed: it meets itself
-      if (a.r + a.r > 0.0f) {  // (visit_self's test: the distance to itself is 0)
-        visit_wide(a, b, 0u, true, friction, staticThreshold, lane);
+      if (a.r + a.r > 0.0f) {  // (visit()'s test: the distance to itself is 0)
+        NodeState o = a;
+        visit_wide(a, o, true, friction, staticThreshold, lane);
         ++hits;
         aMoved = true;
       }
@@ -62,8 +63,9 @@ PIES_DEV void turn_cell(NodeState& a, NodeState& b, bool inCell, uint32_t selfAt
       continue;  // (its state may have changed: the lanes above test again)
     }
     if (first >= 64u) break;
-    visit_wide(a, b, first, false, friction, staticThreshold, lane);
-    if (lane == static_cast<int>(first)) bMoved = true;
+    NodeState o = lane_node(b, first);
+    visit_wide(a, o, false, friction, staticThreshold, lane);
+    if (lane == static_cast<int>(first)) { b = o; bMoved = true; }
     ++hits;
     aMoved = true;
     pending = first >= 63u ? 0ull : pending & ~((2ull << first) - 1ull);
@@ -95,7 +97,7 @@ PIES_DEV uint32_t run_turn(const HashArrays& H, const PairArrays& P, uint32_t i,
   int mx, my, mz;
   uint32_t lx, ly, lz;
   if (!node_range(a.px, a.py, a.pz, a.r, scale, mx, my, mz, lx, ly, lz)) {  // (the sequential loop stops there, Solver.cpp's would not: latched)
-    if (lane == 0) atomicOr(&H.counters[kCounterFlags], 1u);
+    if (lane == 0) atomicOr(&H.counters[kCounterFlags], kFailNonFinite);
     lx = ly = lz = 0;
   }
   const uint32_t ncell = lx * ly * lz;

@@ -756,7 +756,7 @@ int adapt_nc_rounds(pies_solver* s) {
 }
 
 int poll_failure(pies_solver* s) {
-  uint32_t* flagWord = s->dev.hash.counters ? s->dev.hash.counters + 3 : s->dev.pd.tri.counters ? s->dev.pd.tri.counters + kTriCtrFailure : nullptr;
+  uint32_t* flagWord = s->dev.hash.counters ? s->dev.hash.counters + kCounterFlags : s->dev.pd.tri.counters ? s->dev.pd.tri.counters + kTriCtrFailure : nullptr;
   if (s->simFailed || !flagWord || s->device == PIES_DEVICE_NONE) return PIES_OK;
   uint32_t flag = 0;
   HIP_TRY(s, hipSetDevice(s->device));

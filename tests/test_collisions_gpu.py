@@ -315,7 +315,7 @@ def test_the_sequential_chain_still_runs_the_reference_order(pies, oracle):
 
 
 def test_dense_cells_take_the_unstaged_path(pies, oracle):
-    """More distinct nodes around one cell than the resolve kernel stages in LDS (256): those groups are resolved
+    """More distinct nodes around one cell than the resolve kernel stages in LDS (384): those groups are resolved
     straight from global memory, the others from LDS, inside the same passes; both must replay the same order."""
     rng = np.random.default_rng(7)
     dense = rng.uniform(0.05, 3.95, (700, 3)) + [0, 1.0, 0]       # ~90 nodes per 2^3 cell, ~700 around the middle ones
@@ -334,6 +334,54 @@ def test_dense_cells_take_the_unstaged_path(pies, oracle):
     check(g, o)
     g, o = pair(pies, oracle, build, 2, 1, rule=TURNS)  # the reference order by turns: partner lists of several batches of 64
     check(g, o)
+
+
+def cell_ranges(p, r, scale=2.0):
+    """NodeCompRange (Solver.cpp:877-901) in float32: every node's minimum cell and its range's length per axis"""
+    p, r, scale = np.asarray(p, np.float32), np.asarray(r, np.float32), np.float32(scale)
+    R = ((r + np.float32(0.5)) / scale)[:, None]
+    g = p / scale - R
+    f = np.floor(g)
+    return f.astype(np.int64), np.ceil((g - f) + np.float32(2) * R).astype(np.int64)
+
+
+def test_a_full_cell_is_staged_with_its_own_nodes_looked_up(pies, oracle, tune):
+    """(group order) A group is staged in LDS while the eight buckets above its cell hold at most 1 024 entries of at most 384
+    distinct nodes; its own nodes ride in the lanes while the own cell's bucket has at most 64 entries.  ~100 small nodes inside one
+    cell: the staged path that finds each own node in the bucket, looks its table slot up and reads its range (the conditions are
+    checked below from the positions).  The unstaged form and the 27-launch form replay the same order: byte for byte the same."""
+    rng = np.random.default_rng(11)
+    own = np.array([0, 1, 0])
+    dense = rng.uniform(0.4, 1.6, (100, 3)) + 2.0 * own            # inside the cell (0, 1, 0) of the 2.0 grid, 0.4 from its faces
+    loose, _ = particles((5, 5, 5), y0=1.0)
+    p = np.concatenate([dense, loose + [6.0, 0, 0]]).astype(np.float32)  # the block's nearest nodes: cell 3, two cells from cell 0
+    r = np.concatenate([np.full(len(dense), 0.12), np.full(len(loose), 0.5)]).astype(np.float32)
+    v = rng.uniform(-1, 1, p.shape).astype(np.float32)
+
+    lo, length = cell_ranges(p, r)
+    def overlapping(cell):
+        return np.flatnonzero(((lo <= cell) & (cell < lo + length)).all(1))
+    assert (lo == own).all(1).any()                                # the cell has a group
+    assert 65 <= len(overlapping(own)) <= 384                      # its bucket does not fit the lanes
+    above = [overlapping(own + [dx, dy, dz]) for dx in (0, 1) for dy in (0, 1) for dz in (0, 1)]
+    assert sum(len(a) for a in above) <= 1024 and len(np.unique(np.concatenate(above))) <= 384  # and is staged
+    d = np.linalg.norm(p[:100, None].astype(np.float64) - p[None, :100], axis=2) + 10.0 * np.eye(100)
+    assert (d < 0.24).any()                                        # pairs inside the cell overlap
+
+    def build(s):
+        s.add_nodes_raw(p, vel=v, radius=r, invMass=np.ones(len(p), np.float32))
+    g, o = pair(pies, oracle, build, 3, 2, rule=1)
+    check(g, o)
+    ref = g.positions, g.velocities, g.collision_pairs
+    assert ref[2] == o.collision_pairs > 0
+    for name in ("PIES_COLLIDE_GLOBAL", "PIES_COLLIDE_PASSES"):
+        tune(name, "1")
+        g = pies.Solver(scenes.pbd_options(pies, 3))
+        build(g)
+        g.set_flag(pies.FLAG_COLLISION_ORDER, pies.COLLISION_ORDER_GROUPS)
+        g.tick(2)
+        tune(name, None)
+        assert ref[0].tobytes() == g.positions.tobytes() and ref[1].tobytes() == g.velocities.tobytes() and ref[2] == g.collision_pairs, name
 
 
 @pytest.mark.parametrize("rule", [0, TURNS, 1, 2], ids=["reference-order", "reference-order-by-turns", "group-order", "pair-order"])
