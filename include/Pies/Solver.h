@@ -578,6 +578,30 @@ public:
     _ck(pies_measure_nodes(_handle(), n, pairs.data(), about.data(), out.data()));
     return out;
   }
+  // Extension (pies_read_nodes_device / pies_write_nodes_device / pies_read_skin_device in pies_hip.h state the rules): node state
+  // and skins to and from DEVICE memory of the host program - a vertex buffer shared with HIP, a controller that lives on the GPU -
+  // ordered against `stream` (the host's hipStream_t; nullptr: the default stream) by events, without a host synchronisation
+  // unless flags has PIES_IO_HOST_SYNC.  Arrays are in the order of getVertices(); a NULL pointer leaves that array out.
+  // writeNodesDevice does not refresh getVertices(): the next tick does.
+  void readNodesDevice(const pies_device_nodes_t& dst, void* stream = nullptr, uint32_t flags = 0) {
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    uint32_t n = 0;
+    _ck(pies_count(_handle(), PIES_NODES, &n));
+    _ck(pies_read_nodes_device(_handle(), &dst, n, stream, flags));
+  }
+  // ids == nullptr: row k is node k; otherwise a device array of `count` node ids
+  void writeNodesDevice(const pies_device_nodes_t& src, const uint32_t* ids = nullptr, uint32_t count = 0, void* stream = nullptr,
+                        uint32_t flags = 0) {
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    if (!ids) _ck(pies_count(_handle(), PIES_NODES, &count));
+    _ck(pies_write_nodes_device(_handle(), &src, ids, count, stream, flags));
+  }
+  void readSkinDevice(uint32_t skin, void* positions, void* normals = nullptr, void* stream = nullptr, uint32_t flags = 0) {
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    uint32_t n = 0;
+    _ck(pies_get_skin_binding(_handle(), skin, nullptr, nullptr, nullptr, 0, &n));
+    _ck(pies_read_skin_device(_handle(), skin, positions, normals, n, stream, flags));
+  }
   // Extension (pies_collide_field_props in pies_hip.h states the rule): rigid colliders of any shape.  A field is a signed distance
   // function on a lattice in a local frame, negative inside: addField takes the host's samples (sample (i, j, k) at local
   // origin + (i, j, k) * cell, stored at (k * ny + j) * nx + i: an analytic shape, a height field), addFieldFromTriMesh builds

@@ -843,7 +843,10 @@ int pies_set_collision_rounds(pies_solver_t* s, uint32_t rounds);
  * new velocities to a scratch array, a second launch commits them; unset: inplace; a list with a wind always takes scratch: its
  * lanes read their neighbours' velocities);
  * pies_apply_surface_loads, read at every call: PIES_LOAD_VARIANT (inplace / scratch as above; unset: inplace; a list with a
- * fluid drag always takes scratch).  They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
+ * fluid drag always takes scratch);
+ * pies_read_nodes_device / pies_write_nodes_device, read at every call: PIES_NODE_IO_VARIANT (plain: a packed stride-3 row moves as
+ * its lane's three floats, staged: a tile's rows pass through LDS and cross as 16-byte accesses; unset: plain).
+ * They take effect where the library reads them (pies_create, pies_finalize or the next graph capture).  pies_set_tuning must not
  * race with other API calls of the process (a handle reads the switches at different times of its life).  None of
  * them is read from the environment: the only environment variables the library looks at are PIES_SCHEDULE (default schedule
  * of new handles), PIES_PROFILER_SAFE (profiling runs) and the print-only PIES_PCG_DEBUG / PIES_LAYER_DEBUG. */
@@ -869,6 +872,44 @@ int pies_read_nodes(pies_solver_t* s, int what, float* out, uint32_t n);
  * `_vertices[i].position = node.position`, Solver.cpp:157,393).  After pies_tick this is a host-side copy. */
 int pies_read_positions_strided(pies_solver_t* s, void* dst, uint64_t stride_bytes, uint32_t n);
 int pies_write_nodes(pies_solver_t* s, int what, const float* in, uint32_t n);
+/* EXTENSION: node state and skins to and from DEVICE memory of the caller - a renderer with HIP interop, a controller or a force
+ * model that lives on the GPU (a torch tensor's data_ptr) - without a copy across the bus and without a host synchronisation.
+ * Every pointer of pies_device_nodes_t is a device pointer of the handle's device, or NULL (that array is not wanted): position,
+ * prev_position, velocity hold `stride` (3 or 4) floats per node, radius and inv_mass one.  Row i is HOST node i, also under
+ * PIES_FLAG_RENUMBER_NODES.
+ * pies_read_nodes_device fills the non-NULL arrays with exactly the words pies_read_nodes returns; with stride == 4 the fourth float
+ * is written as 0.0f.  n must be pies_count(PIES_NODES).  A changed scene or a pending pies_write_nodes is brought to the device
+ * first.  Read-only: no stale mark, nothing a tick can observe.
+ * pies_write_nodes_device replaces position, prev_position and / or velocity in HBM.  radius and inv_mass must be NULL
+ * (PIES_ERR_UNSUPPORTED: they size the node grid and the PD system; pies_write_nodes remains their path).  ids == NULL: m must be
+ * the node count and row k goes to host node k.  Otherwise ids is a DEVICE array of m host ids and row k goes to node ids[k]; the
+ * ids must be distinct (with duplicates, which row wins is unspecified); a row whose id is not below the node count is ignored.  A
+ * position write keeps pos.w (the inverse mass); with stride == 4 the source's fourth float is not used.  The host mirror is marked
+ * stale for the written arrays like after pies_collide_props: nothing is uploaded, and pies_read_nodes, pies_tick and a scene edit
+ * see the result.  A pies_write_nodes made before the call is uploaded before it.
+ * pies_read_skin_device: pies_read_skin's rule and launches, the vertices (n x 3 floats) and normals (n x 3, may be NULL) of skin
+ * `skin` written to caller memory; n must be the skin's vertex count.
+ * Streams.  `stream` is the caller's hipStream_t, by value; NULL is the legacy default stream.  The library records an event on
+ * the caller's stream and lets the solver's stream wait for it (the caller's earlier work on the buffers is finished first),
+ * launches on the solver's stream - one launch per node call, however many arrays -, records a second event there and lets the
+ * caller's stream wait for it: work the caller queues on `stream` afterwards sees the result.  The host is never synchronised
+ * unless flags has PIES_IO_HOST_SYNC (the call then returns after its launches have finished).  Frames begun before the call
+ * (pies_tick_begin) hold the state before it.  A caller stream that is capturing returns PIES_ERR_STATE.  The store of the packed
+ * stride-3 form has two variants, pies_set_tuning("PIES_NODE_IO_VARIANT", "plain" | "staged"); the words are
+ * the same.  No atomics: two calls agree bit for bit.
+ * PIES_ERR_INVALID: a NULL handle or struct, every pointer NULL, a stride other than 3 or 4, a wrong n or m, an unknown skin, a
+ * pointer that is not 4-byte aligned, a pointer that is not device memory of the handle's device (or whose allocation ends before
+ * the array does), an unknown PIES_NODE_IO_VARIANT.  n == 0 (m == 0) returns PIES_OK.  PIES_ERR_HIP: a PIES_DEVICE_NONE handle
+ * (the arguments are checked first; what needs a device to be checked - the pointers' memory - comes after). */
+typedef struct pies_device_nodes {
+  void *position, *prev_position, *velocity; /* device pointers or NULL; `stride` floats per node */
+  void *radius, *inv_mass;                   /* device pointers or NULL; 1 float per node; read only */
+  uint32_t stride;                           /* 3 or 4 */
+} pies_device_nodes_t;
+enum { PIES_IO_HOST_SYNC = 1 };
+int pies_read_nodes_device(pies_solver_t* s, const pies_device_nodes_t* dst, uint32_t n, void* stream, uint32_t flags);
+int pies_write_nodes_device(pies_solver_t* s, const pies_device_nodes_t* src, const uint32_t* ids, uint32_t m, void* stream, uint32_t flags);
+int pies_read_skin_device(pies_solver_t* s, uint32_t skin, void* positions, void* normals, uint32_t n, void* stream, uint32_t flags);
 /* node ids of a container, flattened, in the order the host added them */
 int pies_get_ids(const pies_solver_t* s, int type, uint32_t* out, uint32_t capacity);
 /* node ids of shape (PIES_SHAPE) or goal (PIES_GOAL) constraint `index`; ids may be NULL to query count */

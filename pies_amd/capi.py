@@ -61,6 +61,7 @@ LOAD_MAX = 64  # PIES_LOAD_MAX
 LOAD_TO_END = 0xFFFFFFFF  # pies_surface_load_t.count: to the container's end
 ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
 MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
+IO_HOST_SYNC = 1  # PIES_IO_HOST_SYNC: a device-side read or write returns after its launches have finished
 LAYER_REST_MAX_SETS = 64  # kLayerRestMaxSets (layer_rest.h): a scene with more distinct sets reads the per-element arrays
 
 # every symbol include/pies_hip.h declares (checked by tests/test_capi_symbols.py against the header)
@@ -85,6 +86,7 @@ SYMBOLS = [
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
     "pies_apply_surface_loads",
     "pies_measure_elements", "pies_measure_nodes",
+    "pies_read_nodes_device", "pies_write_nodes_device", "pies_read_skin_device",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
 ]
 
@@ -315,6 +317,12 @@ class NodeSums(C.Structure):
 
 
 # numpy views of the two records: Solver.measure_elements / measure_nodes return structured arrays
+class DeviceNodes(C.Structure):
+    """pies_device_nodes_t: device addresses (0 / None: the array is not part of the call)"""
+    _fields_ = [("position", C.c_void_p), ("prev_position", C.c_void_p), ("velocity", C.c_void_p), ("radius", C.c_void_p),
+                ("inv_mass", C.c_void_p), ("stride", C.c_uint32)]
+
+
 ELEMENT_MEASURE_DTYPE = np.dtype([("s", np.float32, 3), ("j", np.float32), ("volume", np.float32), ("i1", np.float32),
                                   ("green", np.float32), ("flags", np.uint32)])
 NODE_SUMS_DTYPE = np.dtype([("mass", np.float32), ("momentum", np.float32, 3), ("angular", np.float32, 3),
@@ -412,6 +420,9 @@ def load():
     sig["pies_apply_surface_loads"] = [vp, u32, C.POINTER(SurfaceLoad), f32, pf, pf, pu, pf, pf]
     sig["pies_measure_elements"] = [vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
     sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
+    sig["pies_read_nodes_device"] = [vp, C.POINTER(DeviceNodes), u32, vp, u32]
+    sig["pies_write_nodes_device"] = [vp, C.POINTER(DeviceNodes), vp, u32, vp, u32]
+    sig["pies_read_skin_device"] = [vp, u32, vp, vp, u32, vp, u32]
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
@@ -459,6 +470,7 @@ class Solver:
         if rc != OK:
             raise PiesError("pies_create failed (code %d): no gfx950 HIP device %d, or runtime error" % (rc, device))
         self._h = h
+        self.device = device
 
     def close(self):
         if getattr(self, "_h", None):
@@ -952,6 +964,36 @@ class Solver:
 
     def set_inv_masses(self, m):
         self._write(NODE_INV_MASS, m)
+
+    # -- the same, to and from device memory (integer addresses; pies_amd.tensors speaks torch tensors) --
+    @staticmethod
+    def _device_nodes(position, prev_position, velocity, radius, inv_mass, stride):
+        return DeviceNodes(position or None, prev_position or None, velocity or None, radius or None, inv_mass or None, stride)
+
+    def read_nodes_device(self, position=0, prev_position=0, velocity=0, radius=0, inv_mass=0, stride=3, n=None, stream=0, flags=0):
+        """pies_read_nodes_device: the named arrays (device addresses; `stride` floats per node, radius and inv_mass one) filled
+        in host numbering on the solver's stream, ordered against `stream` (a hipStream_t as an integer, 0: the default stream)
+        by events; no host synchronisation unless flags has IO_HOST_SYNC."""
+        a = self._device_nodes(position, prev_position, velocity, radius, inv_mass, stride)
+        self._ck(self._L.pies_read_nodes_device(self._h, C.byref(a), self.count(NODES) if n is None else n, stream or None, flags))
+
+    def write_nodes_device(self, position=0, prev_position=0, velocity=0, stride=3, ids=0, m=None, stream=0, flags=0):
+        """pies_write_nodes_device: positions, previous positions and / or velocities replaced in HBM from device arrays; ids (a
+        device array of m host ids) names the nodes of the rows, 0: row k is node k and m is the node count."""
+        a = self._device_nodes(position, prev_position, velocity, 0, 0, stride)
+        self._ck(self._L.pies_write_nodes_device(self._h, C.byref(a), ids or None, self.count(NODES) if m is None else m,
+                                                 stream or None, flags))
+
+    def skin_vertex_count(self, skin):
+        n = C.c_uint32()
+        if self._L.pies_get_skin_binding(self._h, skin, None, None, None, 0, C.byref(n)) != OK:
+            raise PiesError("no skin %d" % skin)
+        return n.value
+
+    def read_skin_device(self, skin, positions, normals=0, n=None, stream=0, flags=0):
+        """pies_read_skin_device: pies_read_skin into device arrays (n x 3 floats each; normals 0: not computed)"""
+        self._ck(self._L.pies_read_skin_device(self._h, skin, positions or None, normals or None,
+                                               self.skin_vertex_count(skin) if n is None else n, stream or None, flags))
 
     def ids(self, ctype):
         n, k = self.count(ctype), _IDS_PER[ctype]

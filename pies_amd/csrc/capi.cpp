@@ -111,6 +111,8 @@ int pies_destroy(pies_solver_t* s) {
     if (s->evTick[b]) (void)hipEventDestroy(s->evTick[b]);
     if (s->evCopied[b]) (void)hipEventDestroy(s->evCopied[b]);
   }
+  if (s->evIoIn) (void)hipEventDestroy(s->evIoIn);
+  if (s->evIoOut) (void)hipEventDestroy(s->evIoOut);
   if (s->d_export) (void)hipFree(s->d_export);
   if (s->copyStream) (void)hipStreamDestroy(s->copyStream);
   if (s->evFork) (void)hipEventDestroy(s->evFork);

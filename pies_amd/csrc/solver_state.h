@@ -403,6 +403,8 @@ struct pies_solver {
   float4* d_export = nullptr;
   uint64_t frameBegun = 0;      // frames begun so far (frame ids start at 1)
   uint64_t frameAcquired = 0;   // frame the host currently holds (0: none)
+  // ---- device-side node and skin access (node_io.cpp): the caller's stream and the solver's wait for each other ----
+  hipEvent_t evIoIn = nullptr, evIoOut = nullptr;  // created at the first call: caller's work so far; the call's launches
   // ---- skins: device records of h_skins (built by skin_upload at pies_finalize / before the next use), outputs, export ----
   pies::SkinArrays skin{};
   bool skinDirty = false;            // h_skins and the device records differ
