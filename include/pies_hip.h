@@ -95,9 +95,12 @@ enum {
   PIES_LAYER_MAX_TILES = 24,   /* pies_count only: tiles (= workgroups of a launch) of the phase of schedule LAYERED's plan that has
                                   most, 0 when the plan is not active (after pies_finalize); more than the device's 256 compute
                                   units select the four-wavefronts-per-SIMD kernel variants */
-  PIES_LAYER_MAX_CLASS = 25    /* pies_count only: constraints of the largest colour class of any tile and container of schedule
+  PIES_LAYER_MAX_CLASS = 25,   /* pies_count only: constraints of the largest colour class of any tile and container of schedule
                                   LAYERED's plan, 0 when the plan is not active (after pies_finalize); with at most 256 tiles it
                                   selects the workgroup of the layer kernel: 256 threads up to 256, 512 up to 512, else 1 024 */
+  PIES_PD_CG_BLOCKS = 26       /* pies_count only: workgroups of the PD global step's CG launches that synchronise through a grid
+                                  barrier (after pies_finalize; 0 for PBD): one per 256 rows, at most half of what the device holds
+                                  resident at once, so that a second solver on the card leaves room */
 };
 
 /* How the sequential Gauss-Seidel sweeps of tickPBD (Solver.cpp:58-75) are mapped to the device.
@@ -980,6 +983,20 @@ int pies_layer_rest_unpack(const uint32_t* words, uint32_t* ids, uint32_t* set);
 int pies_layer_rest_usable(uint32_t sets, uint32_t count, uint32_t max_group_nodes, uint32_t lds_bytes);
 /* launches per substep of the captured graph, per kernel class (PIES_KERNEL_COUNT entries) */
 int pies_launch_counts(pies_solver_t* s, uint32_t* out);
+/* The library's resource ledger: every HIP resource it creates or destroys is counted, process-wide, over all handles.  No handle
+ * is taken, so what a destroyed handle left behind stays visible: after the last pies_destroy every live figure is 0.
+ *   out[0..7]  live now:           device bytes, device allocations, pinned host bytes, pinned host allocations, streams, events,
+ *                                  graphs, executable graphs
+ *   out[8..15] created since load: the same eight kinds, in the same order (never decreasing)
+ * Device and pinned bytes are the sizes requested, not what the allocator rounds them to.  pies_clear returns a handle to what
+ * pies_create gave it (two streams, two events) plus what two call families create once per handle and pies_destroy releases:
+ * pies_tick_begin a stream, four events and the frame buffers on the device and in pinned memory (they keep the size of the
+ * largest scene exported), the device-side node and skin access (pies_read_nodes_device and kin) two events.  A graph whose
+ * destruction is skipped under PIES_PROFILER_SAFE=1 stays counted as live.  Nothing inside pies_tick / pies_tick_async creates a
+ * resource once the scene is finalized; pies_finalize, the first call of a query or edit entry point, and a call with more rays,
+ * points or nodes than any before it, may.  Safe to call from any thread at any time; the sixteen words are read one by one, not
+ * as a snapshot.  PIES_ERR_INVALID when out is NULL. */
+int pies_resource_counts(uint64_t out[16]);
 
 #ifdef __cplusplus
 }

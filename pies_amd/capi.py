@@ -42,6 +42,7 @@ SKINS, SKIN_VERTICES = 21, 22  # pies_count: embedded surface meshes (pies_add_s
 LAYER_REST_SETS = 23  # pies_count: sets in the rest dictionary of schedule LAYERED's tetrahedral container (0: per-element arrays)
 LAYER_MAX_TILES = 24  # pies_count: tiles of the phase of schedule LAYERED's plan that has most (0: not active)
 LAYER_MAX_CLASS = 25  # pies_count: the largest colour class of any tile and container of schedule LAYERED's plan (0: not active)
+PD_CG_BLOCKS = 26  # pies_count: workgroups of the PD CG launches that meet at a grid barrier (at most half the resident grid)
 RAY_SCENE_TRIANGLES, RAY_SKIN = 0, 1  # pies_raycast targets
 RAY_CULL_BACK = 1  # pies_raycast flag
 RAY_MISS = 0xFFFFFFFF  # PIES_RAY_MISS
@@ -88,6 +89,7 @@ SYMBOLS = [
     "pies_measure_elements", "pies_measure_nodes",
     "pies_read_nodes_device", "pies_write_nodes_device", "pies_read_skin_device",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
+    "pies_resource_counts",
 ]
 
 
@@ -112,6 +114,21 @@ def layer_rest_usable(sets, count, max_group_nodes, lds_bytes=0):
     """pies_layer_rest_usable: whether such a scene takes the rest dictionary (all or nothing); lds_bytes 0: the library's figure for
     gfx950, the one host-only handles decide with"""
     return load().pies_layer_rest_usable(sets, count, max_group_nodes, lds_bytes) == 1
+
+
+# the eight kinds of pies_resource_counts, in the order of either half of its sixteen words
+RESOURCE_KINDS = ("device_bytes", "device_allocations", "pinned_bytes", "pinned_allocations", "streams", "events", "graphs",
+                  "graph_execs")
+
+
+def resource_counts():
+    """pies_resource_counts: {"live": {kind: n}, "created": {kind: n}} over RESOURCE_KINDS - the HIP resources the library holds
+    now, and has created since it was loaded, over all handles of the process (destroyed ones included)"""
+    out = (C.c_uint64 * 16)()
+    if load().pies_resource_counts(out) != OK:
+        raise PiesError("pies_resource_counts failed")
+    return {"live": {k: int(out[i]) for i, k in enumerate(RESOURCE_KINDS)},
+            "created": {k: int(out[8 + i]) for i, k in enumerate(RESOURCE_KINDS)}}
 
 
 def set_tuning(name, value):
@@ -426,6 +443,7 @@ def load():
     sig["pies_layer_rest_pack"] = [pu, u32, pu]
     sig["pies_layer_rest_unpack"] = [pu, pu, pu]
     sig["pies_layer_rest_usable"] = [u32, u32, u32, u32]
+    sig["pies_resource_counts"] = [C.POINTER(C.c_uint64)]
     sig["pies_get_pd_tile_plan"] = [vp, pu, pu, pu, pu, pu, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), u32]
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -80,13 +80,13 @@ int pies_create(const pies_options_t* options, int device, pies_solver_t** out) 
   if (s->opt.timeSubsteps == 0) s->opt.timeSubsteps = 1;
   s->device = device;
   apply_schedule_environment(s);
-  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&s->sideStream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&s->evFork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->evJoin, hipEventDisableTiming) != hipSuccess) {
-    if (s->evFork) (void)hipEventDestroy(s->evFork);
-    if (s->sideStream) (void)hipStreamDestroy(s->sideStream);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+  if (ledger::stream_create(&s->stream, hipStreamNonBlocking) != hipSuccess ||
+      ledger::stream_create(&s->sideStream, hipStreamNonBlocking) != hipSuccess ||
+      ledger::event_create(&s->evFork, hipEventDisableTiming) != hipSuccess ||
+      ledger::event_create(&s->evJoin, hipEventDisableTiming) != hipSuccess) {
+    if (s->evFork) (void)ledger::event_destroy(s->evFork);
+    if (s->sideStream) (void)ledger::stream_destroy(s->sideStream);
+    if (s->stream) (void)ledger::stream_destroy(s->stream);
     delete s;
     return PIES_ERR_HIP;
   }
@@ -102,23 +102,23 @@ int pies_destroy(pies_solver_t* s) {
   if (s->sideStream) (void)hipStreamSynchronize(s->sideStream);
   if (s->copyStream) (void)hipStreamSynchronize(s->copyStream);
   free_device(s);
-  if (s->h_stage) (void)hipHostFree(s->h_stage);
-  if (s->h_skinStage) (void)hipHostFree(s->h_skinStage);
-  if (s->d_skinExport) (void)hipFree(s->d_skinExport);
+  if (s->h_stage) (void)ledger::host_free(s->h_stage);
+  if (s->h_skinStage) (void)ledger::host_free(s->h_skinStage);
+  if (s->d_skinExport) (void)ledger::dev_free(s->d_skinExport);
   for (int b = 0; b < 2; ++b) {
-    if (s->h_skinExport[b]) (void)hipHostFree(s->h_skinExport[b]);
-    if (s->h_export[b]) (void)hipHostFree(s->h_export[b]);
-    if (s->evTick[b]) (void)hipEventDestroy(s->evTick[b]);
-    if (s->evCopied[b]) (void)hipEventDestroy(s->evCopied[b]);
+    if (s->h_skinExport[b]) (void)ledger::host_free(s->h_skinExport[b]);
+    if (s->h_export[b]) (void)ledger::host_free(s->h_export[b]);
+    if (s->evTick[b]) (void)ledger::event_destroy(s->evTick[b]);
+    if (s->evCopied[b]) (void)ledger::event_destroy(s->evCopied[b]);
   }
-  if (s->evIoIn) (void)hipEventDestroy(s->evIoIn);
-  if (s->evIoOut) (void)hipEventDestroy(s->evIoOut);
-  if (s->d_export) (void)hipFree(s->d_export);
-  if (s->copyStream) (void)hipStreamDestroy(s->copyStream);
-  if (s->evFork) (void)hipEventDestroy(s->evFork);
-  if (s->evJoin) (void)hipEventDestroy(s->evJoin);
-  if (s->sideStream) (void)hipStreamDestroy(s->sideStream);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
+  if (s->evIoIn) (void)ledger::event_destroy(s->evIoIn);
+  if (s->evIoOut) (void)ledger::event_destroy(s->evIoOut);
+  if (s->d_export) (void)ledger::dev_free(s->d_export);
+  if (s->copyStream) (void)ledger::stream_destroy(s->copyStream);
+  if (s->evFork) (void)ledger::event_destroy(s->evFork);
+  if (s->evJoin) (void)ledger::event_destroy(s->evJoin);
+  if (s->sideStream) (void)ledger::stream_destroy(s->sideStream);
+  if (s->stream) (void)ledger::stream_destroy(s->stream);
   delete s;
   return PIES_OK;
 }
@@ -132,6 +132,13 @@ int pies_clear(pies_solver_t* s) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
     free_device(s);
+    // the pinned staging buffers were sized for the scene that goes (the export buffers stay: a frame may be acquired)
+    (void)ledger::host_free(s->h_stage);
+    s->h_stage = nullptr;
+    s->h_stage_n = 0;
+    (void)ledger::host_free(s->h_skinStage);
+    s->h_skinStage = nullptr;
+    s->h_skinStage_n = 0;
   }
   s->h_pos.clear(); s->h_prev.clear(); s->h_vel.clear(); s->h_radius.clear(); s->h_invMass.clear();
   s->h_position.clear(); s->h_distance.clear(); s->h_tet.clear(); s->h_volume.clear(); s->h_bend.clear(); s->h_nodePair.clear();
@@ -505,37 +512,37 @@ int pies_tick(pies_solver_t* s) {
 static int export_prepare(pies_solver* s) {
   const uint32_t n = s->dev.nd.n;
   if (!s->copyStream) {
-    HIP_TRY(s, hipStreamCreateWithFlags(&s->copyStream, hipStreamNonBlocking));
+    HIP_TRY(s, ledger::stream_create(&s->copyStream, hipStreamNonBlocking));
     for (int b = 0; b < 2; ++b) {
-      HIP_TRY(s, hipEventCreateWithFlags(&s->evTick[b], hipEventDisableTiming));
-      HIP_TRY(s, hipEventCreateWithFlags(&s->evCopied[b], hipEventDisableTiming));
+      HIP_TRY(s, ledger::event_create(&s->evTick[b], hipEventDisableTiming));
+      HIP_TRY(s, ledger::event_create(&s->evCopied[b], hipEventDisableTiming));
     }
   }
   if (s->h_export_n < n || !s->d_export) {
     HIP_TRY(s, hipStreamSynchronize(s->copyStream));
     for (int b = 0; b < 2; ++b) {
-      if (s->h_export[b]) (void)hipHostFree(s->h_export[b]);
+      if (s->h_export[b]) (void)ledger::host_free(s->h_export[b]);
       s->h_export[b] = nullptr;
-      HIP_TRY(s, hipHostMalloc((void**)&s->h_export[b], std::max<size_t>(n, 1) * sizeof(float4), hipHostMallocDefault));
+      HIP_TRY(s, ledger::host_malloc((void**)&s->h_export[b], std::max<size_t>(n, 1) * sizeof(float4), hipHostMallocDefault));
     }
-    if (s->d_export) (void)hipFree(s->d_export);
+    if (s->d_export) (void)ledger::dev_free(s->d_export);
     s->d_export = nullptr;
-    HIP_TRY(s, hipMalloc((void**)&s->d_export, std::max<size_t>(n, 1) * sizeof(float4)));
+    HIP_TRY(s, ledger::dev_malloc((void**)&s->d_export, std::max<size_t>(n, 1) * sizeof(float4)));
     s->h_export_n = n;
   }
   const size_t nv = s->skin.nVerts;  // skins: positions and normals of every skin, one device buffer and one pinned buffer per frame
   if (nv && (s->skinExport_n < nv || !s->d_skinExport)) {
     HIP_TRY(s, hipStreamSynchronize(s->copyStream));
     for (int b = 0; b < 2; ++b) {
-      if (s->h_skinExport[b]) (void)hipHostFree(s->h_skinExport[b]);
+      if (s->h_skinExport[b]) (void)ledger::host_free(s->h_skinExport[b]);
       s->h_skinExport[b] = nullptr;
       s->frameSkinVerts[b] = 0;
     }
-    if (s->d_skinExport) (void)hipFree(s->d_skinExport);
+    if (s->d_skinExport) (void)ledger::dev_free(s->d_skinExport);
     s->d_skinExport = nullptr;
     s->skinExport_n = 0;
-    for (int b = 0; b < 2; ++b) HIP_TRY(s, hipHostMalloc((void**)&s->h_skinExport[b], 6 * nv * sizeof(float), hipHostMallocDefault));
-    HIP_TRY(s, hipMalloc((void**)&s->d_skinExport, 6 * nv * sizeof(float)));
+    for (int b = 0; b < 2; ++b) HIP_TRY(s, ledger::host_malloc((void**)&s->h_skinExport[b], 6 * nv * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(s, ledger::dev_malloc((void**)&s->d_skinExport, 6 * nv * sizeof(float)));
     s->skinExport_n = nv;
   }
   return PIES_OK;
@@ -751,6 +758,13 @@ int pies_layer_rest_usable(uint32_t sets, uint32_t count, uint32_t max_group_nod
   return layer_rest_usable(sets, count, max_group_nodes, layer_lds_bytes(max_group_nodes, 0), layer_lds_bytes(max_group_nodes, sets), lds_bytes) ? 1 : 0;
 }
 
+int pies_resource_counts(uint64_t out[16]) {
+  if (!out) return PIES_ERR_INVALID;
+  static_assert(2 * ledger::KINDS == 16, "pies_resource_counts: sixteen words");
+  ledger::counts(out);
+  return PIES_OK;
+}
+
 int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
   if (!s || !out) return PIES_ERR_INVALID;
   switch (what) {
@@ -775,6 +789,7 @@ int pies_count(const pies_solver_t* s, int what, uint32_t* out) {
     case PIES_PD_WINDOW_HALO: *out = s->dev.pd.cg.wRows ? s->pdWindowHalo : 0u; break;
     case PIES_NODES_RENUMBERED: *out = s->nodeOrder.active() ? 1u : 0u; break;
     case PIES_LAYER_REST_SETS: *out = s->layer.active ? s->layer.restSets : 0u; break;
+    case PIES_PD_CG_BLOCKS: *out = s->opt.solver == PIES_SOLVER_PD && s->dev.pd.cg.n ? s->dev.pd.cg.nparts : 0u; break;
     case PIES_LAYER_MAX_TILES: {
       *out = 0;
       if (s->layer.active)

@@ -36,7 +36,7 @@ void free_device(pies_solver* s) {
   destroy_graph(s);
   skin_free_device(s);
   ray_free_device(s);
-  for (void* p : s->dev.allocations) (void)hipFree(p);
+  for (void* p : s->dev.allocations) (void)ledger::dev_free(p);
   s->dev = DeviceScene{};
 }
 
@@ -146,9 +146,9 @@ int alloc_nodes(pies_solver* s) {
     if (int rc = dev_alloc(s, 3ull * n, &d.d_pack)) return rc;
     d.nd.n = n;
     if (s->h_stage_n < n) {
-      if (s->h_stage) (void)hipHostFree(s->h_stage);
+      if (s->h_stage) (void)ledger::host_free(s->h_stage);
       s->h_stage = nullptr;
-      HIP_TRY(s, hipHostMalloc((void**)&s->h_stage, n * sizeof(float4), hipHostMallocDefault));
+      HIP_TRY(s, ledger::host_malloc((void**)&s->h_stage, n * sizeof(float4), hipHostMallocDefault));
       s->h_stage_n = n;
     }
   }

@@ -20,7 +20,7 @@ template <class T> int dev_alloc(pies_solver* s, size_t count, T** d, bool zero 
   *d = nullptr;
   if (count == 0) return PIES_OK;
   void* p = nullptr;
-  HIP_TRY(s, hipMalloc(&p, count * sizeof(T)));
+  HIP_TRY(s, ledger::dev_malloc(&p, count * sizeof(T)));
   s->dev.allocations.push_back(p);
   if (zero) HIP_TRY(s, hipMemsetAsync(p, 0, count * sizeof(T), s->stream));
   *d = static_cast<T*>(p);
@@ -44,7 +44,7 @@ struct Temporaries {
   ~Temporaries() {
     if (s->dev.allocations.size() > mark) (void)hipStreamSynchronize(s->stream);
     while (s->dev.allocations.size() > mark) {
-      (void)hipFree(s->dev.allocations.back());
+      (void)ledger::dev_free(s->dev.allocations.back());
       s->dev.allocations.pop_back();
     }
   }

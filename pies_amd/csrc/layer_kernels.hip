@@ -13,7 +13,11 @@
 // Arithmetic per constraint is pbd_project.h's, the same as the global-memory kernels'.  No MFMA: 3x3 algebra per
 // lane.  Algorithmic bytes are those of the projections executed; HBM traffic is lower because a node
 // record is read and written once per launch instead of once per incident constraint.
+#include <atomic>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "dev_math.h"
 #include "kernels.h"
@@ -491,10 +495,23 @@ static hipError_t layer_prepare_variants(int bytes) {
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 1, DICT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   return e;
 }
+// The limit belongs to the function on the device that is current, whichever handle set it: it is only ever raised, and what it has
+// been raised to is remembered per device and variant family under a mutex (as window_lds_ok does in pd_cg1_kernels.hip), so that
+// a handle with smaller tiles that finalizes later - from any thread - does not take the room from one with larger tiles.
 hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets) {
   const int bytes = static_cast<int>(layer_lds_bytes(maxGroupNodes, restSets));
   if (bytes <= 64 * 1024) return hipSuccess;
-  return restSets ? layer_prepare_variants<true>(bytes) : layer_prepare_variants<false>(bytes);
+  static std::mutex mu;
+  static std::map<std::pair<int, bool>, int> allowed;  // (device, dictionary variants) -> the limit its kernels have been raised to
+  int dev = -1;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  int& have = allowed[std::make_pair(dev, restSets != 0)];
+  if (bytes <= have) return hipSuccess;
+  e = restSets ? layer_prepare_variants<true>(bytes) : layer_prepare_variants<false>(bytes);
+  if (e == hipSuccess) have = bytes;
+  return e;
 }
 
 template <bool DICT>
@@ -530,8 +547,8 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
       if (!((skipMask >> L0.seg[s].kind) & 1)) L.seg[L.nseg++] = L0.seg[s];
   }
   {
-    static unsigned int slot = 0;  // the launch's place in the stamp buffer (64 launches are kept)
-    L.stampSlot = slot++ & 63u;
+    static std::atomic<unsigned int> slot{0};  // the launch's place in the stamp buffer (64 launches are kept); handles may launch from several threads
+    L.stampSlot = slot.fetch_add(1u, std::memory_order_relaxed) & 63u;
   }
   const int variant = [] { const char* e = getenv("PIES_EXP_TET"); return e ? atoi(e) : 0; }();
   if (variant == 1) {  // no SVD (with a dictionary tc_lid holds 13-bit ids: the instantiation that unpacks them)

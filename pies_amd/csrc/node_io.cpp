@@ -65,8 +65,8 @@ int io_begin(pies_solver* s, const char* call, hipStream_t caller) {
   if (e != hipSuccess) (void)hipGetLastError();
   if (e != hipSuccess || status != hipStreamCaptureStatusNone)
     return fail(s, PIES_ERR_STATE, std::string(call) + ": the caller's stream is capturing");
-  if (!s->evIoIn) HIP_TRY(s, hipEventCreateWithFlags(&s->evIoIn, hipEventDisableTiming));
-  if (!s->evIoOut) HIP_TRY(s, hipEventCreateWithFlags(&s->evIoOut, hipEventDisableTiming));
+  if (!s->evIoIn) HIP_TRY(s, ledger::event_create(&s->evIoIn, hipEventDisableTiming));
+  if (!s->evIoOut) HIP_TRY(s, ledger::event_create(&s->evIoOut, hipEventDisableTiming));
   HIP_TRY(s, hipEventRecord(s->evIoIn, caller));
   HIP_TRY(s, hipStreamWaitEvent(s->stream, s->evIoIn, 0));
   return PIES_OK;

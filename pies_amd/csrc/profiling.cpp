@@ -25,7 +25,7 @@ struct StateGuard {
   explicit StateGuard(pies_solver* s_) : s(s_) {
     const size_t bytes = static_cast<size_t>(s->dev.nd.n) * sizeof(float4);
     if (!bytes) { ok = true; return; }
-    if (hipMalloc((void**)&pos, bytes) != hipSuccess || hipMalloc((void**)&prev, bytes) != hipSuccess || hipMalloc((void**)&vel, bytes) != hipSuccess) return;
+    if (ledger::dev_malloc((void**)&pos, bytes) != hipSuccess || ledger::dev_malloc((void**)&prev, bytes) != hipSuccess || ledger::dev_malloc((void**)&vel, bytes) != hipSuccess) return;
     ok = hipMemcpyAsync(pos, s->dev.nd.pos, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
          hipMemcpyAsync(prev, s->dev.nd.prev, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess &&
          hipMemcpyAsync(vel, s->dev.nd.vel, bytes, hipMemcpyDeviceToDevice, s->stream) == hipSuccess;
@@ -38,9 +38,9 @@ struct StateGuard {
       (void)hipMemcpyAsync(s->dev.nd.vel, vel, bytes, hipMemcpyDeviceToDevice, s->stream);
       (void)hipStreamSynchronize(s->stream);
     }
-    if (pos) (void)hipFree(pos);
-    if (prev) (void)hipFree(prev);
-    if (vel) (void)hipFree(vel);
+    if (pos) (void)ledger::dev_free(pos);
+    if (prev) (void)ledger::dev_free(prev);
+    if (vel) (void)ledger::dev_free(vel);
   }
 };
 }  // namespace
@@ -74,15 +74,15 @@ int pies_profile_substep(pies_solver_t* s, int kernel, uint32_t* launches, doubl
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     ~Scope() {
-      if (capturing) { hipGraph_t tmp = nullptr; (void)hipStreamEndCapture(st, &tmp); if (tmp) (void)hipGraphDestroy(tmp); }
-      if (ev0) (void)hipEventDestroy(ev0);
-      if (ev1) (void)hipEventDestroy(ev1);
-      if (ge) (void)hipGraphExecDestroy(ge);
-      if (g) (void)hipGraphDestroy(g);
+      if (capturing) { hipGraph_t tmp = nullptr; (void)ledger::end_capture(st, &tmp); if (tmp) (void)ledger::graph_destroy(tmp); }
+      if (ev0) (void)ledger::event_destroy(ev0);
+      if (ev1) (void)ledger::event_destroy(ev1);
+      if (ge) (void)ledger::graph_exec_destroy(ge);
+      if (g) (void)ledger::graph_destroy(g);
     }
   } sc{s->stream};
-  HIP_TRY(s, hipEventCreate(&sc.ev0));
-  HIP_TRY(s, hipEventCreate(&sc.ev1));
+  HIP_TRY(s, ledger::event_create(&sc.ev0));
+  HIP_TRY(s, ledger::event_create(&sc.ev1));
   const bool eager = under_profiler();  // rocprofv3 7.2 segfaults on a second graph instantiation: launch eagerly there
   if (eager) {
     enqueue_one(&u);
@@ -92,8 +92,8 @@ int pies_profile_substep(pies_solver_t* s, int kernel, uint32_t* launches, doubl
     sc.capturing = true;
     enqueue_one(&u);
     sc.capturing = false;
-    HIP_TRY(s, hipStreamEndCapture(s->stream, &sc.g));
-    HIP_TRY(s, hipGraphInstantiate(&sc.ge, sc.g, nullptr, nullptr, 0));
+    HIP_TRY(s, ledger::end_capture(s->stream, &sc.g));
+    HIP_TRY(s, ledger::graph_instantiate(&sc.ge, sc.g));
     HIP_TRY(s, hipGraphLaunch(sc.ge, s->stream));  // warm
   }
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -127,7 +127,7 @@ int pies_profile_in_situ(pies_solver_t* s, int kernel, uint32_t substeps, uint32
   Probe probe;
   probe.kernel = kernel;
   probe.stream = s->stream;
-  struct Clear { pies_solver* s; Probe* p; ~Clear() { s->probe = nullptr; for (hipEvent_t e : p->events) (void)hipEventDestroy(e); } } clear{s, &probe};
+  struct Clear { pies_solver* s; Probe* p; ~Clear() { s->probe = nullptr; for (hipEvent_t e : p->events) (void)ledger::event_destroy(e); } } clear{s, &probe};
   const bool isPD = s->opt.solver == PIES_SOLVER_PD;
   uint64_t u = 0;
   if (isPD) enqueue_pd_substep(s, -1, nullptr, nullptr);  // warm: caches and clocks as in a running simulation

@@ -13,7 +13,7 @@ using namespace pies;
 namespace pies {
 
 void ray_free_device(pies_solver* s) {
-  for (void* p : s->ray.allocations) (void)hipFree(p);
+  for (void* p : s->ray.allocations) (void)ledger::dev_free(p);
   s->ray = RayBuffers{};
 }
 
@@ -30,11 +30,11 @@ int ray_grow_bytes(pies_solver* s, size_t bytes, void** d) {
   RayBuffers& B = s->ray;
   if (*d) {
     B.allocations.erase(std::remove(B.allocations.begin(), B.allocations.end(), *d), B.allocations.end());
-    (void)hipFree(*d);
+    (void)ledger::dev_free(*d);
     *d = nullptr;
   }
   void* p = nullptr;
-  HIP_TRY(s, hipMalloc(&p, std::max<size_t>(bytes, 1)));
+  HIP_TRY(s, ledger::dev_malloc(&p, std::max<size_t>(bytes, 1)));
   B.allocations.push_back(p);
   *d = p;
   return PIES_OK;

@@ -113,7 +113,7 @@ void build_grid(const std::vector<Box>& boxes, ElementGrid& G) {
 }  // namespace
 
 void skin_free_device(pies_solver* s) {
-  for (void* p : s->skinAllocations) (void)hipFree(p);
+  for (void* p : s->skinAllocations) (void)ledger::dev_free(p);
   s->skinAllocations.clear();
   s->skin = SkinArrays{};
   s->d_skinOut = nullptr;
@@ -125,7 +125,7 @@ namespace {
 template <class T> int skin_upload_array(pies_solver* s, const std::vector<T>& h, const T** d) {
   *d = nullptr;
   void* p = nullptr;
-  HIP_TRY(s, hipMalloc(&p, std::max<size_t>(h.size(), 1) * sizeof(T)));
+  HIP_TRY(s, ledger::dev_malloc(&p, std::max<size_t>(h.size(), 1) * sizeof(T)));
   s->skinAllocations.push_back(p);
   if (!h.empty()) HIP_TRY(s, hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s->stream));
   *d = static_cast<const T*>(p);
@@ -170,14 +170,14 @@ int skin_upload(pies_solver* s) {
   S.nVerts = static_cast<uint32_t>(nv);
   S.nTris = static_cast<uint32_t>(nt);
   void* p = nullptr;
-  HIP_TRY(s, hipMalloc(&p, 6ull * nv * sizeof(float)));
+  HIP_TRY(s, ledger::dev_malloc(&p, 6ull * nv * sizeof(float)));
   s->skinAllocations.push_back(p);
   s->d_skinOut = static_cast<float*>(p);
   if (s->h_skinStage_n < nv) {
-    if (s->h_skinStage) (void)hipHostFree(s->h_skinStage);
+    if (s->h_skinStage) (void)ledger::host_free(s->h_skinStage);
     s->h_skinStage = nullptr;
     s->h_skinStage_n = 0;
-    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_skinStage), 6ull * nv * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(s, ledger::host_malloc(reinterpret_cast<void**>(&s->h_skinStage), 6ull * nv * sizeof(float), hipHostMallocDefault));
     s->h_skinStage_n = nv;
   }
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // the staging vectors die with this scope

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/pies_hip.h"
+#include "resource_ledger.h"
 #include "kernels.h"
 #include "pd_kernels.h"
 #include "hash_kernels.h"
@@ -156,7 +157,7 @@ struct Probe {
   void mark() {
     if (used == events.size()) {
       hipEvent_t e = nullptr;
-      if (hipEventCreate(&e) != hipSuccess) { failed = true; return; }
+      if (ledger::event_create(&e) != hipSuccess) { failed = true; return; }
       events.push_back(e);
     }
     if (hipEventRecord(events[used++], stream) != hipSuccess) failed = true;
@@ -426,7 +427,6 @@ struct pies_solver {
 
   hipGraph_t graph = nullptr;
   hipGraphExec_t graphExec = nullptr;
-  std::vector<std::pair<hipGraph_t, hipGraphExec_t>> retiredGraphs;  // profile-pass graphs, freed with the handle
   // PD: the substep graph exists once per (captured CG iterations, contact-row variant) - a ladder of budgets 2, 4, 8, ... up
   // to the ceiling of pies_set_pcg, instantiated together - so that following the solves means launching another executable
   // graph, not capturing and instantiating one in the middle of a frame (~11 ms).  graph / graphExec then alias an entry.
@@ -435,6 +435,7 @@ struct pies_solver {
   bool graphFromLadder = false;
   uint32_t launchCounts[PIES_KERNEL_COUNT] = {};
   pies::Probe* probe = nullptr;  // set for the duration of pies_profile_in_situ
+  float lastWindingMs = -1.0f;   // diagnostic build only (tools/probe_trimesh.py): this handle's last k_winding launch between two events
 
   uint32_t nodeCount() const { return static_cast<uint32_t>(h_radius.size()); }
 };

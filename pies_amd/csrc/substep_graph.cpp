@@ -28,18 +28,13 @@ void destroy_graph(pies_solver* s) {
   // graphs are not destroyed while a profiler is attached (rocprofv3 7.2 crashes on graph destruction)
   if (!under_profiler()) {
     if (!s->graphFromLadder) {
-      if (s->graphExec) (void)hipGraphExecDestroy(s->graphExec);
-      if (s->graph) (void)hipGraphDestroy(s->graph);
+      if (s->graphExec) (void)ledger::graph_exec_destroy(s->graphExec);
+      if (s->graph) (void)ledger::graph_destroy(s->graph);
     }
     for (auto& kv : s->pdLadder) {
-      if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-      if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
+      if (kv.second.exec) (void)ledger::graph_exec_destroy(kv.second.exec);
+      if (kv.second.graph) (void)ledger::graph_destroy(kv.second.graph);
     }
-    for (auto& ge : s->retiredGraphs) {
-      (void)hipGraphExecDestroy(ge.second);
-      (void)hipGraphDestroy(ge.first);
-    }
-    s->retiredGraphs.clear();
   }
   s->pdLadder.clear();
   s->graphFromLadder = false;
@@ -572,9 +567,9 @@ int select_pd_graph(pies_solver* s) {
 static int capture_substep(pies_solver* s, uint32_t* counts, hipGraph_t* graph, hipGraphExec_t* exec) {
   HIP_TRY(s, hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
   enqueue_substep(s, counts);
-  hipError_t e = hipStreamEndCapture(s->stream, graph);
+  hipError_t e = ledger::end_capture(s->stream, graph);
   if (e != hipSuccess) return fail(s, PIES_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  if (exec) HIP_TRY(s, hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
+  if (exec) HIP_TRY(s, ledger::graph_instantiate(exec, *graph));
   return PIES_OK;
 }
 
@@ -586,7 +581,7 @@ int capture_graph(pies_solver* s) {
     // count launches without running them: a capture that is thrown away
     hipGraph_t tmp = nullptr;
     const int rc = capture_substep(s, s->launchCounts, &tmp, nullptr);
-    if (tmp) (void)hipGraphDestroy(tmp);
+    if (tmp) (void)ledger::graph_destroy(tmp);
     return rc;
   }
   if (!uses_ladder(s)) return capture_substep(s, s->launchCounts, &s->graph, &s->graphExec);
@@ -602,8 +597,13 @@ int capture_graph(pies_solver* s) {
       s->triFastRows = rows;
       s->dev.pd.cg.useCAp = rows ? 1 : 0;
       pies_solver::PdGraph g;
-      if (int rc = capture_substep(s, g.counts, &g.graph, &g.exec)) return rc;
+      const int rc = capture_substep(s, g.counts, &g.graph, &g.exec);
+      // entered also when the capture failed half way (a graph without an executable): destroy_graph releases what it left.
+      // select_pd_graph is not reached on that path, and the caller (pies_finalize, or the re-capture before a tick) leaves
+      // sceneDirty / graphDirty set when this fails: the ladder is captured again before an entry with a null executable could
+      // be selected
       s->pdLadder[ladder_key(r, rows)] = g;
+      if (rc) return rc;
     }
   s->pcgBudget = wantBudget;
   s->triFastRows = wantRows;

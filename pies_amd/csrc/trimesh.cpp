@@ -15,10 +15,6 @@ using namespace pies;
 
 namespace {
 
-#ifdef PIES_EXPERIMENTS
-float g_lastWindingMs = -1.0f;  // tools/probe_trimesh.py: the last k_winding launch between two events on its stream
-#endif
-
 const char* check_mesh(uint32_t nv, const float* positions, uint32_t nt, const uint32_t* tri) {
   if (!positions || nv == 0) return "no vertices";
   if (!tri || nt == 0) return "no triangles";
@@ -44,8 +40,8 @@ int winding_on_device(pies_solver* s, uint32_t nv, const float* positions, uint3
   if (int rc = dev_alloc(s, n, &dIn)) return rc;
 #ifdef PIES_EXPERIMENTS
   hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(s, hipEventCreate(&ev[0]));
-  HIP_TRY(s, hipEventCreate(&ev[1]));
+  HIP_TRY(s, ledger::event_create(&ev[0]));
+  HIP_TRY(s, ledger::event_create(&ev[1]));
   HIP_TRY(s, hipEventRecord(ev[0], s->stream));
 #endif
   launch_winding(s->stream, dPos, dTri, nt, L, dW, dIn);
@@ -53,9 +49,9 @@ int winding_on_device(pies_solver* s, uint32_t nv, const float* positions, uint3
 #ifdef PIES_EXPERIMENTS
   HIP_TRY(s, hipEventRecord(ev[1], s->stream));
   HIP_TRY(s, hipEventSynchronize(ev[1]));
-  HIP_TRY(s, hipEventElapsedTime(&g_lastWindingMs, ev[0], ev[1]));
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
+  HIP_TRY(s, hipEventElapsedTime(&s->lastWindingMs, ev[0], ev[1]));
+  (void)ledger::event_destroy(ev[0]);
+  (void)ledger::event_destroy(ev[1]);
 #endif
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (winding) HIP_TRY(s, hipMemcpy(winding, dW, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -136,9 +132,9 @@ std::vector<uint32_t> boundary_triangles(const std::vector<float>& pos, const st
 extern "C" {
 
 #ifdef PIES_EXPERIMENTS
-int pies_exp_winding_ms(float* out) {
-  if (!out) return PIES_ERR_INVALID;
-  *out = g_lastWindingMs;
+int pies_exp_winding_ms(pies_solver_t* s, float* out) {
+  if (!s || !out) return PIES_ERR_INVALID;
+  *out = s->lastWindingMs;
   return PIES_OK;
 }
 #endif

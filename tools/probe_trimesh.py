@@ -25,12 +25,13 @@ from pies_amd import capi  # noqa: E402
 from test_trimesh import icosphere, lattice_of  # noqa: E402
 
 
-def kernel_ms(L):
+def kernel_ms(L, g):
+    """the handle's last k_winding launch (diagnostic library only)"""
     if not hasattr(L, "pies_exp_winding_ms"):
         return None
-    L.pies_exp_winding_ms.argtypes = [C.POINTER(C.c_float)]
+    L.pies_exp_winding_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     ms = C.c_float()
-    return float(ms.value) if L.pies_exp_winding_ms(C.byref(ms)) == 0 and ms.value >= 0 else None
+    return float(ms.value) if L.pies_exp_winding_ms(g._h, C.byref(ms)) == 0 and ms.value >= 0 else None
 
 
 def main():
@@ -47,7 +48,7 @@ def main():
             t0 = time.perf_counter()
             g.voxelize_tri_mesh(v, tri, origin, cell, dims)
             call = (time.perf_counter() - t0) * 1e3
-            k = kernel_ms(L)
+            k = kernel_ms(L, g)
             best_call = call if best_call is None else min(best_call, call)
             best_kernel = k if best_kernel is None or (k is not None and k < best_kernel) else best_kernel
         t0 = time.perf_counter()
