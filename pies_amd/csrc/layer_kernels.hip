@@ -59,7 +59,9 @@ PIES_DEV uint32_t hi16(uint32_t v) { return v >> 16; }
 // bits of tc_lid) instead of three float4 per element from HBM.  A template parameter: neither path pays the other's registers.
 // FORM: 1 = the tetrahedral projection on row pairs with its rare paths behind wave-uniform tests (tet_rows.h), 0 = tet_core; the
 // same bits either way.  The 256-register instantiations have both (launch_layer: PIES_LAYER_TET_FORM); the 128-register ones keep tet_core.
-template <int BLOCK, int TETV, int WPE = 1, bool DICT = false, int FORM = 0>
+// DIST: 1 = the distance projection's three quotients from one reciprocal (distance_quotient.h), 0 = three divisions; the same bits
+// either way.  The row-pair instantiations have both (launch_layer: PIES_LAYER_DIST_FORM); every other one has 1.
+template <int BLOCK, int TETV, int WPE = 1, bool DICT = false, int FORM = 0, int DIST = 1>
 __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D, LayerLaunch L, LayerParams P) {
   static_assert(FORM == 0 || TETV == 0, "the row-pair form is the full projection");
   static_assert(3 * kLayerRestMaxSets <= BLOCK, "the prologue requests the rest dictionary with one load per lane");
@@ -307,13 +309,13 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
           }
           if (off[c] + tid < off[c + 1] && PIES_IN_BOUNDS(max(lo16(id[c]), hi16(id[c])) < m, 12u)) {
             float4 a = sp[lo16(id[c])];
-            distance_core(a, sp[hi16(id[c])], rw[c]);
+            distance_core<DIST != 0>(a, sp[hi16(id[c])], rw[c]);
             sp[lo16(id[c])] = a;
           }
           for (uint32_t t = off[c] + tid + BLOCK; t < off[c + 1]; t += BLOCK) {  // classes larger than the workgroup
             const uint32_t jd = D.dc_lid[t];
             float4 a = sp[lo16(jd)];
-            distance_core(a, sp[hi16(jd)], D.dc_rw[t]);
+            distance_core<DIST != 0>(a, sp[hi16(jd)], D.dc_rw[t]);
             sp[lo16(jd)] = a;
           }
           lds_barrier();
@@ -324,7 +326,7 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
         for (uint32_t t = off[c] + tid; t < off[c + 1]; t += BLOCK) {
           const uint32_t jd = D.dc_lid[t];
           float4 a = sp[lo16(jd)];
-          distance_core(a, sp[hi16(jd)], D.dc_rw[t]);
+          distance_core<DIST != 0>(a, sp[hi16(jd)], D.dc_rw[t]);
           sp[lo16(jd)] = a;
         }
         lds_barrier();
@@ -493,6 +495,8 @@ static hipError_t layer_prepare_variants(int bytes) {
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<1024, 0, 1, DICT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 1, DICT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 1, DICT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<256, 0, 1, DICT, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer<512, 0, 1, DICT, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   return e;
 }
 // The limit belongs to the function on the device that is current, whichever handle set it: it is only ever raised, and what it has
@@ -515,8 +519,13 @@ hipError_t layer_prepare(uint32_t maxGroupNodes, uint32_t restSets) {
 }
 
 template <bool DICT>
-static void launch_layer_variant(hipStream_t st, uint32_t want, bool throughput, bool rowForm, size_t lds, const NodeArrays& nd,
+static void launch_layer_variant(hipStream_t st, uint32_t want, bool throughput, bool rowForm, bool quotientForm, size_t lds, const NodeArrays& nd,
                                  const LayerData& D, const LayerLaunch& L, const LayerParams& P) {
+  if (rowForm && !quotientForm && !throughput && want <= 512) {  // the same with the distance projection's three divisions
+    if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0, 1, DICT, 1, 0>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
+    else hipLaunchKernelGGL((k_layer<512, 0, 1, DICT, 1, 0>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
+    return;
+  }
   if (rowForm && !throughput && want <= 512) {  // the 256-register instantiations with the projection on row pairs (tet_rows.h)
     if (want <= 256) hipLaunchKernelGGL((k_layer<256, 0, 1, DICT, 1>), dim3(L.groups), dim3(256), lds, st, nd, D, L, P);
     else hipLaunchKernelGGL((k_layer<512, 0, 1, DICT, 1>), dim3(L.groups), dim3(512), lds, st, nd, D, L, P);
@@ -567,8 +576,11 @@ void launch_layer(hipStream_t st, const NodeArrays& nd, const LayerData& D, cons
   const bool throughput = L.groups > 256u;  // several tiles per compute unit
   // PIES_LAYER_TET_FORM=0 (tuning switch; tests and A/B): tet_core in every instantiation.  The same bits either way.
   const bool rowForm = [] { const char* e = tuning_env("PIES_LAYER_TET_FORM"); return !e || e[0] != '0'; }();
-  if (restDict) launch_layer_variant<true>(st, want, throughput, rowForm, lds, nd, D, L, P);
-  else launch_layer_variant<false>(st, want, throughput, rowForm, lds, nd, D, L, P);
+  // PIES_LAYER_DIST_FORM=0 (tuning switch; tests and A/B): the distance projection divides three times, as before round 14, in the
+  // row-pair instantiations (the others have the one form).  The same bits either way.
+  const bool quotientForm = [] { const char* e = tuning_env("PIES_LAYER_DIST_FORM"); return !e || e[0] != '0'; }();
+  if (restDict) launch_layer_variant<true>(st, want, throughput, rowForm, quotientForm, lds, nd, D, L, P);
+  else launch_layer_variant<false>(st, want, throughput, rowForm, quotientForm, lds, nd, D, L, P);
 }
 
 }  // namespace pies

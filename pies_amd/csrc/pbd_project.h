@@ -3,6 +3,7 @@
 // every schedule executes the same IEEE sequence per constraint; they differ only in where the node records live.
 #pragma once
 #include "dev_math.h"
+#include "distance_quotient.h"
 
 namespace pies {
 
@@ -42,14 +43,22 @@ PIES_DEV void position_core(float4& p, const float4 tw) {
 }
 
 // DistanceConstraint (Constraints.cpp:11-37): only node a moves, by the full correction.  rw = (rest, w)
+// SHARED: the three quotients by dist from one reciprocal (distance_quotient.h) for lanes whose operands are in the range where
+// that is the compiler's division bit for bit; every other lane, and every lane with SHARED = false, divides with `/`.
+template <bool SHARED = true>
 PIES_DEV void distance_core(float4& a, const float4 b, const float2 rw) {
   const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-  const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-  float ux = 1.0f, uy = 0.0f, uz = 0.0f;
-  if (dist > 0.00001f) {
-    ux = dx / dist;
-    uy = dy / dist;
-    uz = dz / dist;
+  const float sum = dx * dx + dy * dy + dz * dz;
+  float dist, ux = 1.0f, uy = 0.0f, uz = 0.0f;
+  if (SHARED) {
+    dq::direction(dx, dy, dz, sum, dq::HardwareSeed(), dist, ux, uy, uz);
+  } else {
+    dist = sqrtf(sum);
+    if (dist > dq::kDistMin) {
+      ux = dx / dist;
+      uy = dy / dist;
+      uz = dz / dist;
+    }
   }
   const float nd = -(rw.x - dist);  // -disp
   const float px = a.x + nd * ux, py = a.y + nd * uy, pz = a.z + nd * uz;

@@ -197,7 +197,7 @@ def main():
         plain = compile_isa(tmp, "plain.s", argv)
     out = {}
     for form, what in ((0, "tet_core (the form before tet_rows.h)"), (1, "tet_rows.h")):
-        sym = "_ZN4pies7k_layerILi%dELi0ELi1ELb%dELi%dEEE" % (block, dict_, form)
+        sym = "_ZN4pies7k_layerILi%dELi0ELi1ELb%dELi%dELi1EEE" % (block, dict_, form)  # (DIST = 1: the distance projection's product form)
         title = "k_layer<%d, 0, 1, %s, %d>, %s" % (block, "true" if dict_ else "false", form, what)
         total, n_noted, regs = report(noted, sym, title, dump if form == 1 else None)
         n_plain = len(kernel_text(plain, sym)[0])

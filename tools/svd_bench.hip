@@ -11,7 +11,9 @@
 //
 // Last, the issue cost of packed fp32 for a wavefront alone on its SIMD: a stream of independent v_pk_fma_f32 on aligned pairs
 // against twice as many v_fma_f32 (build this file with -fno-slp-vectorize as well: the scalar stream then stays scalar, and the
-// projection figures are those of the scalar build).
+// projection figures are those of the scalar build).  The scalar stream runs twice more: with lanes 0-31 alone active (does a
+// half-empty wavefront issue faster?) and with two wavefronts per SIMD (what a second wavefront's instruction costs the first) -
+// the two numbers that price any form of the projection that splits an element over lanes or wavefronts.
 //
 // build: hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I pies_amd/csrc -I include tools/svd_bench.hip -o /tmp/svd_bench
 #include <hip/hip_runtime.h>
@@ -72,8 +74,10 @@ template <int VARIANT, bool FLAT> static void run(const char* name, float4* d) {
 
 // 16 independent accumulators per lane: 8 packed fused multiply-adds, or 16 scalar ones, per round
 typedef float pk2 __attribute__((ext_vector_type(2)));
-template <bool PACKED> __global__ void k_issue(float4* out, int rounds, float m0, float c0) {  // (m0, c0 from the host: operands in registers)
+// HALF: lanes 32-63 of every wavefront leave at once
+template <bool PACKED, bool HALF = false> __global__ void k_issue(float4* out, int rounds, float m0, float c0) {  // (m0, c0 from the host: operands in registers)
   const float t = 1.0f + 1.0e-6f * static_cast<float>(threadIdx.x);
+  if (HALF && (threadIdx.x & 63u) >= 32u) return;
   if (PACKED) {
     pk2 a[8];
 #pragma unroll
@@ -104,17 +108,17 @@ template <bool PACKED> __global__ void k_issue(float4* out, int rounds, float m0
     out[threadIdx.x + blockIdx.x * blockDim.x] = make_float4(s, 0.f, 0.f, 0.f);
   }
 }
-template <bool PACKED> static float issue_ns(float4* d) {  // ns per instruction, one wavefront per SIMD
+template <bool PACKED, bool HALF = false> static float issue_ns(float4* d, int threads = 256) {  // ns per instruction of one wavefront; 256 threads: one wavefront per SIMD
   const int rounds = 2000, per_round = PACKED ? 64 : 128;
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  hipLaunchKernelGGL((k_issue<PACKED>), dim3(256), dim3(256), 0, 0, d, rounds, 0.999f, 1.0e-3f);
+  hipLaunchKernelGGL((k_issue<PACKED, HALF>), dim3(256), dim3(threads), 0, 0, d, rounds, 0.999f, 1.0e-3f);
   hipDeviceSynchronize();
   float best = 1e30f;
   for (int rep = 0; rep < 5; ++rep) {
     hipEventRecord(e0, 0);
-    hipLaunchKernelGGL((k_issue<PACKED>), dim3(256), dim3(256), 0, 0, d, rounds, 0.999f, 1.0e-3f);
+    hipLaunchKernelGGL((k_issue<PACKED, HALF>), dim3(256), dim3(threads), 0, 0, d, rounds, 0.999f, 1.0e-3f);
     hipEventRecord(e1, 0);
     hipEventSynchronize(e1);
     float ms = 0.f;
@@ -131,6 +135,13 @@ int main() {
     const float pk = issue_ns<true>(d), sc = issue_ns<false>(d);
     std::printf("issue cost, one wavefront per SIMD, independent instructions: v_pk_fma_f32 %.3f ns, v_fma_f32 %.3f ns: a packed one costs %.2f scalar ones\n",
                 pk, sc, pk / sc);
+    // cycles at the clock the device reports (hipDeviceAttributeClockRate, kHz): per instruction of ONE wavefront's stream
+    int khz = 0;
+    hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, 0);
+    const float half = issue_ns<false, true>(d), two = issue_ns<false>(d, 512);
+    const float cyc = 1.0e-6f * static_cast<float>(khz);
+    std::printf("independent v_fma_f32 per wavefront, at %d MHz: one wavefront per SIMD %.3f ns = %.2f cycles; lanes 0-31 alone %.3f ns = %.2f cycles; "
+                "two wavefronts per SIMD %.3f ns = %.2f cycles each (%.2f per SIMD)\n", khz / 1000, sc, sc * cyc, half, half * cyc, two, two * cyc, 0.5f * two * cyc);
   }
   run<3, false>("healthy element, tet_rows.h (row pairs)", d);
   run<3, true>("flattened element (y = const), tet_rows.h (row pairs)", d);
