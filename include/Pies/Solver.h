@@ -541,6 +541,126 @@ public:
     }
     return out;
   }
+  // Extension (pies_apply_anchors in pies_hip.h states the rule): anchors tie nodes to frames that move - a tyre's rim to its hub, a
+  // cloth corner to a joint, a picked node to the mouse - under both solvers.  addAnchors stores a set (an asset like a field: it
+  // survives every scene edit and ends with clear()); applyAnchors ties the set's nodes for dt seconds to the frames as they stand
+  // and move now - a node's springs are solved together and implicitly, so any stiffness is stable; a pin puts the node on its
+  // point - and returns per frame the impulse the anchors gave the nodes, its torque about the frame's pivot and the number of live
+  // anchors: the host applies -impulse and -torque to its rigid body.  strength 0 releases a frame.  Call it before tick;
+  // getVertices() is refreshed the way tick refreshes it.
+  struct AnchorFrame : pies_anchor_frame_t {
+    // origin: the world position of local (0, 0, 0); the axes are the world's and pivot = origin until set otherwise
+    explicit AnchorFrame(const glm::vec3& originInWorld = glm::vec3(0.0f, 0.0f, 0.0f)) {
+      std::memset(static_cast<pies_anchor_frame_t*>(this), 0, sizeof(pies_anchor_frame_t));
+      for (int k = 0; k < 3; ++k) origin[k] = pivot[k] = originInWorld[k];
+      axes[0] = axes[4] = axes[8] = 1.0f;
+      strength = 1.0f;
+    }
+    // unit and orthogonal
+    AnchorFrame& setAxes(const glm::vec3& axis0, const glm::vec3& axis1, const glm::vec3& axis2) {
+      for (int k = 0; k < 3; ++k) {
+        axes[k] = axis0[k];
+        axes[3 + k] = axis1[k];
+        axes[6 + k] = axis2[k];
+      }
+      return *this;
+    }
+    AnchorFrame& setMotion(const glm::vec3& linear, const glm::vec3& angularVelocity, const glm::vec3& about) {
+      for (int k = 0; k < 3; ++k) {
+        velocity[k] = linear[k];
+        angular[k] = angularVelocity[k];
+        pivot[k] = about[k];
+      }
+      return *this;
+    }
+    AnchorFrame& setStrength(float s) {
+      strength = s;
+      return *this;
+    }
+    // a world position in the frame's coordinates: axis_j . (p - origin), each dot product summed left to right in fp32
+    glm::vec3 toLocal(const glm::vec3& p) const {
+      const float d[3] = {p[0] - origin[0], p[1] - origin[1], p[2] - origin[2]};
+      glm::vec3 l;
+      for (int j = 0; j < 3; ++j) l[j] = (axes[3 * j] * d[0] + axes[3 * j + 1] * d[1]) + axes[3 * j + 2] * d[2];
+      return l;
+    }
+  };
+  struct Anchor : pies_anchor_t {
+    static Anchor spring(uint32_t nodeId, uint32_t frameIndex, const glm::vec3& localPoint, float k, float c = 0.0f) {
+      return _make(nodeId, frameIndex, localPoint, k, c, 0u);
+    }
+    static Anchor pin(uint32_t nodeId, uint32_t frameIndex, const glm::vec3& localPoint) {
+      return _make(nodeId, frameIndex, localPoint, 0.0f, 0.0f, PIES_ANCHOR_PIN);
+    }
+
+   private:
+    static Anchor _make(uint32_t nodeId, uint32_t frameIndex, const glm::vec3& l, float k, float c, uint32_t f) {
+      Anchor a;
+      a.node = nodeId;
+      a.frame = frameIndex;
+      for (int j = 0; j < 3; ++j) a.local[j] = l[j];
+      a.stiffness = k;
+      a.damping = c;
+      a.flags = f;
+      return a;
+    }
+  };
+  struct AnchorReaction {
+    glm::vec3 impulse, torque;
+    uint32_t live;
+  };
+  // the set's id; frameCount: how many frames applyAnchors will be given for it
+  uint32_t addAnchors(const std::vector<Anchor>& anchors, uint32_t frameCount) {
+    std::vector<pies_anchor_t> records(anchors.begin(), anchors.end());
+    uint32_t id = 0;
+    _ck(pies_add_anchors(_handle(), static_cast<uint32_t>(records.size()), records.data(), frameCount, &id));
+    return id;
+  }
+  // the nodes `ids` tied by springs (k, c) to frame frameIndex where they are now, `frame` being where that frame stands now: the
+  // attachment points are the nodes' present positions.  frameCount 0: frameIndex + 1.
+  uint32_t addAnchorsHere(const std::vector<uint32_t>& ids, uint32_t frameIndex, const AnchorFrame& frame, float k, float c = 0.0f,
+                          uint32_t frameCount = 0) {
+    uint32_t n = 0;
+    _ck(pies_count(_handle(), PIES_NODES, &n));
+    std::vector<float> pos(3 * size_t(n));
+    if (n) _ck(pies_read_nodes(_handle(), PIES_NODE_POSITION, pos.data(), n));
+    std::vector<Anchor> anchors;
+    for (uint32_t id : ids) {
+      if (id >= n) throw std::runtime_error("Pies::Solver::addAnchorsHere: node id out of range");
+      anchors.push_back(Anchor::spring(id, frameIndex, frame.toLocal(glm::vec3(pos[3 * size_t(id)], pos[3 * size_t(id) + 1], pos[3 * size_t(id) + 2])), k, c));
+    }
+    return addAnchors(anchors, frameCount ? frameCount : frameIndex + 1);
+  }
+  // perAnchor, when given: per anchor of the set the impulse it gave its node (x, y, z) and its stretch (w)
+  std::vector<AnchorReaction> applyAnchors(uint32_t set, const std::vector<AnchorFrame>& frames, float dt,
+                                           std::vector<glm::vec4>* perAnchor = nullptr) {
+    const uint32_t n = static_cast<uint32_t>(frames.size());
+    std::vector<pies_anchor_frame_t> records(frames.begin(), frames.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n)), entries;
+    std::vector<uint32_t> live(n);
+    if (perAnchor) {
+      uint32_t count = 0;
+      _ck(pies_get_anchors(_handle(), set, nullptr, 0, &count, nullptr));
+      entries.resize(4 * size_t(count));
+    }
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_apply_anchors(_handle(), set, n, records.data(), dt, impulse.data(), torque.data(), live.data(),
+                           perAnchor ? entries.data() : nullptr));
+    _refreshPositions();
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
+    if (perAnchor) {
+      perAnchor->resize(entries.size() / 4);
+      for (size_t i = 0; i < perAnchor->size(); ++i)
+        for (int c = 0; c < 4; ++c) (*perAnchor)[i][c] = entries[4 * i + c];
+    }
+    std::vector<AnchorReaction> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].live = live[k];
+    }
+    return out;
+  }
   // Extension (pies_measure_elements / pies_measure_nodes in pies_hip.h state the rules): how the body is doing, evaluated on the
   // device without a read-back.  measureElements answers for elements [first, first + count) of the tetrahedral (PIES_TET) or the
   // volume (PIES_VOLUME) constraints in the order they were added - stretches, det F, volume, |F|^2, the norm of the Green strain

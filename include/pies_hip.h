@@ -710,6 +710,79 @@ typedef struct pies_surface_load { /* 16 words, no padding */
 } pies_surface_load_t;
 int pies_apply_surface_loads(pies_solver_t* s, uint32_t n_loads, const pies_surface_load_t* loads, float dt, float* out_impulse,
                              float* out_torque, uint32_t* out_nodes, float* out_volume, float* out_area);
+/* EXTENSION (the reference pins a node to where it stood at creation; goal constraints and fixed regions are PD only): ANCHORS - nodes
+ * tied to moving frames by implicit spring-dampers or by pins, applied where HBM holds the nodes, under both solvers: a tyre's rim on a
+ * rigid hub, a cloth corner on a joint, a mouse drag.  A device-side edit of node state like pies_collide_props, pies_apply_forces
+ * and pies_apply_surface_loads; it hands back what the attachment pulls with, per frame.
+ * SETS ARE ASSETS, like fields: pies_add_anchors stores n anchors that refer to n_frames frames and returns the set's id (0, 1, ...
+ * per handle); a set survives pies_finalize, scene edits and ticks and ends with pies_clear (ids start from 0 again) or
+ * pies_destroy.  The library keeps a host copy of every set - pies_get_anchors reads it and needs no device - and stages the device
+ * copy at the first use and again after a pies_finalize dropped it; pies_add_anchors works on PIES_DEVICE_NONE handles.  Node ids
+ * are HOST ids of nodes that exist when the set is added; nodes appended later do not disturb a set.  pies_get_anchors: anchors may
+ * be NULL (then capacity is not read), else capacity >= the set's count; n and n_frames may each be NULL.
+ * pies_apply_anchors applies one set with the frames of this call (n_frames records, the set's count) acting for dt seconds.  The
+ * outputs may each be NULL: out_impulse, out_torque (n_frames x 3), out_live (n_frames), out_anchor (n x 4, the set's own order).
+ * The rule, in fp32 without fused multiply-adds, with pies_collide_props' conventions: dot products summed left to right as
+ * x x + y y + z z, cross is pies_raycast's, a + b * t is the product rounded, then the sum, a vector times a scalar is taken
+ * componentwise, every test is the positive form written.  Only + - * / sqrtf and comparisons occur.
+ * A node has position p (invMass w in .w) and velocity v: the state the call found.  With h = dt, for anchor i with frame f:
+ *   t_i = ((origin + axis_0 * l_0) + axis_1 * l_1) + axis_2 * l_2        l = local
+ *   u_i = velocity + cross(angular, t_i - pivot)
+ *   x_i = p - t_i;   stretch_i = sqrtf(x_i . x_i)
+ * An anchor is LIVE iff w > 0 and strength_f > 0 (the positive form: a NaN is not live).  A node without a live anchor is not
+ * written.
+ *   SPRINGS.  For a node's live spring anchors, in ascending anchor index:
+ *     k_i = stiffness_i * strength_f;  c_i = damping_i * strength_f;  a_i = c_i + k_i * h
+ *     g_i = x_i * k_i + (v - u_i) * a_i
+ *     A = sum a_i,  G = sum g_i              (from 0.0f, ascending anchor index, componentwise)
+ *     hw = h * w;   e = -((G * hw) / (1 + hw * A));   v' = v + e
+ *     j_i = (g_i + e * a_i) * (-h)           the impulse anchor i gave the node
+ *   This is implicit Euler for a node held by several isotropic spring-dampers at once:
+ *   m e = -h sum (k_i (x_i + h (v' - u_i)) + c_i (v' - u_i)).  It is stable for every k dt; as k -> inf it gives p + h v' = t + h u:
+ *   the node reaches the moving target in one step.  Positions and previous positions are not written.
+ *   A LIVE PIN (PIES_ANCHOR_PIN; a node that carries a pin carries no other anchor of the set).  p = t_i, the previous position
+ *     = t_i, v' = u_i, and j_i = (u_i - v) * (1 / w): pies_collide_props' touch - the position correction itself carries no impulse.
+ * out_anchor[4 i .. 4 i + 3] = j_i and stretch_i; j is 0 for an anchor that is not live, the stretch is always given (of a pin:
+ * before the pin moved the node).  out_impulse[f] sums j_i of frame f's anchors in a fixed two-level order: per tile of 256
+ * consecutive anchor indices in ascending index from 0.0f (another frame's anchor adds 0), then the tiles in ascending index from
+ * 0.0f.  out_torque[f] sums cross(t_i - pivot_f, j_i) in the same order; out_live[f] counts the live anchors of frame f.  Nothing is
+ * summed with atomics and the order is a function of the set alone - not of a kernel variant, not of PIES_FLAG_RENUMBER_NODES -, so
+ * two calls agree bit for bit.  The host applies -impulse and -torque (about the frame's pivot) to its own body.  A call is ONE
+ * implicit solve per node over the set's anchors: two sets applied one after the other are not one combined set.
+ * Runs on the handle's stream behind whatever ticks and begun frames are queued, finalizes a changed scene first and synchronises
+ * once before it returns; export frames begun earlier, captured graphs and pies_launch_counts are left as they were.  The edit is in
+ * HBM only: the host mirror is marked stale for the velocities, and for positions and previous positions when the set has pins;
+ * nothing is uploaded.  With dt == 0 the springs do nothing and the pins still hold.  strength scales k and c of the frame's
+ * springs; 0 releases its springs AND its pins.
+ * pies_add_anchors: PIES_ERR_INVALID for NULL anchors or n == 0, a node id >= the node count, n_frames == 0 or > PIES_ANCHOR_FRAME_MAX,
+ * frame >= n_frames, a non-finite local, stiffness or damping negative or non-finite, an unknown flag, a node that carries a pin
+ * and any other anchor of the same set; PIES_ERR_UNSUPPORTED for more than 2^24 anchors or more than PIES_ANCHOR_SET_MAX sets.
+ * pies_apply_anchors: PIES_ERR_INVALID for an unknown set, n_frames different from the set's, NULL frames, a non-finite member of a
+ * frame, a negative strength, a negative or non-finite dt; PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked
+ * first). */
+#define PIES_ANCHOR_SET_MAX 64   /* sets per handle */
+#define PIES_ANCHOR_FRAME_MAX 64 /* frames per set */
+enum { PIES_ANCHOR_PIN = 1 }; /* flags */
+typedef struct pies_anchor { /* 32 bytes */
+  uint32_t node;   /* host node id */
+  uint32_t frame;  /* index into the frames of pies_apply_anchors */
+  float local[3];  /* the attachment point in the frame's coordinates */
+  float stiffness; /* k >= 0, finite */
+  float damping;   /* c >= 0, finite */
+  uint32_t flags;  /* 0 or PIES_ANCHOR_PIN */
+} pies_anchor_t;
+typedef struct pies_anchor_frame { /* 22 words, no padding */
+  float origin[3];   /* world position of local (0, 0, 0) */
+  float axes[9];     /* axis j = axes[3 j .. 3 j + 2], unit and orthogonal (the host's duty) */
+  float velocity[3]; /* velocity of the pivot */
+  float angular[3];  /* angular velocity about the pivot */
+  float pivot[3];    /* point the angular velocity and the returned torque refer to */
+  float strength;    /* >= 0, finite: scales k and c of the frame's springs; 0 releases its springs AND its pins */
+} pies_anchor_frame_t;
+int pies_add_anchors(pies_solver_t* s, uint32_t n, const pies_anchor_t* anchors, uint32_t n_frames, uint32_t* set);
+int pies_get_anchors(const pies_solver_t* s, uint32_t set, pies_anchor_t* anchors, uint32_t capacity, uint32_t* n, uint32_t* n_frames);
+int pies_apply_anchors(pies_solver_t* s, uint32_t set, uint32_t n_frames, const pies_anchor_frame_t* frames, float dt,
+                       float* out_impulse, float* out_torque, uint32_t* out_live, float* out_anchor);
 /* EXTENSION (the reference has no such query): STRAIN, VOLUME AND MOMENTUM MEASURES evaluated where HBM holds the body - how the
  * body is doing, without a read-back.  Both calls are READ-ONLY: node state, the host mirror's stale marks, export frames begun
  * earlier, captured graphs and pies_launch_counts are left exactly as they were.  They run on the handle's stream behind whatever

@@ -60,6 +60,8 @@ LOAD_PRESSURE, LOAD_GAS, LOAD_FLUID = 0, 1, 2  # pies_surface_load_t.type
 LOAD_INWARD = 1  # pies_surface_load_t.flags: the range's triangles are wound with their normals inward
 LOAD_MAX = 64  # PIES_LOAD_MAX
 LOAD_TO_END = 0xFFFFFFFF  # pies_surface_load_t.count: to the container's end
+ANCHOR_SET_MAX, ANCHOR_FRAME_MAX = 64, 64  # PIES_ANCHOR_SET_MAX: sets per handle; PIES_ANCHOR_FRAME_MAX: frames per set
+ANCHOR_PIN = 1  # pies_anchor_t.flags: the node sits on the attachment point
 ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
 MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
 IO_HOST_SYNC = 1  # PIES_IO_HOST_SYNC: a device-side read or write returns after its launches have finished
@@ -85,7 +87,7 @@ SYMBOLS = [
     "pies_add_skin", "pies_get_skin_binding", "pies_read_skin", "pies_export_acquire_skin",
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
-    "pies_apply_surface_loads",
+    "pies_apply_surface_loads", "pies_add_anchors", "pies_get_anchors", "pies_apply_anchors",
     "pies_measure_elements", "pies_measure_nodes",
     "pies_read_nodes_device", "pies_write_nodes_device", "pies_read_skin_device",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
@@ -314,6 +316,52 @@ class SurfaceLoad(C.Structure):
         return self
 
 
+class AnchorFrame(C.Structure):
+    """pies_anchor_frame_t field for field: a moving frame of pies_apply_anchors - where the host's rigid body is and how it moves."""
+    _fields_ = [
+        ("origin", C.c_float * 3), ("axes", C.c_float * 9), ("velocity", C.c_float * 3), ("angular", C.c_float * 3),
+        ("pivot", C.c_float * 3), ("strength", C.c_float),
+    ]
+
+    @classmethod
+    def make(cls, origin, axes=None, velocity=(0, 0, 0), angular=(0, 0, 0), pivot=None, strength=1.0):
+        """origin: the world position of local (0, 0, 0); axes: 3 x 3, row j the unit axis j (None: the world's); pivot None: the
+        origin; strength scales the stiffness and damping of the frame's springs, 0 releases its springs and its pins"""
+        f = cls()
+        f.origin[:] = [float(x) for x in origin]
+        f.axes[:] = [float(x) for x in np.asarray(np.eye(3) if axes is None else axes, dtype=np.float32).reshape(9)]
+        f.velocity[:] = [float(x) for x in velocity]
+        f.angular[:] = [float(x) for x in angular]
+        f.pivot[:] = [float(x) for x in (origin if pivot is None else pivot)]
+        f.strength = strength
+        return f
+
+
+class Anchor(C.Structure):
+    """pies_anchor_t field for field: one node tied to the point `local` of frame `frame` by a spring-damper, or pinned to it."""
+    _fields_ = [
+        ("node", C.c_uint32), ("frame", C.c_uint32), ("local", C.c_float * 3), ("stiffness", C.c_float), ("damping", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, node, frame_index, local, stiffness=0.0, damping=0.0, pin=False):
+        a = cls()
+        a.node, a.frame, a.stiffness, a.damping, a.flags = node, frame_index, stiffness, damping, ANCHOR_PIN if pin else 0
+        a.local[:] = [float(x) for x in local]
+        return a
+
+    @classmethod
+    def at(cls, node, frame_index, frame, position, stiffness=0.0, damping=0.0, pin=False):
+        """the anchor whose attachment point is the world `position` as `frame` (an AnchorFrame) stands: local_j = axis_j .
+        (position - origin), in fp32, each dot product summed left to right"""
+        f32 = np.float32
+        d = np.array(list(position), f32) - np.array(list(frame.origin), f32)
+        axes = np.array(list(frame.axes), f32).reshape(3, 3)
+        local = [(axes[j, 0] * d[0] + axes[j, 1] * d[1]) + axes[j, 2] * d[2] for j in range(3)]
+        return cls.make(node, frame_index, local, stiffness, damping, pin)
+
+
 class ElementMeasure(C.Structure):
     """pies_element_measure_t field for field: one element's record of pies_measure_elements (eight words)."""
     _fields_ = [("s", C.c_float * 3), ("j", C.c_float), ("volume", C.c_float), ("i1", C.c_float), ("green", C.c_float),
@@ -435,7 +483,10 @@ def load():
     sig["pies_collide_field_props"] = [vp, u32, C.POINTER(FieldProp), pf, pf, pu, pu]
     sig["pies_apply_forces"] = [vp, u32, C.POINTER(Force), f32, pf, pf, pu]
     sig["pies_apply_surface_loads"] = [vp, u32, C.POINTER(SurfaceLoad), f32, pf, pf, pu, pf, pf]
-    sig["pies_measure_elements"] = [vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
+    sig["pies_add_anchors"] = [vp, u32, C.POINTER(Anchor), u32, pu]
+    sig["pies_get_anchors"] = [vp, u32, C.POINTER(Anchor), u32, pu, pu]
+    sig["pies_apply_anchors"] = [vp, u32, u32, C.POINTER(AnchorFrame), f32, pf, pf, pu, pf]
+    sig["pies_measure_elements"] =[vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
     sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
     sig["pies_read_nodes_device"] = [vp, C.POINTER(DeviceNodes), u32, vp, u32]
     sig["pies_write_nodes_device"] = [vp, C.POINTER(DeviceNodes), vp, u32, vp, u32]
@@ -781,6 +832,46 @@ class Solver:
         the device holds them; every load reads the state the call found.  Returns (impulse float32 (k, 3), torque float32 (k, 3)
         about each load's point, nodes uint32 (k), volume float32 (k), area float32 (k)) with reaction=True, else None."""
         return self._node_edit(self._L.pies_apply_surface_loads, SurfaceLoad, loads, (dt,), reaction, extras=2)
+
+    def add_anchors(self, anchors, n_frames):
+        """pies_add_anchors: stores a set of anchors (a sequence of Anchor) that refer to n_frames frames.  Returns the set id.  A set
+        is an asset: it survives finalize, scene edits and ticks, and ends with clear() or the handle."""
+        anchors = list(anchors)
+        arr = (Anchor * max(len(anchors), 1))(*anchors)
+        out = C.c_uint32()
+        self._ck(self._L.pies_add_anchors(self._h, len(anchors), arr if anchors else None, n_frames, C.byref(out)))
+        return out.value
+
+    def get_anchors(self, anchor_set):
+        """pies_get_anchors: (anchors: a list of Anchor in the set's own order, n_frames), from the library's host copy"""
+        n, frames = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.pies_get_anchors(self._h, anchor_set, None, 0, C.byref(n), C.byref(frames)))
+        arr = (Anchor * max(n.value, 1))()
+        self._ck(self._L.pies_get_anchors(self._h, anchor_set, arr, n.value, None, None))
+        return [Anchor.from_buffer_copy(arr[i]) for i in range(n.value)], frames.value
+
+    def apply_anchors(self, anchor_set, frames, dt, reaction=True, per_anchor=False):
+        """pies_apply_anchors: ties the set's nodes to the frames (a sequence of AnchorFrame, as many as the set was added with) as
+        they stand and move now, for dt seconds, where the device holds the nodes.  Returns (impulse float32 (f, 3), torque
+        float32 (f, 3) about each frame's pivot, live uint32 (f)) with reaction=True - the host applies -impulse and -torque to its
+        own body -, followed by the per-anchor array float32 (n, 4): the impulse the anchor gave its node and its stretch, in the
+        set's own order, with per_anchor=True; None when neither is asked for."""
+        frames = list(frames)
+        k = len(frames)
+        arr = (AnchorFrame * max(k, 1))(*frames)
+        out, args = (), (None, None, None)
+        if reaction:
+            out = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32))
+            args = (_pf(out[0]), _pf(out[1]), _pu(out[2]))
+        if per_anchor:
+            n = C.c_uint32()
+            self._ck(self._L.pies_get_anchors(self._h, anchor_set, None, 0, C.byref(n), None))
+            out += (np.zeros((n.value, 4), np.float32),)
+            args += (_pf(out[-1]),)
+        else:
+            args += (None,)
+        self._ck(self._L.pies_apply_anchors(self._h, anchor_set, k, arr if k else None, dt, *args))
+        return out or None
 
     def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
         """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at

@@ -30,10 +30,11 @@ struct EditLane {
   bool haveVel = false;
 };
 
-PIES_DEV EditLane edit_lane(const PropPass& P) {
+// (h: a host id below P.nd.n when `live`)
+PIES_DEV EditLane edit_lane_at(const PropPass& P, uint32_t h, bool live) {
   EditLane L;
-  L.h = blockIdx.x * kPropTile + threadIdx.x;
-  L.live = L.h < P.nd.n;
+  L.h = h;
+  L.live = live;
   if (L.live) {
     L.i = P.inv ? P.inv[L.h] : L.h;
     const float4 p4 = P.nd.pos[L.i];
@@ -42,6 +43,10 @@ PIES_DEV EditLane edit_lane(const PropPass& P) {
     L.movable = !(L.w == 0.0f);
   }
   return L;
+}
+PIES_DEV EditLane edit_lane(const PropPass& P) {
+  const uint32_t h = blockIdx.x * kPropTile + threadIdx.x;
+  return edit_lane_at(P, h, h < P.nd.n);
 }
 
 PIES_DEV void need_velocity(const PropPass& P, EditLane& L) {

@@ -35,5 +35,7 @@ struct PropPass {
 void launch_prop_collide(hipStream_t st, const PropPass& P);
 // out[k * kPropSumWords + c]: the tile records of prop k folded in ascending tile index (c < 6 from 0.0f, c == 6 the hit count)
 void launch_prop_fold(hipStream_t st, const PropPass& P, float* out);
+// ... of nTiles tiles that are not tiles of node ids (anchor_kernels.h: tiles of anchor indices), nRecords <= PIES_PROP_MAX
+void launch_prop_fold_tiles(hipStream_t st, const uint64_t* tileMask, const float* tileSums, uint32_t nTiles, uint32_t nRecords, float* out);
 
 }  // namespace pies

@@ -58,8 +58,13 @@ void launch_prop_collide(hipStream_t st, const PropPass& P) {
 }
 
 void launch_prop_fold(hipStream_t st, const PropPass& P, float* out) {
-  if (!P.nd.n || !P.nProps || P.nProps > PIES_PROP_MAX || !P.tileMask) return;
-  hipLaunchKernelGGL(k_prop_fold, dim3(P.nProps), dim3(kPropTile), 0, st, P.tileMask, P.tileSums, prop_tiles(P.nd.n), P.nProps, out);
+  if (!P.nd.n) return;
+  launch_prop_fold_tiles(st, P.tileMask, P.tileSums, prop_tiles(P.nd.n), P.nProps, out);
+}
+
+void launch_prop_fold_tiles(hipStream_t st, const uint64_t* tileMask, const float* tileSums, uint32_t nTiles, uint32_t nRecords, float* out) {
+  if (!nTiles || !nRecords || nRecords > PIES_PROP_MAX || !tileMask) return;
+  hipLaunchKernelGGL(k_prop_fold, dim3(nRecords), dim3(kPropTile), 0, st, tileMask, tileSums, nTiles, nRecords, out);
 }
 
 }  // namespace pies

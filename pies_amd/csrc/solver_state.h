@@ -20,6 +20,7 @@
 #include "ray_kernels.h"
 #include "field_kernels.h"
 #include "measure_kernels.h"
+#include "anchor_kernels.h"
 
 namespace pies {
 
@@ -192,6 +193,23 @@ struct HostField {
   std::vector<float> samples;
 };
 
+// A set of anchors (pies_add_anchors, anchors.cpp): the host copy pies_get_anchors reads, and what the device copy is staged from -
+// the anchors sorted by (node, anchor index) as a compact list of the anchored HOST node ids in ascending id, offsets into the
+// sorted records and, in every record, its index in the set's own order.
+struct HostAnchorSet {
+  std::vector<pies_anchor_t> anchors;  // the set's own order
+  uint32_t nFrames = 0;
+  bool pins = false;                   // some anchor is a pin: a call edits positions and previous positions too
+  std::vector<uint32_t> nodes;         // anchored host node ids, ascending, once each
+  std::vector<uint32_t> offsets;       // nodes + 1: the node's records are [offsets[a], offsets[a + 1])
+  std::vector<AnchorRecord> records;   // sorted (anchor_kernels.h)
+};
+struct AnchorSetDevice {  // nullptr: not staged
+  uint32_t* nodes = nullptr;
+  uint32_t* offsets = nullptr;
+  AnchorRecord* records = nullptr;
+};
+
 // Device buffers of pies_raycast.  free_device drops them, so the triangle list never outlives the scene or the node numbering
 // it was built from; every buffer grows on demand and a handle that never casts a ray holds none.
 struct RayBuffers {
@@ -244,6 +262,14 @@ struct RayBuffers {
   float2* loadTileSums = nullptr;
   size_t loadSumCap = 0;                       // (slot, load) records
   std::vector<uint32_t> loadTilesHost;         // the staging copy of loadTiles: alive until the call has synchronised
+  // pies_apply_anchors (anchors.cpp) shares propOut, propTileMask and propTileSums above - its tiles are of 256 ANCHOR indices -;
+  // the device copies of the sets it has met (not staged: the host copy in pies_solver::h_anchors is staged again at the next
+  // use), the frames of a call and what the second walk leaves per anchor in the set's own order
+  AnchorSetDevice anchorSets[PIES_ANCHOR_SET_MAX] = {};
+  pies_anchor_frame_t* anchorFrames = nullptr;  // PIES_ANCHOR_FRAME_MAX records
+  float4* anchorImpulse = nullptr;              // per anchor: j, stretch
+  float4* anchorTorque = nullptr;               // per anchor: cross(t - pivot, j), the frame's index | the live bit
+  size_t anchorOutCap = 0;                      // anchors both hold
   // pies_measure_elements / pies_measure_nodes (measure.cpp) have their buffers to themselves.  Per container (0: PIES_TET, 1:
   // PIES_VOLUME) the elements staged in HOST order with node ids in DEVICE numbering, upload_tets' layout - the scene's own
   // tetrahedral records are in plan order and PBD stages no volume records
@@ -360,6 +386,7 @@ struct pies_solver {
   std::vector<uint32_t> h_lines;
   std::vector<pies::HostSkin> h_skins;  // extension: embedded surface meshes (pies_add_skin)
   std::vector<pies::HostField> h_fields;  // extension: signed distance fields (pies_add_field*); assets: only pies_clear drops them
+  std::vector<pies::HostAnchorSet> h_anchors;  // extension: anchor sets (pies_add_anchors); assets like the fields
   uint32_t constraintId = 0;
 
   bool sceneDirty = true;    // topology/rest data changed: rebuild plans + upload everything
