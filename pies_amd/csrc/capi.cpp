@@ -238,32 +238,34 @@ int pies_set_pcg_retry(pies_solver_t* s, int enabled) {
   return PIES_OK;
 }
 
+// the words of CgArrays::stats (CgStat), zeros where there is no PD system on a device
+static int download_pcg_stats(pies_solver* s, float st[kStatWords]) {
+  std::fill(st, st + kStatWords, 0.0f);
+  if (s->opt.solver != PIES_SOLVER_PD || !s->dev.pd.cg.stats) return PIES_OK;
+  HIP_TRY(s, hipSetDevice(s->device));
+  HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, kStatWords * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PIES_OK;
+}
+
 int pies_get_pcg_stats(pies_solver_t* s, float* max_rel_residual, uint32_t* max_iters_used, uint32_t* solves) {
   if (!s) return PIES_ERR_INVALID;
-  float st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (s->opt.solver == PIES_SOLVER_PD && s->dev.pd.cg.stats) {
-    HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  if (max_rel_residual) *max_rel_residual = std::sqrt(st[0]);
-  if (max_iters_used) *max_iters_used = static_cast<uint32_t>(st[1]);
-  if (solves) *solves = static_cast<uint32_t>(st[2]);
+  float st[kStatWords];
+  if (int rc = download_pcg_stats(s, st)) return rc;
+  if (max_rel_residual) *max_rel_residual = std::sqrt(st[kStatWorst]);
+  if (max_iters_used) *max_iters_used = static_cast<uint32_t>(st[kStatIters]);
+  if (solves) *solves = static_cast<uint32_t>(st[kStatSolves]);
   return PIES_OK;
 }
 
 int pies_get_pcg_health(pies_solver_t* s, uint64_t* short_solves, uint64_t* solves_total, uint32_t* substeps_retried, uint32_t* budget) {
   if (!s) return PIES_ERR_INVALID;
-  float st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (s->opt.solver == PIES_SOLVER_PD && s->dev.pd.cg.stats) {
-    HIP_TRY(s, hipSetDevice(s->device));
-    HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  // stats[4], [5]: solves left above the tolerance / solves run by the substeps whose result was kept (a substep
-  // that pies_tick ran again takes its counts back), since the buffers were built
+  float st[kStatWords];
+  if (int rc = download_pcg_stats(s, st)) return rc;
+  // kStatLife: solves left above the tolerance / solves run by the substeps whose result was kept (a substep that pies_tick ran
+  // again takes its counts back), since the buffers were built
   uint64_t life[2];
-  std::memcpy(life, st + 4, sizeof(life));  // (64-bit integer counters in the words [4..5] and [6..7])
+  std::memcpy(life, st + kStatLife, sizeof(life));
   if (short_solves) *short_solves = life[0];
   if (solves_total) *solves_total = life[1];
   if (substeps_retried) *substeps_retried = s->pcgRetries;
@@ -419,7 +421,7 @@ int pies_tick_async(pies_solver_t* s) {
     ++s->asyncSinceSync;
     if (s->goalDirty)
       if (int rc = pd_upload_goals(s)) return rc;
-    if (s->asyncSinceSync == 1) HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, 4 * sizeof(float), s->stream));
+    if (s->asyncSinceSync == 1) HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, kStatTickWords * sizeof(float), s->stream));
   } else if (s->nodeCollisions && s->dev.hash.counters) {
     // The node grid's captured radix passes hold the scene's cell box plus five key bits, and the host can only follow a
     // growing box at a synchronisation (adapt_sort_passes): a caller that queues PBD ticks blindly gets one every 16 ticks,
@@ -452,8 +454,8 @@ int pies_synchronize(pies_solver_t* s) {
 // runs again with four times the budget, up to the ceiling of pies_set_pcg.
 static int pd_tick_checked(pies_solver* s) {
   const uint32_t n = s->dev.nd.n;
-  float before[8], after[8];
-  HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, 4 * sizeof(float), s->stream));
+  float before[kStatWords], after[kStatWords];
+  HIP_TRY(s, hipMemsetAsync(s->dev.pd.cg.stats, 0, kStatTickWords * sizeof(float), s->stream));
   for (uint32_t sub = 0; sub < s->opt.timeSubsteps; ++sub) {
     HIP_TRY(s, hipMemcpyAsync(before, s->dev.pd.cg.stats, sizeof(before), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipMemcpyAsync(s->dev.snapPos, s->dev.nd.pos, n * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
@@ -465,9 +467,9 @@ static int pd_tick_checked(pies_solver* s) {
       if (int rc = launch_substep(s)) return rc;
       HIP_TRY(s, hipMemcpyAsync(after, s->dev.pd.cg.stats, sizeof(after), hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(s, hipStreamSynchronize(s->stream));
-      const bool ranShort = after[3] > before[3];
+      const bool ranShort = after[kStatShort] > before[kStatShort];
       if (!ranShort || s->pcgBudget >= s->pcgMaxIters || s->pcgPinned) {
-        if (ranShort) s->pcgShortSolves += static_cast<uint64_t>(after[3] - before[3]);
+        if (ranShort) s->pcgShortSolves += static_cast<uint64_t>(after[kStatShort] - before[kStatShort]);
         break;
       }
       // put the substep's input back (the statistics too: the attempt does not count) and capture a larger budget
@@ -481,7 +483,7 @@ static int pd_tick_checked(pies_solver* s) {
       s->pcgBudget = pcg_ran_short(s, s->pcgBudget);
       ++s->pcgRetries;
       if (const char* e = std::getenv("PIES_PCG_DEBUG"); e && e[0] == '1')
-        std::fprintf(stderr, "[pies] pcg: substep ran short (residual^2 %.3g): again with budget %u\n", after[0], s->pcgBudget);
+        std::fprintf(stderr, "[pies] pcg: substep ran short (residual^2 %.3g): again with budget %u\n", after[kStatWorst], s->pcgBudget);
       if (int rc = s->pdLadder.empty() ? capture_graph(s) : select_pd_graph(s)) return rc;
     }
   }

@@ -125,4 +125,10 @@ void launch_tet(hipStream_t st, float4* pos, const uint4* ids, const float4* q0,
 // BendConstraint: Constraints.h:121-129 + Constraints.cpp:312-366
 void launch_bend(hipStream_t st, float4* pos, const uint4* ids, const float2* angle_w, uint32_t start, uint32_t count);
 
+// Workgroups of `threads` threads (and ldsBytes of dynamic LDS) of a kernel that the current device (the solver's) holds at once,
+// halved so that a second solver on the card leaves room: the size of a launch whose workgroups wait for each other at a grid
+// barrier.  0: not known (the caller uses one workgroup).  Computed once per kernel, LDS size and device (a process may hold
+// handles on several).  Defined in pair_lists.hip.
+uint32_t resident_blocks_halved(const void* kernel, int threads, uint32_t ldsBytes = 0);
+
 }  // namespace pies

@@ -83,9 +83,5 @@ uint32_t pass_lists(hipStream_t st, const HashArrays& H, const PairArrays& P, fl
 // first attempt the repeat is armed, after the second the sequential loop takes a pass that neither attempt could keep
 uint32_t pass_end(hipStream_t st, const HashArrays& H, const PairArrays& P, const NodeArrays& nd, float gridSpacing, float friction,
                   float staticThreshold, uint32_t repeat);
-// Workgroups of `threads` threads of a kernel that the current device (the solver's) holds at once, halved so that a second solver
-// on the card leaves room: the size of a launch whose workgroups wait for each other at a grid barrier.  0: not known (the caller
-// uses one workgroup).  Computed once per kernel and device (a process may hold handles on several).
-uint32_t resident_blocks_halved(const void* kernel, int threads);
 
 }  // namespace pies

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <tuple>
 #include <utility>
 
 #include "pair_device.h"
@@ -796,19 +797,19 @@ __global__ void k_pair_arm(HashArrays H, PairArrays P) {
 }
 
 // ---- the host steps of a pass that both orders share -----------------------------------------------------------------------------
-uint32_t resident_blocks_halved(const void* kernel, int threads) {
+uint32_t resident_blocks_halved(const void* kernel, int threads, uint32_t ldsBytes) {
   static std::mutex mu;
-  static std::map<std::pair<const void*, int>, uint32_t> cache;
+  static std::map<std::tuple<const void*, uint32_t, int>, uint32_t> cache;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_pair(kernel, dev);
+  const auto key = std::make_tuple(kernel, ldsBytes, dev);
   const auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int perCu = 0;
   hipDeviceProp_t prop;
   uint32_t v = 0;
-  if (hipGetDeviceProperties(&prop, dev) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, threads, 0) == hipSuccess)
+  if (hipGetDeviceProperties(&prop, dev) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, threads, ldsBytes) == hipSuccess)
     v = static_cast<uint32_t>(std::max(0, perCu)) * static_cast<uint32_t>(std::max(0, prop.multiProcessorCount)) / 2u;
   cache[key] = v;
   return v;

@@ -62,43 +62,7 @@ struct CgStamp {
 };
 #endif
 
-// f(value, column) for every stored entry of row i (lane `lane` of slice `sl`): the row dictionary or the SELL arrays
-template <class F> PIES_DEV void row_entries(const CgArrays& A, uint32_t sl, uint32_t lane, uint32_t i, F f) {
-  if (A.rowStencil) {
-    if (i < A.n) {
-      const uint32_t rs = A.rowStencil[i];
-      const uint32_t b = rs & 0xffffffu, e = b + (rs >> 24);
-#pragma unroll 4
-      for (uint32_t q = b; q < e; ++q) {
-        const int2 pr = A.stencil[q];
-        f(__int_as_float(pr.y), static_cast<uint32_t>(static_cast<int>(i) + pr.x));
-      }
-    }
-  } else {
-    const uint32_t off = A.sliceOff[sl], width = (A.sliceOff[sl + 1] - off) >> 6;
-#pragma unroll 4
-    for (uint32_t kk = 0; kk < width; ++kk) {
-      const uint32_t at = off + (kk << 6) + lane;
-      f(A.val[at], A.col[at]);  // (padding entries: the row itself with value 0)
-    }
-  }
-}
-
 // ---- windowed rows (CgArrays: wRows ...) -----------------------------------------------------------------------------------
-// The chunks a workgroup sweeps: workgroups that share an XCD (equal blockIdx % 8) take one contiguous part of the chunks, like
-// slice_sweep's wavefronts.
-struct ChunkSweep {
-  uint32_t begin, end, step;
-};
-PIES_DEV ChunkSweep chunk_sweep(uint32_t nchunks, uint32_t nblocks) {
-  const uint32_t labels = nblocks < 8u ? nblocks : 8u;
-  const uint32_t x = blockIdx.x % labels, xb = blockIdx.x / labels;
-  const uint32_t nbx = (nblocks - x + labels - 1u) / labels;
-  const uint32_t segBeg = static_cast<uint32_t>((static_cast<uint64_t>(nchunks) * x) / labels);
-  const uint32_t segEnd = static_cast<uint32_t>((static_cast<uint64_t>(nchunks) * (x + 1u)) / labels);
-  return {segBeg + xb, segEnd, nbx};
-}
-
 // One sweep over the matrix in its windowed form, chunk by chunk:
 //   own(i, aux)         the row's own streaming work, in the natural order (coalesced); returns what its window slot holds and
 //                       may leave 16 bytes for the row's turn behind the sum in `aux` (AUX)
@@ -116,7 +80,7 @@ PIES_DEV void window_rows(const CgArrays& A, uint32_t nblocks, Own own, Halo hal
   extern __shared__ float4 pies_window[];
   float4* __restrict__ win = pies_window;
   float4* __restrict__ auxv = pies_window + A.wLdsSlots;  // (wRows slots behind the largest window)
-  const ChunkSweep cs = chunk_sweep(A.wChunks, nblocks);
+  const Sweep cs = xcd_sweep(A.wChunks, nblocks, 1u, 0u);  // a workgroup takes whole chunks, one per step
   const uint32_t R = A.wRows, spc = R >> 6;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   for (uint32_t c = cs.begin; c < cs.end; c += cs.step) {
@@ -179,36 +143,25 @@ PIES_DEV void window_rows(const CgArrays& A, uint32_t nblocks, Own own, Halo hal
 
 // r = f - (K + C) x ; t = D^-1 r ; partI = {r.t, r.r, f.f}.  RHS: f is evaluated here (Msn_h2 + the node's records + contacts +
 // shape / goal terms + floor: rhs_of_node with one lane per node) instead of being read from the array k_pd_rhs wrote.
-// prevPart != nullptr: an extra block closes the previous solve's statistics (see k_cg_init).
+// One more block opens the solve (solve_open; prevPart: the previous solve's final partials, or nullptr).
 template <bool RHS, bool WIN>
 __global__ void __launch_bounds__(kBlock) k_cg1_init(CgArrays A, const float4* __restrict__ x, const float4* __restrict__ f, RhsArrays R,
                                                      const float* __restrict__ prevPart) {
   if (blockIdx.x == A.npartsI) {
-    if (prevPart) solve_statistics(A, prevPart);
-    if (threadIdx.x == 0) {
-      A.scal[10] = 0.0f;
-      A.ticket[0] = 0u;
-      A.ticket[1] = 0u;
-    }
+    solve_open(A, prevPart);
     return;
   }
   float acc9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   Vec3f* __restrict__ t0 = A.t1[0];
-  // what a row does with (K x)_i (fp64 sums, see below), its own x and its right-hand side
+  // what a row does with (K x)_i (fp64 sums, see row_residual), its own x and its right-hand side; the contact part in DOUBLE
+  // here (see contact_row), in float in k_cg_init: kept as it is
   auto finish = [&](uint32_t i, double sx, double sy, double sz, const float4 xi, float4 fi) {
     double cx = 0.0, cy = 0.0, cz = 0.0;
     contact_row<4, double>(A, i, [&](uint32_t j, float& px, float& py, float& pz) { const float4 v = x[j]; px = v.x; py = v.y; pz = v.z; }, cx, cy, cz);
     if (!RHS) fi = f[i];
-    const float cd = A.cdiag[i], di = A.dinv[i];
-    const double cdd = static_cast<double>(cd);
-    const float rx = static_cast<float>(static_cast<double>(fi.x) - (fma(cdd, static_cast<double>(xi.x), sx) + cx));
-    const float ry = static_cast<float>(static_cast<double>(fi.y) - (fma(cdd, static_cast<double>(xi.y), sy) + cy));
-    const float rz = static_cast<float>(static_cast<double>(fi.z) - (fma(cdd, static_cast<double>(xi.z), sz) + cz));
-    const float tx = di * rx, ty = di * ry, tz = di * rz;
-    t0[i] = Vec3f{tx, ty, tz};
-    acc9[0] += rx * tx; acc9[1] += ry * ty; acc9[2] += rz * tz;
-    acc9[3] += rx * rx; acc9[4] += ry * ry; acc9[5] += rz * rz;
-    acc9[6] += fi.x * fi.x; acc9[7] += fi.y * fi.y; acc9[8] += fi.z * fi.z;
+    Vec3f t;
+    row_residual(A, i, xi, fi, sx, sy, sz, cx, cy, cz, t, acc9);
+    t0[i] = t;
   };
   if (WIN) {
     // (the right-hand side's gather is issued with the window's loads, in the natural order, and waits in LDS for the row's turn)
@@ -225,17 +178,13 @@ __global__ void __launch_bounds__(kBlock) k_cg1_init(CgArrays A, const float4* _
     return;
   }
   const uint32_t lane = threadIdx.x & 63u;
-  const SliceSweep sw = slice_sweep<1>(A.n, A.npartsI);
+  const Sweep sw = slice_sweep<1>(A.n, A.npartsI);
   for (uint32_t sl = sw.begin; sl < sw.end; sl += sw.step) {
     const uint32_t i = sl * 64u + lane;
     const bool live = i < A.n;
     float4 fi = make_float4(0.f, 0.f, 0.f, 0.f);
     if (RHS) fi = rhs_of_node<1>(R, i, 0u, live);  // (issued first: its gathers are in flight beside the row's)
-    // (K + C) x in DOUBLE: the products are ~ (m / h^2) |x| ~ 1e6 and cancel against f to a residual five orders smaller; summed
-    // in fp32 the row carries a noise of an ulp of 1e6 (0.1: 2e-5 in x per solve, a random walk over the local/global
-    // iterations - measured against the oracle's fp64 solve: 2.3 x the deviation of the reference's own fp32 arithmetic, in
-    // every variant of the local step and of the CG).  fp64 fused multiply-adds cost this memory-bound launch nothing.
-    double sx = 0.0, sy = 0.0, sz = 0.0;
+    double sx = 0.0, sy = 0.0, sz = 0.0;  // K x in double (see row_residual)
     row_entries(A, sl, lane, i, [&](float a, uint32_t j) {
       const float4 xj = x[j];
       const double ad = static_cast<double>(a);
@@ -256,20 +205,19 @@ template <bool WIN> __global__ void __launch_bounds__(kBlock) k_cg1_first(CgArra
   if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      A.scal[c] = red[c];  // gamma_0
-      A.scal[6 + c] = bb[c];
+      A.scal[kScalGamma + c] = red[c];  // gamma_0
+      A.scal[kScalBb + c] = bb[c];
     }
-    A.scal[9] = 0.0f;  // iterations of this solve
+    A.scal[kScalIters] = 0.0f;
   }
   if (all_converged(rr, bb, tol2)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       // the final residual norms themselves, for the statistics: partI is overwritten by the next solve's k_cg1_init while the
       // extra workgroup of that very launch closes this solve's statistics (a mix of two solves could read as "short")
 #pragma unroll
-      for (int c = 0; c < 3; ++c) A.scal[18 + c] = rr[c];
-      A.scal[11] = 0.0f;  // converged at the first look
-      A.scal[10] = 1.0f;
+      for (int c = 0; c < 3; ++c) A.scal[kScalFinalRr + c] = rr[c];
     }
+    solve_over(A, 0, 0);  // converged at the first look
     return;
   }
   const uint32_t lane = threadIdx.x & 63u;
@@ -289,7 +237,7 @@ template <bool WIN> __global__ void __launch_bounds__(kBlock) k_cg1_first(CgArra
         A, gridDim.x, [&](uint32_t i, float4&) { return slot(i); }, slot,
         [&](uint32_t i, float sx, float sy, float sz, const float4 ti, const float4) { finish(i, sx, sy, sz, ti.x, ti.y, ti.z); });
   } else {
-    const SliceSweep sw = slice_sweep<1>(A.n, gridDim.x);
+    const Sweep sw = slice_sweep<1>(A.n, gridDim.x);
     for (uint32_t sl = sw.begin; sl < sw.end; sl += sw.step) {
       const uint32_t i = sl * 64u + lane;
       float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -335,32 +283,44 @@ PIES_DEV void cg1_rows(const CgArrays& A, float4* __restrict__ x, int it, const 
     float cx, cy, cz;
     renew(j, ux, uy, uz, cx, cy, cz);
   };
+  // The row's own update, everything that does not wait for the row's sum: x, p, the new t (returned) and c, r.t and r.r
+  auto own = [&](uint32_t i, float& tx, float& ty, float& tz) {
+    float cx, cy, cz;
+    renew(i, tx, ty, tz, cx, cy, cz);
+    const Vec3f told = tO[i];
+    float px = told.x, py = told.y, pz = told.z;  // p = u + beta p_old, u = the OLD t
+    if (!FIRST) {
+      const Vec3f po = p[i];
+      px = fmaf(beta[0], po.x, px); py = fmaf(beta[1], po.y, py); pz = fmaf(beta[2], po.z, pz);
+    }
+    float4 xi = x[i];
+    xi.x = fmaf(alpha[0], px, xi.x);
+    xi.y = fmaf(alpha[1], py, xi.y);
+    xi.z = fmaf(alpha[2], pz, xi.z);
+    const float kd = A.kdiag[i] + A.cdiag[i];
+    const float rx = kd * tx, ry = kd * ty, rz = kd * tz;
+    x[i] = xi;
+    p[i] = Vec3f{px, py, pz};
+    tN[i] = Vec3f{tx, ty, tz};
+    cN[i] = Vec3f{cx, cy, cz};
+    acc[0] += rx * tx; acc[1] += ry * ty; acc[2] += rz * tz;
+    acc[6] += rx * rx; acc[7] += ry * ry; acc[8] += rz * rz;
+  };
+  // What waits for the row's sum (K t)_i: w = (K + C) t, a = D^-1 w and w.t
+  auto behind = [&](uint32_t i, float sx, float sy, float sz, float tx, float ty, float tz) {
+    contact_row<1>(A, i, fetch, sx, sy, sz);
+    const float cd = A.cdiag[i], di = A.dinv[i];
+    const float wx = fmaf(cd, tx, sx), wy = fmaf(cd, ty, sy), wz = fmaf(cd, tz, sz);
+    aN[i] = Vec3f{di * wx, di * wy, di * wz};
+    acc[3] += wx * tx; acc[4] += wy * ty; acc[5] += wz * tz;
+  };
   if (WIN) {
-    // The row's own updates - everything that does not wait for the row's sum - happen while its window slot is filled, in the
-    // natural order: x, p, the new t and c, r.t and r.r.  Behind the sum only w = (K + C) t, a = D^-1 w and w.t are left.
+    // the own updates happen while the row's window slot is filled, in the natural order
     window_rows<float, false>(
         A, gridDim.x,
         [&](uint32_t i, float4&) {
-          float tx, ty, tz, cx, cy, cz;
-          renew(i, tx, ty, tz, cx, cy, cz);
-          const Vec3f told = tO[i];
-          float px = told.x, py = told.y, pz = told.z;
-          if (!FIRST) {
-            const Vec3f po = p[i];
-            px = fmaf(beta[0], po.x, px); py = fmaf(beta[1], po.y, py); pz = fmaf(beta[2], po.z, pz);
-          }
-          float4 xi = x[i];
-          xi.x = fmaf(alpha[0], px, xi.x);
-          xi.y = fmaf(alpha[1], py, xi.y);
-          xi.z = fmaf(alpha[2], pz, xi.z);
-          const float kd = A.kdiag[i] + A.cdiag[i];
-          const float rx = kd * tx, ry = kd * ty, rz = kd * tz;
-          x[i] = xi;
-          p[i] = Vec3f{px, py, pz};
-          tN[i] = Vec3f{tx, ty, tz};
-          cN[i] = Vec3f{cx, cy, cz};
-          acc[0] += rx * tx; acc[1] += ry * ty; acc[2] += rz * tz;
-          acc[6] += rx * rx; acc[7] += ry * ry; acc[8] += rz * rz;
+          float tx, ty, tz;
+          own(i, tx, ty, tz);
           return make_float4(tx, ty, tz, 0.f);
         },
         [&](uint32_t j) {
@@ -368,17 +328,11 @@ PIES_DEV void cg1_rows(const CgArrays& A, float4* __restrict__ x, int it, const 
           fetch(j, ux, uy, uz);
           return make_float4(ux, uy, uz, 0.f);
         },
-        [&](uint32_t i, float sx, float sy, float sz, const float4 t, const float4) {
-          contact_row<1>(A, i, fetch, sx, sy, sz);
-          const float cd = A.cdiag[i], di = A.dinv[i];
-          const float wx = fmaf(cd, t.x, sx), wy = fmaf(cd, t.y, sy), wz = fmaf(cd, t.z, sz);
-          aN[i] = Vec3f{di * wx, di * wy, di * wz};
-          acc[3] += wx * t.x; acc[4] += wy * t.y; acc[5] += wz * t.z;
-        }, stamp);
+        [&](uint32_t i, float sx, float sy, float sz, const float4 t, const float4) { behind(i, sx, sy, sz, t.x, t.y, t.z); }, stamp);
     return;
   }
   const uint32_t lane = threadIdx.x & 63u;
-  const SliceSweep sw = slice_sweep<1>(A.n, gridDim.x);
+  const Sweep sw = slice_sweep<1>(A.n, gridDim.x);
   for (uint32_t sl = sw.begin; sl < sw.end; sl += sw.step) {
     const uint32_t i = sl * 64u + lane;
     float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -390,30 +344,9 @@ PIES_DEV void cg1_rows(const CgArrays& A, float4* __restrict__ x, int it, const 
       sz = fmaf(a, uz, sz);
     });
     if (i < A.n) {
-      contact_row<1>(A, i, fetch, sx, sy, sz);
-      float tx, ty, tz, cx, cy, cz;
-      renew(i, tx, ty, tz, cx, cy, cz);
-      const Vec3f told = tO[i];
-      float px = told.x, py = told.y, pz = told.z;  // p = u + beta p_old, u = the OLD t
-      if (!FIRST) {
-        const Vec3f po = p[i];
-        px = fmaf(beta[0], po.x, px); py = fmaf(beta[1], po.y, py); pz = fmaf(beta[2], po.z, pz);
-      }
-      float4 xi = x[i];
-      xi.x = fmaf(alpha[0], px, xi.x);
-      xi.y = fmaf(alpha[1], py, xi.y);
-      xi.z = fmaf(alpha[2], pz, xi.z);
-      const float cd = A.cdiag[i], di = A.dinv[i], kd = A.kdiag[i] + cd;
-      const float wx = fmaf(cd, tx, sx), wy = fmaf(cd, ty, sy), wz = fmaf(cd, tz, sz);
-      const float rx = kd * tx, ry = kd * ty, rz = kd * tz;
-      x[i] = xi;
-      p[i] = Vec3f{px, py, pz};
-      tN[i] = Vec3f{tx, ty, tz};
-      cN[i] = Vec3f{cx, cy, cz};
-      aN[i] = Vec3f{di * wx, di * wy, di * wz};
-      acc[0] += rx * tx; acc[1] += ry * ty; acc[2] += rz * tz;
-      acc[3] += wx * tx; acc[4] += wy * ty; acc[5] += wz * tz;
-      acc[6] += rx * rx; acc[7] += ry * ry; acc[8] += rz * rz;
+      float tx, ty, tz;
+      own(i, tx, ty, tz);
+      behind(i, sx, sy, sz, tx, ty, tz);
     }
   }
 }
@@ -437,7 +370,7 @@ PIES_DEV void cg1_scalars(const float gam[3], const float del[3], const float ga
 
 // Launch `it` of a solve's iterations (it >= 1): scalars from the partial sums of the launch before, then the rows.
 // overflow > 0: the solve's last captured launch; when the residual is still above the tolerance after its rows, its
-// workgroups (all resident, see cg_update_resident_blocks) run up to `overflow` more iterations themselves, one grid barrier
+// workgroups (all resident, see resident_blocks_halved) run up to `overflow` more iterations themselves, one grid barrier
 // per iteration where the captured path has a kernel boundary.
 // (Measured and dropped: register targets for this kernel.  __launch_bounds__(kBlock, 5) - five wavefronts per SIMD, the rows fit 85-92
 // registers without spills: 41.1 against 39.5 us per launch with the row dictionary at 1M rows; amdgpu_waves_per_eu(4, 4): 43.9
@@ -445,7 +378,7 @@ PIES_DEV void cg1_scalars(const float gam[3], const float del[3], const float ga
 // depends on at 1M rows is whether the launch before it streamed the same matrix arrays - see launch_pd_solve1.)
 template <bool FIRST, bool WIN>
 __global__ void __launch_bounds__(kBlock) k_cg1_iter(CgArrays A, float4* __restrict__ x, int it, float tol2, int overflow) {
-  if (A.scal[10] != 0.0f) return;  // the solve converged in an earlier launch
+  if (A.scal[kScalOver] != 0.0f) return;  // the solve converged in an earlier launch
   CgStamp st;
   st.open(it);
   st.mark();
@@ -456,40 +389,37 @@ __global__ void __launch_bounds__(kBlock) k_cg1_iter(CgArrays A, float4* __restr
   float red[9];
   float alpha[3], beta[3] = {0.f, 0.f, 0.f}, gam[3], bb[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) bb[c] = A.scal[6 + c];
+  for (int c = 0; c < 3; ++c) bb[c] = A.scal[kScalBb + c];
   if (FIRST) {
     block_reduce_partials<3>(A.part1[0] + 3, 9, A.partCount[2], red + 3);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      gam[c] = A.scal[c];
+      gam[c] = A.scal[kScalGamma + c];
       alpha[c] = red[3 + c] > 0.0f ? gam[c] / red[3 + c] : 0.0f;
     }
   } else {
     block_reduce_partials<9>(A.part1[(it - 1) & 1], 9, A.partCount[(it - 1) & 1], red);
     const float rr[3] = {red[6], red[7], red[8]};
     if (all_converged(rr, bb, tol2)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        A.scal[11] = static_cast<float>(1 + ((it - 1) & 1));  // where the final residual partials are
-        A.scal[10] = 1.0f;
-      }
+      solve_over(A, 1 + ((it - 1) & 1), it - 1);  // (the launch before this one wrote the final partials)
       return;
     }
     float gamOld[3], alphaOld[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       gam[c] = red[c];
-      gamOld[c] = A.scal[3 * (it & 1) + c];         // gamma_{it-2}
-      alphaOld[c] = A.scal[12 + 3 * (it & 1) + c];  // alpha_{it-2}
+      gamOld[c] = A.scal[kScalGamma + 3 * (it & 1) + c];    // gamma_{it-2}
+      alphaOld[c] = A.scal[kScalAlpha + 3 * (it & 1) + c];  // alpha_{it-2}
     }
     cg1_scalars(gam, red + 3, gamOld, alphaOld, alpha, beta);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      A.scal[3 * ((it - 1) & 1) + c] = gam[c];
-      A.scal[12 + 3 * ((it - 1) & 1) + c] = alpha[c];
+      A.scal[kScalGamma + 3 * ((it - 1) & 1) + c] = gam[c];
+      A.scal[kScalAlpha + 3 * ((it - 1) & 1) + c] = alpha[c];
     }
-    A.scal[9] = static_cast<float>(it);
+    A.scal[kScalIters] = static_cast<float>(it);
   }
   float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   uniform3(alpha);  // (the same in every lane: scalar registers for the rows' sweep)
@@ -525,11 +455,7 @@ __global__ void __launch_bounds__(kBlock) k_cg1_iter(CgArrays A, float4* __restr
     block_write_partial<9>(acc, A.part1[kk & 1], 9);
     if (blockIdx.x == 0 && threadIdx.x == 0) A.partCount[kk & 1] = gridDim.x;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    A.scal[9] = static_cast<float>(kk);
-    A.scal[11] = static_cast<float>(1 + (kk & 1));
-    A.scal[10] = 1.0f;
-  }
+  solve_over(A, 1 + (kk & 1), kk);
 }
 
 // The windowed kernels take their window as dynamic LDS: above 64 KB a kernel has to be told - per DEVICE (the attribute belongs to
@@ -554,16 +480,10 @@ static bool window_lds_ok(uint32_t bytes) {
 }
 
 PIES_BOUNDS_REPORT(cg1)
-// workgroups of k_cg1_iter the device holds at once (its continuation's grid barrier needs all of a launch resident)
-uint32_t cg1_iter_resident_blocks(int device, uint32_t windowLdsBytes) {
-  int perCu = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
-  if (windowLdsBytes) {
-    if (!window_lds_ok(windowLdsBytes)) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_cg1_iter<false, true>, kBlock, windowLdsBytes) != hipSuccess) return 0;
-  } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_cg1_iter<false, false>, kBlock, 0) != hipSuccess) return 0;
-  return static_cast<uint32_t>(std::max(0, perCu)) * static_cast<uint32_t>(std::max(0, prop.multiProcessorCount));
+uint32_t cg1_iter_resident_blocks_halved(uint32_t windowLdsBytes) {
+  if (!windowLdsBytes) return resident_blocks_halved(reinterpret_cast<const void*>(k_cg1_iter<false, false>), kBlock);
+  if (!window_lds_ok(windowLdsBytes)) return 0;
+  return resident_blocks_halved(reinterpret_cast<const void*>(k_cg1_iter<false, true>), kBlock, windowLdsBytes);
 }
 
 void launch_pd_solve1(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, int iters, float tol, bool first, bool last, bool fuseRhs,
@@ -578,7 +498,7 @@ void launch_pd_solve1(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, 
   // its partial sums (partCount).
   const dim3 wide(A.npartsI), narrow(A.nparts), block(kBlock);
   // every solve of a substep captures the same number of launches, so the previous solve's last one left its partials here
-  const float* prev = first ? nullptr : A.part1[iters & 1];
+  const float* prev = first ? nullptr : last_solve_partials(A, iters, true);
   const RhsArrays R = rhs_arrays(nd, pd);
   // Which launches of a solve take the windowed matrix where it was built (PIES_PD_WINDOW_KERNELS: 1 the iterations, 2 the first
   // product, 4 the residual; default 3).  The iterations gather three vectors per column and gain from the window by themselves
@@ -617,7 +537,7 @@ void launch_pd_solve1(hipStream_t st, const NodeArrays& nd, const PdArrays& pd, 
     if (hook) hook(hookCtx, 14);
   }
   if (!last) return;
-  A.partB = A.part1[iters & 1];
+  A.partB = last_solve_partials(A, iters, true);
   launch_cg_finish(st, A);
 }
 

@@ -11,17 +11,17 @@ namespace pies {
 constexpr int kBlock = 256;
 
 // ------------------------------------------------------------------------------------------------------
-// Jacobi-preconditioned CG, 3 right-hand sides at once.  Launch shape: kCgBlocks blocks of 256 threads,
-// grid-stride.  Dot products: per-block partials, re-reduced in a fixed order by every block of the
-// consuming kernel (deterministic, no atomics, no extra launch).
-//   partB[b] = { rz[3], rr[3] }  of the current residual     (written by init / update)
-//   partA[b] = { pAp[3] }                                    (written by ap)
-//   scal     = { rz[2][3] ping-pong, bb[3] }                 (written by block 0 of ap)
+// Jacobi-preconditioned CG, 3 right-hand sides at once.  Launch shape: workgroups of 256 threads; a wavefront takes slices of
+// the matrix (64 / lanesPerRow rows), the workgroups of one XCD a contiguous part of them (xcd_sweep).  nparts workgroups where a
+// launch may have to go on behind grid_barrier, npartsI where not (CgArrays).  Dot products: per-workgroup partials, re-reduced
+// in a fixed order by every workgroup of the consuming kernel (deterministic, no atomics, no extra launch).
+//   partI[b]         = { r.z[3], r.r[3], f.f[3] } of the first residual   (k_cg_init, k_cg1_init)
+//   two-launch form:   partA[b] = { p.Ap[3] } (k_cg_ap),  partB0 / partB1[b] = { r.z[3], r.r[3] } (k_cg_update, ping-pong)
+//   one-launch form:   part1[h][b] = { r.t[3], w.t[3], r.r[3] } (k_cg1_first, k_cg1_iter, ping-pong; partCount: how many b)
+//   scal, stats      : the solve's scalars and the solves' statistics, by the names of CgScal and CgStat (pd_kernels.h)
+// What both forms share is stated once, here: the walk over a row's entries (row_entries), the residual of a row (row_residual),
+// a row's contact part (contact_row, contact_rows_of_node), opening a solve and marking it over (solve_open, solve_over).
 // ------------------------------------------------------------------------------------------------------
-struct Red6 {
-  float v[6];
-};
-
 template <int NV> PIES_DEV void block_reduce_partials(const float* __restrict__ part, int stride, uint32_t nparts, float out[NV]) {
   __shared__ float lds[4][NV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -127,20 +127,68 @@ template <int kAhead = 4, class ACC = float, class Fetch> PIES_DEV void contact_
   }
 }
 
-// The slices a wavefront sweeps: blocks that share an XCD (equal blockIdx % 8, see xcd_block) take one contiguous
-// part of the matrix, so the rows a slice gathers from were fetched into that XCD's L2 by its neighbours.
-struct SliceSweep {
+// What a wavefront or a workgroup sweeps, begin / end / step in units of its own: workgroups that share an XCD (equal
+// blockIdx % 8, see xcd_block) take one contiguous segment of the `units`, so what one of them gathers was fetched into that
+// XCD's L2 by its neighbours.  A workgroup takes `each` units per step, this thread the one numbered `mine` among them.
+struct Sweep {
   uint32_t begin, end, step;
 };
-template <int LPR> PIES_DEV SliceSweep slice_sweep(uint32_t n, uint32_t nblocks) {  // nblocks: the launch's SpMV blocks (the first ones)
-  constexpr uint32_t kRows = 64u / LPR;  // rows of a slice
-  const uint32_t nslices = (n + kRows - 1u) / kRows;
+PIES_DEV Sweep xcd_sweep(uint32_t units, uint32_t nblocks, uint32_t each, uint32_t mine) {  // nblocks: the launch's sweeping blocks (the first ones)
   const uint32_t labels = nblocks < 8u ? nblocks : 8u;
   const uint32_t x = blockIdx.x % labels, xb = blockIdx.x / labels;
   const uint32_t nbx = (nblocks - x + labels - 1u) / labels;  // blocks carrying this label
-  const uint32_t segBeg = static_cast<uint32_t>((static_cast<uint64_t>(nslices) * x) / labels);
-  const uint32_t segEnd = static_cast<uint32_t>((static_cast<uint64_t>(nslices) * (x + 1u)) / labels);
-  return {segBeg + xb * (kBlock / 64u) + (threadIdx.x >> 6), segEnd, nbx * (kBlock / 64u)};
+  const uint32_t segBeg = static_cast<uint32_t>((static_cast<uint64_t>(units) * x) / labels);
+  const uint32_t segEnd = static_cast<uint32_t>((static_cast<uint64_t>(units) * (x + 1u)) / labels);
+  return {segBeg + xb * each + mine, segEnd, nbx * each};
+}
+// the slices (64 / LPR rows) a wavefront sweeps
+template <int LPR> PIES_DEV Sweep slice_sweep(uint32_t n, uint32_t nblocks) {
+  constexpr uint32_t kRows = 64u / LPR;
+  return xcd_sweep((n + kRows - 1u) / kRows, nblocks, kBlock / 64u, threadIdx.x >> 6);
+}
+
+// f(value, column) for every stored entry that lane `lane` of slice `sl` holds of row i: the row dictionary (one lane per row
+// only) or the SELL arrays, whose indexing is the same at every lane count
+template <int LPR = 1, class F> PIES_DEV void row_entries(const CgArrays& A, uint32_t sl, uint32_t lane, uint32_t i, F f) {
+  if (LPR == 1 && A.rowStencil) {
+    if (i < A.n) {
+      const uint32_t rs = A.rowStencil[i];
+      const uint32_t b = rs & 0xffffffu, e = b + (rs >> 24);
+#pragma unroll 4
+      for (uint32_t q = b; q < e; ++q) {
+        const int2 pr = A.stencil[q];
+        f(__int_as_float(pr.y), static_cast<uint32_t>(static_cast<int>(i) + pr.x));
+      }
+    }
+  } else {
+    const uint32_t off = A.sliceOff[sl], width = (A.sliceOff[sl + 1] - off) >> 6;
+#pragma unroll 4
+    for (uint32_t kk = 0; kk < width; ++kk) {
+      const uint32_t at = off + (kk << 6) + lane;
+      f(A.val[at], A.col[at]);  // (padding entries: the row itself with value 0)
+    }
+  }
+}
+
+// The residual of row i: r = f - (cdiag x + K x + C x), given the row's sums (K x) = k* and (C x) = c*, then z = D^-1 r and
+// acc9 += {r.z, r.r, f.f}.  In DOUBLE: the products are ~ (m / h^2) |x| ~ 1e6 and cancel against f to a residual five orders
+// smaller; summed in fp32 the row carries a noise of an ulp of 1e6 (0.1: 2e-5 in x per solve, a random walk over the local/global
+// iterations - measured against the oracle's fp64 solve: 2.3 x the deviation of the reference's own fp32 arithmetic, in every
+// variant of the local step and of the CG).  fp64 fused multiply-adds cost these memory-bound launches nothing.
+// C: the type the caller summed the contact part in (k_cg_init: float, k_cg1_init: double - see there).
+template <class C>
+PIES_DEV Vec3f row_residual(const CgArrays& A, uint32_t i, const float4 xi, const float4 fi, double kx, double ky, double kz, C cx, C cy, C cz,
+                            Vec3f& z, float acc9[9]) {
+  const float cd = A.cdiag[i], di = A.dinv[i];
+  const double cdd = static_cast<double>(cd);
+  const float rx = static_cast<float>(static_cast<double>(fi.x) - (fma(cdd, static_cast<double>(xi.x), kx) + static_cast<double>(cx)));
+  const float ry = static_cast<float>(static_cast<double>(fi.y) - (fma(cdd, static_cast<double>(xi.y), ky) + static_cast<double>(cy)));
+  const float rz = static_cast<float>(static_cast<double>(fi.z) - (fma(cdd, static_cast<double>(xi.z), kz) + static_cast<double>(cz)));
+  z = Vec3f{di * rx, di * ry, di * rz};
+  acc9[0] += rx * z.x; acc9[1] += ry * z.y; acc9[2] += rz * z.z;
+  acc9[3] += rx * rx; acc9[4] += ry * ry; acc9[5] += rz * rz;
+  acc9[6] += fi.x * fi.x; acc9[7] += fi.y * fi.y; acc9[8] += fi.z * fi.z;
+  return Vec3f{rx, ry, rz};
 }
 
 // Statistics at the end of a solve (max relative residual over the tick's solves, iterations of the solve): run by one
@@ -149,12 +197,12 @@ template <int LPR> PIES_DEV SliceSweep slice_sweep(uint32_t n, uint32_t nblocks)
 PIES_DEV void solve_statistics(const CgArrays& A, const float* __restrict__ prevPartB) {
   float red[6];
   // a solve that converged before its last captured iteration left its final partials where k_cg_ap found them
-  // (scal[10] = 1, scal[11] = 0: partI, 1 / 2: the ping-pong pair); otherwise the last k_cg_update wrote prevPartB
-  const bool done = A.scal[10] != 0.0f;
-  const int where = static_cast<int>(A.scal[11]);
-  if (done && where == 0 && A.single) {  // (k_cg1_first left the norms in scal[18..20]: partI belongs to the next solve by now)
+  // (solve_over; kScalWhere = 0: partI, 1 / 2: the ping-pong pair); otherwise the last k_cg_update wrote prevPartB
+  const bool done = A.scal[kScalOver] != 0.0f;
+  const int where = static_cast<int>(A.scal[kScalWhere]);
+  if (done && where == 0 && A.single) {  // (k_cg1_first left the norms in kScalFinalRr: partI belongs to the next solve by now)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) red[3 + c] = A.scal[18 + c];
+    for (int c = 0; c < 3; ++c) red[3 + c] = A.scal[kScalFinalRr + c];
   }
   else if (done && where == 0) block_reduce_partials<6>(A.partI, 9, A.nparts, red);
   else if (A.single) {  // one launch per iteration: {r.t, w.t, r.r} per workgroup, the residual norms in the last three
@@ -167,21 +215,41 @@ PIES_DEV void solve_statistics(const CgArrays& A, const float* __restrict__ prev
     bool above = false;  // the very test the CG kernels take their early exit on (all_converged)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float bb = A.scal[6 + c];
+      const float bb = A.scal[kScalBb + c];
       const float rel = bb > 0.f ? red[3 + c] / bb : 0.f;
       worst = fmaxf(worst, rel);
       above = above || !(red[3 + c] <= A.tol2 * bb);
     }
-    A.stats[0] = fmaxf(A.stats[0], worst);  // max over solves of ||r||^2 / ||b||^2
-    A.stats[1] = fmaxf(A.stats[1], A.scal[9]);
-    A.stats[2] += 1.0f;
+    A.stats[kStatWorst] = fmaxf(A.stats[kStatWorst], worst);
+    A.stats[kStatIters] = fmaxf(A.stats[kStatIters], A.scal[kScalIters]);
+    A.stats[kStatSolves] += 1.0f;
     const float ranShort = above ? 1.0f : 0.0f;  // the solve used its whole captured budget and is still above the tolerance
-    A.stats[3] += ranShort;
-    // lifetime counters, as 64-bit integers in the words [4..5] and [6..7] (a float stops counting at 2^24)
-    unsigned long long* life = reinterpret_cast<unsigned long long*>(A.stats + 4);
+    A.stats[kStatShort] += ranShort;
+    unsigned long long* life = reinterpret_cast<unsigned long long*>(A.stats + kStatLife);
     life[0] += above ? 1ull : 0ull;
     life[1] += 1ull;
   }
+}
+
+// The bookkeeping workgroup that opens a solve (one behind the launch's row blocks: inside block 0 it delayed that block's rows
+// by 2-3 us): it closes the previous solve's statistics (prevPart != nullptr: its final partials; its scal[] entries are still
+// intact, this solve's second launch is the first to overwrite them) and clears what the solve's launches tell each other.
+PIES_DEV void solve_open(const CgArrays& A, const float* __restrict__ prevPart) {
+  if (prevPart) solve_statistics(A, prevPart);
+  if (threadIdx.x == 0) {
+    A.scal[kScalOver] = 0.0f;  // this solve is not over yet
+    A.ticket[0] = 0u;          // grid barrier counter of the solve's last launch
+    A.ticket[1] = 0u;          // its abort word
+  }
+}
+
+// The solve is over after `iterations` of them: it converged, or it went on inside its last launch and ended there.  Every later
+// launch of the solve returns on kScalOver; solve_statistics finds the final residual partials by `where` (CgScal).
+PIES_DEV void solve_over(const CgArrays& A, int where, int iterations) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  A.scal[kScalIters] = static_cast<float>(iterations);
+  A.scal[kScalWhere] = static_cast<float>(where);
+  A.scal[kScalOver] = 1.0f;
 }
 
 // Contact part of (K + C) v for the nodes that take part in contacts, one wavefront per node: lane t takes the node's

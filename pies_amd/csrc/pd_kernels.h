@@ -17,6 +17,29 @@ struct Vec3f {
   float x, y, z;
 };
 
+// Words of CgArrays::scal: what the launches of one solve hand to each other (written by thread 0 of workgroup 0).
+enum CgScal : int {
+  kScalGamma = 0,    // [2][3] r.z per column of the two latest iterations, ping-pong by the iteration's parity
+  kScalBb = 6,       // [3] f.f per column: what the residual norms are relative to
+  kScalIters = 9,    // iterations this solve has started
+  kScalOver = 10,    // != 0: the solve is over (converged, or went on inside its last launch): later launches return on it
+  kScalWhere = 11,   // where its final residual partials are: 0 = partI (over at the first look), 1 + h = half h of the ping-pong pair
+  kScalAlpha = 12,   // [2][3] alpha per column, ping-pong like kScalGamma (one-launch form only)
+  kScalFinalRr = 18, // [3] the residual norms of a solve of the one-launch form that was over at its first look
+  kScalWords = 21,
+};
+// Words of CgArrays::stats, read by the host (capi.cpp, substep_graph.cpp).
+enum CgStat : int {
+  kStatWorst = 0,      // over the tick: max over its solves of ||r||^2 / ||b||^2
+  kStatIters = 1,      // over the tick: most iterations a solve used
+  kStatSolves = 2,     // over the tick: solves
+  kStatShort = 3,      // over the tick: solves that ended above the tolerance
+  kStatTickWords = 4,  // (the words above: what the host clears at the start of a tick)
+  kStatLife = 4,       // since the buffers were built, as two 64-bit integers (a float stops counting at 2^24) in the words
+                       // [4..5] and [6..7]: solves that ended above the tolerance, solves
+  kStatWords = 8,
+};
+
 struct CgArrays {
   uint32_t n;
   uint32_t nparts;  // blocks per CG launch (<= kCgBlocks)
@@ -28,7 +51,7 @@ struct CgArrays {
   // K in sliced ELL form: a slice is one wavefront's rows, 64 / lanesPerRow of them; lane L = lanesPerRow * r + q of the slice
   // takes entries q, q + lanesPerRow, ... of its row r, entry step j of the slice sits at sliceOff[s] + 64 j + L, so a
   // wavefront's loads of col/val are contiguous.  Rows are padded to the slice's longest row with (col = the row itself, val = 0).
-  uint32_t lanesPerRow;      // 1 (large systems) or 4
+  uint32_t lanesPerRow;      // 1, 2, 4 or 8 (the row dictionary, the window and the one-launch form: 1 only)
   const uint32_t* sliceOff;  // slices + 1 offsets (in entries)
   const uint32_t* col;
   const float* val;
@@ -73,11 +96,9 @@ struct CgArrays {
   // merged contact rows (tri_lists.hip k_contact_csr): distinct columns of a node's contact row, -w * multiplicity
   const uint32_t *rowStart, *rowLen, *rowCol;
   const float* rowCoef;
-  float* scal;   // rz[2][3], bb[3], iterations, [10] the solve is over (converged, or went on inside its last launch), [11] where
-                 // its final residual partials are
-  uint32_t* ticket;  // [0] grid barrier counter of the solve's last k_cg_update, [1] its abort word (zeroed by k_cg_init)
-  float* stats;  // over the tick: [0] max relative residual^2 of its solves, [1] max iterations, [2] solves, [3] solves that ended
-                 // above the tolerance; since the buffers were built: [4] solves above the tolerance, [5] solves
+  float* scal;   // the solve's scalars (CgScal)
+  uint32_t* ticket;  // [0] grid barrier counter of the solve's last launch, [1] its abort word (zeroed by solve_open)
+  float* stats;  // the solves' statistics (CgStat)
   float tol2;    // squared relative tolerance of the solve whose statistics are being closed
   // ---- one launch per CG iteration (pd_cg1_kernels.hip; Chronopoulos-Gear's single-reduction form) ----
   // the preconditioned vectors t = D^-1 r, c = D^-1 s (s = (K + C) p by recurrence), a = D^-1 w (w = (K + C) t) as 12-byte
@@ -219,9 +240,15 @@ void launch_pd_velocity(hipStream_t st, const NodeArrays& nd, const PdArrays& pd
 // ncCount (node-node contacts per node, PIES_FLAG_PD_NODE_CONTACTS): nor for the nodes with one (launch_nc_friction applies it)
 // npBits (bitmap of the listed node pairs' nodes): nor for those (launch_pd_node_pair_friction applies it)
 
-// workgroups of k_cg_update the device holds at once (0: unknown); the CG kernels' grid stays below it, see grid_barrier
 inline uint32_t window_lds_bytes(const CgArrays& A) { return (A.wLdsSlots + A.wRows) * 16u; }  // the largest window + a chunk's rows of 16 bytes (window_rows)
-uint32_t cg_update_resident_blocks(int device);
-uint32_t cg1_iter_resident_blocks(int device, uint32_t windowLdsBytes = 0);  // windowLdsBytes != 0: the windowed kernel with that much LDS
+// Half of the workgroups of k_cg_update / k_cg1_iter the current device holds at once (0: unknown): the grid of a launch that
+// goes on behind grid_barrier stays below it, and a second solver on the card finds room.
+uint32_t cg_update_resident_blocks_halved();
+uint32_t cg1_iter_resident_blocks_halved(uint32_t windowLdsBytes = 0);  // windowLdsBytes != 0: the windowed kernel with that much LDS
+// where the last solve of a substep left its final residual partials after `iters` captured iterations (every solve of a substep
+// captures as many): what closes its statistics reads them there
+inline float* last_solve_partials(const CgArrays& cg, int iters, bool single) {
+  return single ? cg.part1[iters & 1] : (iters & 1) ? cg.partB1 : cg.partB0;
+}
 
 }  // namespace pies

@@ -692,8 +692,7 @@ void launch_pd_stabilize(hipStream_t st, const NodeArrays& nd, const PdArrays& p
   CgArrays A = pd.cg;
   A.tol2 = tol * tol;
   A.single = single ? 1 : 0;
-  float* pb[2] = {pd.cg.partB, pd.cg.partBnext};
-  A.partB = single ? pd.cg.part1[maxIters & 1] : pb[maxIters & 1];  // where the last solve's final residual partials are (launch_pd_solve / launch_pd_solve1)
+  A.partB = last_solve_partials(A, maxIters, single);
   hipLaunchKernelGGL(k_pd_stabilize, dim3(grid_for(nd.n).x + (closeSolve ? 1u : 0u)), dim3(kBlock), 0, st, nd.pos, pd.statp, pd.nstatic, nd.n, A,
                      closeSolve ? 1 : 0);
 }

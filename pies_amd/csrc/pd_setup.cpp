@@ -373,8 +373,8 @@ int pd_build(pies_solver* s) {
   // k_cg_update's in-kernel continuation synchronises its workgroups with a grid barrier: the grid must fit the device at once
   // (occupancy of the kernel x compute units of THIS device; half of it, so that a second solver on the card leaves room)
   if (s->device >= 0) {
-    const uint32_t resident = std::min(cg_update_resident_blocks(s->device), cg1_iter_resident_blocks(s->device));
-    if (resident >= 2) cg.nparts = std::max(1u, std::min(cg.nparts, resident / 2u));
+    const uint32_t resident = std::min(cg_update_resident_blocks_halved(), cg1_iter_resident_blocks_halved());
+    if (resident >= 1) cg.nparts = std::max(1u, std::min(cg.nparts, resident));
   }
   // The launches of the one-launch-per-iteration form that have no grid barrier (all but a solve's last): as many workgroups as the
   // rows ask for, whatever the device holds at once (1M rows: 1 024 instead of the 512 the continuation's barrier allows - the
@@ -443,8 +443,8 @@ int pd_build(pies_solver* s) {
       // no more workgroups than chunks; the continuation's grid must fit the device beside the window's LDS
       cg.nparts = std::max(1u, std::min(cg.nparts, cg.wChunks));
       cg.npartsI = std::max(cg.nparts, std::min(cg.npartsI, cg.wChunks));
-      const uint32_t resident = cg1_iter_resident_blocks(s->device, window_lds_bytes(cg));
-      if (resident >= 2) cg.nparts = std::max(1u, std::min(cg.nparts, resident / 2u));
+      const uint32_t resident = cg1_iter_resident_blocks_halved(window_lds_bytes(cg));
+      if (resident >= 1) cg.nparts = std::max(1u, std::min(cg.nparts, resident));
     }
   }
   // lanes of k_pd_rhs per node: four for the ~24 per-element records of a node, one when they are a few tile sums
@@ -540,7 +540,7 @@ int pd_build(pies_solver* s) {
   cg.kdiag = d_kdiag;
   cg.single = 0;
   if (int rc = dev_alloc(s, 2, &cg.ticket, true)) return rc;
-  if (int rc = dev_alloc(s, 8, &cg.stats, true)) return rc;
+  if (int rc = dev_alloc(s, kStatWords, &cg.stats, true)) return rc;
   // ---- point-triangle contact pipeline (Solver.cpp:680-875) ------------------------------------------------
   pd.tri = TriArrays{};
   cg.tIncCnt = cg.tIncStart = cg.tInc = nullptr;

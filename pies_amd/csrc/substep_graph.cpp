@@ -626,12 +626,12 @@ int adapt_pcg_budget(pies_solver* s) {
   s->asyncSinceSync = 0;  // (called right after a host synchronisation)
   if (s->opt.solver != PIES_SOLVER_PD || !s->dev.pd.cg.stats || !s->graphExec || s->sceneDirty || under_profiler()) return PIES_OK;
   if (s->pcgPinned) return PIES_OK;  // PIES_PCG_BUDGET: tests of the overflow path keep the captured budget where they put it
-  float st[4] = {0, 0, 0, 0};
+  float st[kStatTickWords] = {0, 0, 0, 0};
   HIP_TRY(s, hipMemcpyAsync(st, s->dev.pd.cg.stats, sizeof(st), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  if (st[2] == 0.0f) return PIES_OK;  // no solve since the statistics were reset
-  const uint32_t used = static_cast<uint32_t>(st[1]);
-  const bool converged = st[0] <= s->pcgTol * s->pcgTol;
+  if (st[kStatSolves] == 0.0f) return PIES_OK;  // no solve since the statistics were reset
+  const uint32_t used = static_cast<uint32_t>(st[kStatIters]);
+  const bool converged = st[kStatWorst] <= s->pcgTol * s->pcgTol;
   uint32_t budget = s->pcgBudget;
   if (!converged && budget < s->pcgMaxIters) {
     // a solve ran out of iterations above the tolerance (new contacts stiffen the system at once): back to the full

@@ -196,13 +196,12 @@ def test_pd_local_step_variants_agree(pies, oracle, tune):
     assert np.abs(res[0] - res[1]).max() <= 0.1 * TOL and np.abs(res[1] - res[2]).max() <= 0.1 * TOL
 
 
-def test_row_dictionary_changes_nothing(pies, tune):
-    """The system matrix as a row dictionary (rows with the same stencil share one copy: column offsets from the row and values)
-    against the SELL arrays: the same entries in the same order, so the same sums - positions equal bit for bit after four
-    ticks, pins, floor contacts and two materials included."""
+def _row_dictionary_changes_nothing(pies, tune, single):
+    """single: the one-launch CG (1, what this scene takes by itself) or PIES_PD_CG_SINGLE=0, the two-launch form"""
     res = []
     for flag in ("0", "1"):
         tune("PIES_PD_ROW_DICT", flag)
+        tune("PIES_PD_CG_SINGLE", None if single else "0")
         g = pies.Solver(pd_options(pies, 6))
         g.create_tet_box(12, 12, 14, translation=(0.0, 0.02, 0.0), w=1.0, volume=True, triangles=True)
         g.create_tet_box(6, 5, 7, translation=(20.0, 0.5, 1.0), w=3.0, volume=True, triangles=True)
@@ -210,7 +209,7 @@ def test_row_dictionary_changes_nothing(pies, tune):
         g.set_prev_positions(g.positions)
         g.add_position(np.arange(0, 35, dtype=np.uint32), 2.0)
         g.tick(4)
-        assert not g.failed
+        assert not g.failed and g.count(pies.PD_CG_SINGLE) == single
         stencils = g.count(pies.ROW_STENCILS)
         assert (stencils > 0) == (flag == "1") and stencils * 8 <= g.count(pies.NODES), stencils
         res.append((g.positions, g.velocities, g.pcg_stats()))
@@ -219,6 +218,19 @@ def test_row_dictionary_changes_nothing(pies, tune):
     # (the statistics are sums over the rows in the order the kernels' threads own them - the windowed matrix that serves a scene
     # without a dictionary since round 5 deals its rows differently -, so the largest residual agrees to rounding, not to the bit)
     assert res[0][2][1:] == res[1][2][1:] and abs(res[0][2][0] - res[1][2][0]) <= 1e-3 * res[1][2][0]
+
+
+def test_row_dictionary_changes_nothing(pies, tune):
+    """The system matrix as a row dictionary (rows with the same stencil share one copy: column offsets from the row and values)
+    against the SELL arrays: the same entries in the same order, so the same sums - positions equal bit for bit after four
+    ticks, pins, floor contacts and two materials included."""
+    _row_dictionary_changes_nothing(pies, tune, 1)
+
+
+def test_row_dictionary_changes_nothing_two_launch(pies, tune):
+    """The same in the two-launch form of the CG (pd_cg_kernels.hip), whose kernels walk the dictionary through the same
+    row_entries as the one-launch form's."""
+    _row_dictionary_changes_nothing(pies, tune, 0)
 
 
 def test_pd_flattened_and_inverted_elements(pies, oracle):
