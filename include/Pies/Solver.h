@@ -661,6 +661,106 @@ public:
     }
     return out;
   }
+  // Extension (pies_apply_ties in pies_hip.h states the rule): ties bind nodes to points on other bodies - a cloth sewn to a body,
+  // skin glued to flesh, two bodies welded at a seam, a seam that rips - under both solvers.  Where an anchor lets the host pull a
+  // body, a tie lets two parts of the scene pull each other: the carrier feels it.  addTies stores a set (an asset like an anchor
+  // set: it survives every scene edit and ends with clear()); applyTies binds the set's nodes for dt seconds in `iterations`
+  // Jacobi iterations - implicit, so any stiffness is stable; stiff seams want more iterations - and returns per group the impulse
+  // the ties gave their tied nodes, its torque about the group's pivot and the number of live ties.  strength 0 releases a group;
+  // breakStretch > 0 breaks the ties found longer, for good (tieState, resetTies).  Call it after tick; getVertices() is
+  // refreshed the way tick refreshes it.
+  struct Tie : pies_tie_t {
+    // the point (u, v) of the triangle (c0, c1, c2) as pies_closest_points reports it: weights ((1 - u) - v, u, v)
+    static Tie onTriangle(uint32_t nodeId, uint32_t c0, uint32_t c1, uint32_t c2, float u, float v, float k, float c = 0.0f,
+                          uint32_t groupIndex = 0) {
+      return _make(nodeId, c0, c1, c2, (1.0f - u) - v, u, v, k, c, groupIndex);
+    }
+    // the point e0 + t (e1 - e0) of an edge
+    static Tie onEdge(uint32_t nodeId, uint32_t e0, uint32_t e1, float t, float k, float c = 0.0f, uint32_t groupIndex = 0) {
+      return _make(nodeId, e0, e1, e0, 1.0f - t, t, 0.0f, k, c, groupIndex);
+    }
+    static Tie toNode(uint32_t nodeId, uint32_t other, float k, float c = 0.0f, uint32_t groupIndex = 0) {
+      return _make(nodeId, other, other, other, 1.0f, 0.0f, 0.0f, k, c, groupIndex);
+    }
+
+   private:
+    static Tie _make(uint32_t a, uint32_t b0, uint32_t b1, uint32_t b2, float w0, float w1, float w2, float k, float c, uint32_t g) {
+      Tie t;
+      t.node = a;
+      t.to[0] = b0; t.to[1] = b1; t.to[2] = b2;
+      t.weight[0] = w0; t.weight[1] = w1; t.weight[2] = w2;
+      t.stiffness = k;
+      t.damping = c;
+      t.group = g;
+      return t;
+    }
+  };
+  struct TieGroup : pies_tie_group_t {
+    explicit TieGroup(const glm::vec3& torquePivot = glm::vec3(0.0f, 0.0f, 0.0f), float s = 1.0f, float breakAt = 0.0f) {
+      for (int k = 0; k < 3; ++k) pivot[k] = torquePivot[k];
+      strength = s;
+      break_stretch = breakAt;
+    }
+    TieGroup& setStrength(float s) {
+      strength = s;
+      return *this;
+    }
+    TieGroup& setBreakStretch(float length) {
+      break_stretch = length;
+      return *this;
+    }
+  };
+  struct TieReaction {
+    glm::vec3 impulse, torque;
+    uint32_t live;
+  };
+  // the set's id; groupCount: how many groups applyTies will be given for it
+  uint32_t addTies(const std::vector<Tie>& ties, uint32_t groupCount = 1) {
+    std::vector<pies_tie_t> records(ties.begin(), ties.end());
+    uint32_t id = 0;
+    _ck(pies_add_ties(_handle(), static_cast<uint32_t>(records.size()), records.data(), groupCount, &id));
+    return id;
+  }
+  // perTie, when given: per tie of the set the impulse it gave its tied node (x, y, z) and its stretch (w)
+  std::vector<TieReaction> applyTies(uint32_t set, const std::vector<TieGroup>& groups, float dt, uint32_t iterations = 4,
+                                     std::vector<glm::vec4>* perTie = nullptr) {
+    const uint32_t n = static_cast<uint32_t>(groups.size());
+    std::vector<pies_tie_group_t> records(groups.begin(), groups.end());
+    std::vector<float> impulse(3 * size_t(n)), torque(3 * size_t(n)), entries;
+    std::vector<uint32_t> live(n);
+    if (perTie) {
+      uint32_t count = 0;
+      _ck(pies_get_ties(_handle(), set, nullptr, 0, &count, nullptr));
+      entries.resize(4 * size_t(count));
+    }
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_apply_ties(_handle(), set, n, records.data(), dt, iterations, impulse.data(), torque.data(), live.data(),
+                        perTie ? entries.data() : nullptr));
+    _refreshPositions();
+    for (uint32_t k = 0; k < _skinVertices.size(); ++k) _refreshSkin(k);
+    if (perTie) {
+      perTie->resize(entries.size() / 4);
+      for (size_t i = 0; i < perTie->size(); ++i)
+        for (int c = 0; c < 4; ++c) (*perTie)[i][c] = entries[4 * i + c];
+    }
+    std::vector<TieReaction> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].impulse = glm::vec3(impulse[3 * k], impulse[3 * k + 1], impulse[3 * k + 2]);
+      out[k].torque = glm::vec3(torque[3 * k], torque[3 * k + 1], torque[3 * k + 2]);
+      out[k].live = live[k];
+    }
+    return out;
+  }
+  // per tie of the set: 1 once it broke
+  std::vector<uint8_t> tieState(uint32_t set) {
+    uint32_t count = 0;
+    _ck(pies_get_ties(_handle(), set, nullptr, 0, &count, nullptr));
+    std::vector<uint8_t> broken(count);
+    _ck(pies_get_tie_state(_handle(), set, broken.data(), count, nullptr));
+    return broken;
+  }
+  // no tie of the set is broken any more
+  void resetTies(uint32_t set) { _ck(pies_reset_ties(_handle(), set)); }
   // Extension (pies_measure_elements / pies_measure_nodes in pies_hip.h state the rules): how the body is doing, evaluated on the
   // device without a read-back.  measureElements answers for elements [first, first + count) of the tetrahedral (PIES_TET) or the
   // volume (PIES_VOLUME) constraints in the order they were added - stretches, det F, volume, |F|^2, the norm of the Green strain

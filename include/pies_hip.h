@@ -783,6 +783,86 @@ int pies_add_anchors(pies_solver_t* s, uint32_t n, const pies_anchor_t* anchors,
 int pies_get_anchors(const pies_solver_t* s, uint32_t set, pies_anchor_t* anchors, uint32_t capacity, uint32_t* n, uint32_t* n_frames);
 int pies_apply_anchors(pies_solver_t* s, uint32_t set, uint32_t n_frames, const pies_anchor_frame_t* frames, float dt,
                        float* out_impulse, float* out_torque, uint32_t* out_live, float* out_anchor);
+/* EXTENSION (the reference joins bodies by distance constraints between nodes only): TIES - nodes bound to points on other bodies by
+ * implicit spring-dampers, solved where HBM holds the nodes, under both solvers: a cloth sewn to a body, skin glued to flesh, two
+ * soft bodies welded at a seam, a tendon ending on a surface, a seam that rips.  Where an anchor lets the host act on a body, a tie
+ * lets two parts of the scene act on each other: the carrier feels the pull.  A device-side edit of node state like
+ * pies_apply_anchors; it hands back what the seam pulls with, per group.
+ * A tie binds node a to the point q = sum weight_j p_bj carried by the nodes b0 b1 b2: a triangle's corners with barycentric
+ * weights, an edge (weight[2] == 0), one node (weights 1, 0, 0).  A slot with weight exactly 0 is read but never written.
+ * SETS ARE ASSETS exactly as anchor sets are: pies_add_ties stores n ties that refer to n_groups groups and returns the set's id (0,
+ * 1, ... per handle); a set survives pies_finalize, scene edits and ticks and ends with pies_clear or pies_destroy.  The library
+ * keeps a host copy - pies_get_ties and pies_get_tie_state read it and need no device - and stages the device copy at the first use
+ * and again after a pies_finalize dropped it; pies_add_ties works on PIES_DEVICE_NONE handles.  Ids are HOST ids of nodes that exist
+ * at the call.  pies_get_ties: ties may be NULL (then capacity is not read), else capacity >= the set's count; n and n_groups may
+ * each be NULL.  pies_get_tie_state: broken (one byte per tie, 1: broken) may be NULL, else capacity >= the set's count; n_broken may
+ * be NULL.  pies_reset_ties: no tie of the set is broken any more.
+ * pies_apply_ties applies one set with the groups of this call (n_groups records, the set's count) acting for dt seconds, in
+ * `iterations` Jacobi iterations.  The outputs may each be NULL: out_impulse, out_torque (n_groups x 3), out_live (n_groups),
+ * out_tie (n x 4, the set's own order).
+ * The rule, in fp32 without fused multiply-adds, with pies_apply_anchors' conventions: dot is x x + y y + z z summed left to right,
+ * cross is pies_raycast's, a vector times a scalar is taken componentwise, every test is the positive form written, so a NaN is
+ * "not live" and "not broken".  Only + - * / sqrtf and comparisons occur.
+ *   COUNTS.  cnt_v is the number of (tie, slot) entries of the SET in which node v takes part: slot a always counts, a `to` slot
+ *   counts iff its weight is not 0.  cnt_v is a function of the set alone - not of liveness, not of the call.  An entry's
+ *   coefficient c is +1 for slot a and -weight_j for `to` slot j.
+ *   PER TIE, ONCE PER CALL.  Tie i has group g, node a and carrier nodes 0 1 2 with weights b0 b1 b2; p is a position with the
+ *   invMass w in .w, from the state the call found; h = dt; counts are converted to float.
+ *     q = (p0 * b0 + p1 * b1) + p2 * b2;   x = p_a - q;   stretch_i = sqrtf(x . x)
+ *     W = w_a * cnt_a + (((b0*b0) * (w0*cnt0) + (b1*b1) * (w1*cnt1)) + (b2*b2) * (w2*cnt2))
+ *     k = stiffness * strength_g;  c = damping * strength_g;  a = c + k * h;  den = 1.0f + (h * a) * W
+ *   A tie becomes BROKEN iff break_stretch_g > 0 and stretch_i > break_stretch_g; it stays broken until pies_reset_ties.  A tie is
+ *   LIVE iff it is not broken (this call's breaks included), strength_g > 0 and W > 0.
+ *   ITERATIONS.  J_i starts at 0.  Iteration t = 1 .. iterations:
+ *     step 1, every live tie, from the velocities iteration t - 1 left (the first: the state the call found):
+ *       uq = (v0 * b0 + v1 * b1) + v2 * b2;   r = v_a - uq
+ *       rho = (x * k + r * a) * h + J_i;   dJ_i = -(rho / den);   J_i = J_i + dJ_i
+ *     step 2, every node v with a live entry and w_v != 0:  v = v + S * w_v, where S sums dJ_i * c over the node's LIVE entries
+ *       from 0.0f in ascending tie index (a node is in a tie's counted slots once).  No other node is written.
+ *   Positions and previous positions are never written.
+ *   This is Jacobi with mass splitting (Tonge et al. 2012) on the implicit Euler system of zero-length spring-dampers between a and
+ *   the carried point: every node's inverse mass is shared out among its cnt_v entries, so the ties of one iteration cannot
+ *   overshoot together and velocities stay bounded for every k dt.  With fewer ties than nodes the iteration converges to the
+ *   coupled solve (1 + h a C M^-1 C^T) J = -h (k x + a r); very stiff seams take hundreds of iterations.
+ *   Equal and opposite impulses through weights that sum to 1 conserve momentum when no tied node is fixed, and angular momentum
+ *   where the tied node sits on its carried point (a sewn seam); a stretched tie pulls along k x + a r, not along x, and turns the
+ *   pair by cross(x_i, J_i).
+ * out_tie[4 i .. 4 i + 3] = J_i and stretch_i; J is 0 for a tie that is not live, the stretch is always given.  out_impulse[g] sums
+ * J_i of group g's ties, out_torque[g] sums cross(q_i - pivot_g, J_i) and out_live[g] counts the live ties, in the anchors' fixed
+ * two-level order over tie indices: tiles of 256 in ascending index from 0.0f (another group's tie adds 0), then the tiles in
+ * ascending index from 0.0f.  J_i is what the seam gave node a; the carrier got -J_i.  The order is a function of the set alone - not
+ * of PIES_FLAG_RENUMBER_NODES -, so two calls agree bit for bit.
+ * With dt == 0 the iterations do not run: nothing is written, every J is 0, and ties still break and are counted live.
+ * Runs on the handle's stream behind whatever ticks and begun frames are queued, finalizes a changed scene first and synchronises
+ * once before it returns; export frames begun earlier, captured graphs and pies_launch_counts are left as they were.  The edit is in
+ * HBM only: the host mirror is marked stale for the velocities; nothing is uploaded.  When some group has break_stretch > 0 the
+ * call reads the broken bytes back into the host copy before it returns, so a later re-staging keeps them.
+ * pies_add_ties: PIES_ERR_INVALID for NULL ties or n == 0, an id >= the node count (in any slot), a non-finite weight, all three
+ * weights 0, stiffness or damping negative or non-finite, group >= n_groups, n_groups == 0 or > PIES_TIE_GROUP_MAX, a tie whose node
+ * and nonzero-weight `to` ids are not pairwise distinct; PIES_ERR_UNSUPPORTED for more than 2^24 ties or more than PIES_TIE_SET_MAX
+ * sets.  pies_apply_ties: PIES_ERR_INVALID for an unknown set, n_groups different from the set's, NULL groups, a non-finite or
+ * negative member of a group (the pivot: non-finite), a negative or non-finite dt, iterations outside 1 .. 64; PIES_ERR_HIP: a
+ * PIES_DEVICE_NONE handle (the arguments are checked first). */
+#define PIES_TIE_SET_MAX 64    /* sets per handle */
+#define PIES_TIE_GROUP_MAX 64  /* groups per set */
+typedef struct pies_tie {      /* 40 bytes */
+  uint32_t node;       /* host id of the tied node a */
+  uint32_t to[3];      /* host ids b0 b1 b2 of the carrier: a triangle's corners, an edge (weight[2] == 0), one node (1, 0, 0) */
+  float weight[3];     /* finite; q = sum weight_j p_bj.  A slot with weight exactly 0 is read but never written */
+  float stiffness, damping; /* k, c: finite, >= 0 */
+  uint32_t group;      /* < n_groups */
+} pies_tie_t;
+typedef struct pies_tie_group { /* 5 words */
+  float pivot[3];      /* point the returned torque refers to */
+  float strength;      /* >= 0, finite: scales k and c; 0 releases the group */
+  float break_stretch; /* >= 0, finite; > 0: a tie of the group found longer than this breaks and stays broken */
+} pies_tie_group_t;
+int pies_add_ties(pies_solver_t* s, uint32_t n, const pies_tie_t* ties, uint32_t n_groups, uint32_t* set);
+int pies_get_ties(const pies_solver_t* s, uint32_t set, pies_tie_t* ties, uint32_t capacity, uint32_t* n, uint32_t* n_groups);
+int pies_apply_ties(pies_solver_t* s, uint32_t set, uint32_t n_groups, const pies_tie_group_t* groups, float dt, uint32_t iterations,
+                    float* out_impulse, float* out_torque, uint32_t* out_live, float* out_tie);
+int pies_get_tie_state(const pies_solver_t* s, uint32_t set, uint8_t* broken, uint32_t capacity, uint32_t* n_broken);
+int pies_reset_ties(pies_solver_t* s, uint32_t set);
 /* EXTENSION (the reference has no such query): STRAIN, VOLUME AND MOMENTUM MEASURES evaluated where HBM holds the body - how the
  * body is doing, without a read-back.  Both calls are READ-ONLY: node state, the host mirror's stale marks, export frames begun
  * earlier, captured graphs and pies_launch_counts are left exactly as they were.  They run on the handle's stream behind whatever

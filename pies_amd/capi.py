@@ -62,6 +62,7 @@ LOAD_MAX = 64  # PIES_LOAD_MAX
 LOAD_TO_END = 0xFFFFFFFF  # pies_surface_load_t.count: to the container's end
 ANCHOR_SET_MAX, ANCHOR_FRAME_MAX = 64, 64  # PIES_ANCHOR_SET_MAX: sets per handle; PIES_ANCHOR_FRAME_MAX: frames per set
 ANCHOR_PIN = 1  # pies_anchor_t.flags: the node sits on the attachment point
+TIE_SET_MAX, TIE_GROUP_MAX = 64, 64  # PIES_TIE_SET_MAX: sets per handle; PIES_TIE_GROUP_MAX: groups per set
 ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
 MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
 IO_HOST_SYNC = 1  # PIES_IO_HOST_SYNC: a device-side read or write returns after its launches have finished
@@ -88,6 +89,7 @@ SYMBOLS = [
     "pies_voxelize_tri_mesh", "pies_add_tri_mesh_volume", "pies_raycast", "pies_closest_points", "pies_collide_props",
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
     "pies_apply_surface_loads", "pies_add_anchors", "pies_get_anchors", "pies_apply_anchors",
+    "pies_add_ties", "pies_get_ties", "pies_apply_ties", "pies_get_tie_state", "pies_reset_ties",
     "pies_measure_elements", "pies_measure_nodes",
     "pies_read_nodes_device", "pies_write_nodes_device", "pies_read_skin_device",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
@@ -362,6 +364,46 @@ class Anchor(C.Structure):
         return cls.make(node, frame_index, local, stiffness, damping, pin)
 
 
+class Tie(C.Structure):
+    """pies_tie_t field for field: node `node` bound to the point sum weight_j p_to[j] by a spring-damper of group `group`."""
+    _fields_ = [
+        ("node", C.c_uint32), ("to", C.c_uint32 * 3), ("weight", C.c_float * 3), ("stiffness", C.c_float), ("damping", C.c_float),
+        ("group", C.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, node, to, weights=(1.0, 0.0, 0.0), stiffness=0.0, damping=0.0, group=0):
+        """to: one, two or three carrier node ids (missing slots repeat the first id with weight 0); weights: as many, or three"""
+        to = [int(i) for i in np.atleast_1d(to)]
+        weights = [float(x) for x in weights][:max(len(to), 1)] if len(to) < 3 else [float(x) for x in weights]
+        t = cls()
+        t.node, t.stiffness, t.damping, t.group = node, stiffness, damping, group
+        t.to[:] = (to + [to[0]] * 3)[:3]
+        t.weight[:] = (weights + [0.0] * 3)[:3]
+        return t
+
+    @classmethod
+    def on_triangle(cls, node, corner_ids, u, v, stiffness=0.0, damping=0.0, group=0):
+        """the tie to the point (u, v) of a triangle as pies_closest_points reports it: weights ((1 - u) - v, u, v) in fp32"""
+        f32 = np.float32
+        u, v = f32(u), f32(v)
+        return cls.make(node, corner_ids, ((f32(1.0) - u) - v, u, v), stiffness, damping, group)
+
+
+class TieGroup(C.Structure):
+    """pies_tie_group_t field for field: what a call gives the ties of one group."""
+    _fields_ = [("pivot", C.c_float * 3), ("strength", C.c_float), ("break_stretch", C.c_float)]
+
+    @classmethod
+    def make(cls, pivot=(0, 0, 0), strength=1.0, break_stretch=0.0):
+        """pivot: the point the returned torque refers to; strength scales stiffness and damping, 0 releases the group;
+        break_stretch > 0: a tie found longer than this breaks and stays broken until reset_ties"""
+        g = cls()
+        g.pivot[:] = [float(x) for x in pivot]
+        g.strength, g.break_stretch = strength, break_stretch
+        return g
+
+
 class ElementMeasure(C.Structure):
     """pies_element_measure_t field for field: one element's record of pies_measure_elements (eight words)."""
     _fields_ = [("s", C.c_float * 3), ("j", C.c_float), ("volume", C.c_float), ("i1", C.c_float), ("green", C.c_float),
@@ -486,6 +528,11 @@ def load():
     sig["pies_add_anchors"] = [vp, u32, C.POINTER(Anchor), u32, pu]
     sig["pies_get_anchors"] = [vp, u32, C.POINTER(Anchor), u32, pu, pu]
     sig["pies_apply_anchors"] = [vp, u32, u32, C.POINTER(AnchorFrame), f32, pf, pf, pu, pf]
+    sig["pies_add_ties"] = [vp, u32, C.POINTER(Tie), u32, pu]
+    sig["pies_get_ties"] = [vp, u32, C.POINTER(Tie), u32, pu, pu]
+    sig["pies_apply_ties"] = [vp, u32, u32, C.POINTER(TieGroup), f32, u32, pf, pf, pu, pf]
+    sig["pies_get_tie_state"] = [vp, u32, C.POINTER(C.c_uint8), u32, pu]
+    sig["pies_reset_ties"] = [vp, u32]
     sig["pies_measure_elements"] =[vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
     sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
     sig["pies_read_nodes_device"] = [vp, C.POINTER(DeviceNodes), u32, vp, u32]
@@ -872,6 +919,58 @@ class Solver:
             args += (None,)
         self._ck(self._L.pies_apply_anchors(self._h, anchor_set, k, arr if k else None, dt, *args))
         return out or None
+
+    def add_ties(self, ties, n_groups=1):
+        """pies_add_ties: stores a set of ties (a sequence of Tie) that refer to n_groups groups.  Returns the set id.  A set is an
+        asset: it survives finalize, scene edits and ticks, and ends with clear() or the handle."""
+        ties = list(ties)
+        arr = (Tie * max(len(ties), 1))(*ties)
+        out = C.c_uint32()
+        self._ck(self._L.pies_add_ties(self._h, len(ties), arr if ties else None, n_groups, C.byref(out)))
+        return out.value
+
+    def get_ties(self, tie_set):
+        """pies_get_ties: (ties: a list of Tie in the set's own order, n_groups), from the library's host copy"""
+        n, groups = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.pies_get_ties(self._h, tie_set, None, 0, C.byref(n), C.byref(groups)))
+        arr = (Tie * max(n.value, 1))()
+        self._ck(self._L.pies_get_ties(self._h, tie_set, arr, n.value, None, None))
+        return [Tie.from_buffer_copy(arr[i]) for i in range(n.value)], groups.value
+
+    def apply_ties(self, tie_set, groups, dt, iterations=4, reaction=True, per_tie=False):
+        """pies_apply_ties: binds the set's nodes to their carriers for dt seconds in `iterations` Jacobi iterations, with the
+        groups (a sequence of TieGroup, as many as the set was added with) of this call, where the device holds the nodes.
+        Returns (impulse float32 (g, 3): what the group's ties gave their nodes a, torque float32 (g, 3) about each group's pivot,
+        live uint32 (g)) with reaction=True, followed by the per-tie array float32 (n, 4): J and the stretch, in the set's own
+        order, with per_tie=True; None when neither is asked for."""
+        groups = list(groups)
+        k = len(groups)
+        arr = (TieGroup * max(k, 1))(*groups)
+        out, args = (), (None, None, None)
+        if reaction:
+            out = (np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.uint32))
+            args = (_pf(out[0]), _pf(out[1]), _pu(out[2]))
+        if per_tie:
+            n = C.c_uint32()
+            self._ck(self._L.pies_get_ties(self._h, tie_set, None, 0, C.byref(n), None))
+            out += (np.zeros((n.value, 4), np.float32),)
+            args += (_pf(out[-1]),)
+        else:
+            args += (None,)
+        self._ck(self._L.pies_apply_ties(self._h, tie_set, k, arr if k else None, dt, iterations, *args))
+        return out or None
+
+    def tie_state(self, tie_set):
+        """pies_get_tie_state: the set's broken bytes (uint8 (n), 1: broken), from the library's host copy"""
+        n = C.c_uint32()
+        self._ck(self._L.pies_get_ties(self._h, tie_set, None, 0, C.byref(n), None))
+        out = np.zeros(n.value, np.uint8)
+        self._ck(self._L.pies_get_tie_state(self._h, tie_set, out.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, None))
+        return out
+
+    def reset_ties(self, tie_set):
+        """pies_reset_ties: no tie of the set is broken any more"""
+        self._ck(self._L.pies_reset_ties(self._h, tie_set))
 
     def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
         """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at

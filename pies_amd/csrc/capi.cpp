@@ -129,6 +129,7 @@ int pies_clear(pies_solver_t* s) {
   s->skinDirty = false;
   s->h_fields.clear();  // (their device copies go with free_device below)
   s->h_anchors.clear();  // (the same)
+  s->h_ties.clear();  // (the same)
   if (s->device != PIES_DEVICE_NONE) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);

@@ -21,6 +21,7 @@
 #include "field_kernels.h"
 #include "measure_kernels.h"
 #include "anchor_kernels.h"
+#include "tie_kernels.h"
 
 namespace pies {
 
@@ -210,6 +211,29 @@ struct AnchorSetDevice {  // nullptr: not staged
   AnchorRecord* records = nullptr;
 };
 
+// A set of ties (pies_add_ties, ties.cpp): the host copy pies_get_ties and pies_get_tie_state read, and what the device copy is
+// staged from - one record per tie in the set's own order with the set's counts, and a CSR from the tied HOST node ids (ascending,
+// once each) to their (tie, coefficient) entries in ascending tie index.  `broken` is the truth between calls: a call that may
+// break ties reads the device's bytes back into it, and a staging (the first use, after free_device, after pies_reset_ties)
+// uploads it.
+struct HostTieSet {
+  std::vector<pies_tie_t> ties;        // the set's own order
+  uint32_t nGroups = 0;
+  std::vector<uint8_t> broken;         // per tie
+  bool brokenChanged = false;          // pies_reset_ties since the device copy's bytes were written
+  std::vector<TieRecord> records;      // (tie_kernels.h)
+  std::vector<uint32_t> nodes;         // tied host node ids, ascending, once each
+  std::vector<uint32_t> offsets;       // nodes + 1
+  std::vector<TieEntry> entries;
+};
+struct TieSetDevice {  // nullptr: not staged
+  TieRecord* records = nullptr;
+  uint8_t* broken = nullptr;
+  uint32_t* nodes = nullptr;
+  uint32_t* offsets = nullptr;
+  TieEntry* entries = nullptr;
+};
+
 // Device buffers of pies_raycast.  free_device drops them, so the triangle list never outlives the scene or the node numbering
 // it was built from; every buffer grows on demand and a handle that never casts a ray holds none.
 struct RayBuffers {
@@ -270,6 +294,15 @@ struct RayBuffers {
   float4* anchorImpulse = nullptr;              // per anchor: j, stretch
   float4* anchorTorque = nullptr;               // per anchor: cross(t - pivot, j), the frame's index | the live bit
   size_t anchorOutCap = 0;                      // anchors both hold
+  // pies_apply_ties (ties.cpp) shares propOut, propTileMask and propTileSums too - tiles of 256 TIE indices -; the device copies
+  // of its sets, the groups of a call and, per tie, what the iterations pass on (tie_kernels.h: TiePass)
+  TieSetDevice tieSets[PIES_TIE_SET_MAX] = {};
+  pies_tie_group_t* tieGroups = nullptr;        // PIES_TIE_GROUP_MAX records
+  float4* tieDelta = nullptr;
+  float4* tieImpulse = nullptr;
+  float4* tieTorque = nullptr;
+  float4* tieScratch = nullptr;                 // 2 per tie
+  size_t tieCap = 0;                            // ties all four hold
   // pies_measure_elements / pies_measure_nodes (measure.cpp) have their buffers to themselves.  Per container (0: PIES_TET, 1:
   // PIES_VOLUME) the elements staged in HOST order with node ids in DEVICE numbering, upload_tets' layout - the scene's own
   // tetrahedral records are in plan order and PBD stages no volume records
@@ -387,6 +420,7 @@ struct pies_solver {
   std::vector<pies::HostSkin> h_skins;  // extension: embedded surface meshes (pies_add_skin)
   std::vector<pies::HostField> h_fields;  // extension: signed distance fields (pies_add_field*); assets: only pies_clear drops them
   std::vector<pies::HostAnchorSet> h_anchors;  // extension: anchor sets (pies_add_anchors); assets like the fields
+  std::vector<pies::HostTieSet> h_ties;        // extension: tie sets (pies_add_ties); assets like the anchor sets
   uint32_t constraintId = 0;
 
   bool sceneDirty = true;    // topology/rest data changed: rebuild plans + upload everything
