@@ -761,6 +761,80 @@ public:
   }
   // no tie of the set is broken any more
   void resetTies(uint32_t set) { _ck(pies_reset_ties(_handle(), set)); }
+  // Extension (pies_drive_actuators in pies_hip.h states the rule): actuators let the body move itself - a muscle, a tendon, a
+  // bellows, a hinge that folds: distance and bend constraints whose rest length or rest angle follows an activation, written where
+  // the device holds the rest records, without the rebuild a rest edit costs otherwise.  addActuators stores a set (an asset like
+  // an anchor set: it survives every scene edit and ends with clear()); driveActuators writes the rests from one activation per
+  // channel and returns per channel the measured values and the written rests of its live actuators added, and their count.  Call
+  // it before tick; node state is not touched.
+  struct Actuator : pies_actuator_t {
+    // the rest becomes base (1 + gain u), clamped to [lo, hi]; base is the constraint's rest when the set is added
+    static Actuator scaled(int containerType, uint32_t constraintIndex, uint32_t channelIndex, float g, float lowest, float highest) {
+      return _make(containerType, constraintIndex, channelIndex, g, lowest, highest, 0u);
+    }
+    // the rest becomes base + gain u, clamped to [lo, hi]
+    static Actuator offset(int containerType, uint32_t constraintIndex, uint32_t channelIndex, float g, float lowest, float highest) {
+      return _make(containerType, constraintIndex, channelIndex, g, lowest, highest, PIES_ACTUATOR_OFFSET);
+    }
+
+   private:
+    static Actuator _make(int t, uint32_t i, uint32_t c, float g, float l, float h, uint32_t f) {
+      Actuator a;
+      a.type = t;
+      a.index = i;
+      a.channel = c;
+      a.gain = g;
+      a.lo = l;
+      a.hi = h;
+      a.base = 0.0f;
+      a.flags = f;
+      return a;
+    }
+  };
+  struct ActuatorChannel {
+    float value, rest;  // sums over the channel's live actuators: measured lengths / dihedral cosines, written rests
+    uint32_t live;
+  };
+  // the set's id; channelCount: how many activations driveActuators will be given for it
+  uint32_t addActuators(const std::vector<Actuator>& actuators, uint32_t channelCount = 1) {
+    std::vector<pies_actuator_t> records(actuators.begin(), actuators.end());
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);  // (the constraints the records name)
+    uint32_t id = 0;
+    _ck(pies_add_actuators(_handle(), static_cast<uint32_t>(records.size()), records.data(), channelCount, &id));
+    return id;
+  }
+  // the set as the library holds it, `base` filled in
+  std::vector<pies_actuator_t> actuators(uint32_t set, uint32_t* channelCount = nullptr) {
+    uint32_t count = 0;
+    _ck(pies_get_actuators(_handle(), set, nullptr, 0, &count, channelCount));
+    std::vector<pies_actuator_t> out(count);
+    if (count) _ck(pies_get_actuators(_handle(), set, out.data(), count, nullptr, nullptr));
+    return out;
+  }
+  struct ActuatorEntry {
+    float rest, value;  // the rest the actuator's constraint holds after the call; its measured length / dihedral cosine
+  };
+  // perActuator, when given: one entry per actuator of the set, in the set's own order
+  std::vector<ActuatorChannel> driveActuators(uint32_t set, const std::vector<float>& activation,
+                                              std::vector<ActuatorEntry>* perActuator = nullptr) {
+    const uint32_t n = static_cast<uint32_t>(activation.size());
+    std::vector<float> sums(2 * size_t(n)), entries;
+    std::vector<uint32_t> live(n);
+    if (perActuator) {
+      uint32_t count = 0;
+      _ck(pies_get_actuators(_handle(), set, nullptr, 0, &count, nullptr));
+      entries.resize(2 * size_t(count));
+    }
+    _pushState(_pushed[4] >= 0 ? static_cast<SolverName>(_pushed[4]) : _options.solver);
+    _ck(pies_drive_actuators(_handle(), set, n, activation.data(), sums.data(), live.data(), perActuator ? entries.data() : nullptr));
+    if (perActuator) {
+      perActuator->resize(entries.size() / 2);
+      for (size_t i = 0; i < perActuator->size(); ++i) (*perActuator)[i] = ActuatorEntry{entries[2 * i], entries[2 * i + 1]};
+    }
+    std::vector<ActuatorChannel> out(n);
+    for (size_t k = 0; k < n; ++k) out[k] = ActuatorChannel{sums[2 * k], sums[2 * k + 1], live[k]};
+    return out;
+  }
   // Extension (pies_measure_elements / pies_measure_nodes in pies_hip.h state the rules): how the body is doing, evaluated on the
   // device without a read-back.  measureElements answers for elements [first, first + count) of the tetrahedral (PIES_TET) or the
   // volume (PIES_VOLUME) constraints in the order they were added - stretches, det F, volume, |F|^2, the norm of the Green strain

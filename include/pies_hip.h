@@ -863,6 +863,79 @@ int pies_apply_ties(pies_solver_t* s, uint32_t set, uint32_t n_groups, const pie
                     float* out_impulse, float* out_torque, uint32_t* out_live, float* out_tie);
 int pies_get_tie_state(const pies_solver_t* s, uint32_t set, uint8_t* broken, uint32_t capacity, uint32_t* n_broken);
 int pies_reset_ties(pies_solver_t* s, uint32_t set);
+/* EXTENSION (the reference fixes a constraint's rest datum at creation): ACTUATORS - distance and bend constraints whose rest length
+ * or rest angle the host drives every tick, written where HBM holds the rest records, under every schedule and both solvers: a
+ * muscle, a tendon, a pneumatic bellows, a winch cable, a hinge that folds.  pies_set_rest does the same edit through a full
+ * rebuild; a drive call rebuilds nothing: the rest datum of a distance or bend constraint lives in one word of one record that
+ * every kernel reads through a pointer, and enters no plan, colouring, dictionary or system matrix.
+ * Tetrahedral and volume rest data do and stay with pies_set_rest.
+ * SETS ARE ASSETS exactly as anchor sets are: pies_add_actuators stores n actuators that refer to n_channels activation channels
+ * and returns the set's id (0, 1, ... per handle); a set survives pies_finalize, scene edits and ticks and ends with pies_clear or
+ * pies_destroy.  The library keeps a host copy - pies_get_actuators reads it and needs no device - and stages the device copy at the
+ * first drive and again after a pies_finalize dropped it, with every index translated to the constraint's slot in the order the
+ * device holds (the inverse of what pies_get_order returns); pies_add_actuators works on PIES_DEVICE_NONE handles.  index is the
+ * constraint's index in its container in HOST order (pies_get_ids / pies_get_rest order), of a constraint that exists at the call;
+ * constraints appended later do not disturb a set.  pies_add_actuators writes `base` of the stored copy: the constraint's rest datum
+ * at that moment (what pies_get_rest returns then; the caller's value is ignored).  No two actuators of one set name the same
+ * constraint; when two sets drive one constraint the later call wins.  pies_get_actuators: actuators may be NULL (then capacity is
+ * not read), else capacity >= the set's count; n and n_channels may each be NULL.
+ * pies_drive_actuators drives one set with the activations of this call (n_channels floats, the set's count).  The outputs may each
+ * be NULL: out_sums (n_channels x 2), out_live (n_channels), out_actuator (n x 2, the set's own order).
+ * The rule, in fp32 without fused multiply-adds, with pies_apply_anchors' conventions: dot products summed left to right as
+ * x x + y y + z z, cross(a, b) = (a.y b.z - b.y a.z, a.z b.x - b.z a.x, a.x b.y - b.x a.y) as in pies_raycast, a + b * t is the
+ * product rounded, then the sum, a vector divided by a scalar is taken componentwise, every test is the positive form written.  Only
+ * + - * / sqrtf fminf fmaxf and comparisons occur.  For actuator i with u = activation[channel_i]:
+ *   r_i = base_i * (1.0f + gain_i * u)          with PIES_ACTUATOR_OFFSET:  r_i = base_i + gain_i * u
+ *   r_i = fminf(fmaxf(r_i, lo_i), hi_i)
+ * The actuator is LIVE iff u - u == 0.0f (u is finite: inf - inf and NaN - NaN are NaN, which equals nothing).  A live actuator
+ * replaces the rest datum of its constraint by r_i in every device array that holds it; an actuator that is not live writes nothing
+ * and its constraint keeps the rest it has.
+ *   value_i, measured on the state the call found, from the constraint's own node ids a b (c d); p is a position:
+ *     DISTANCE: d = p_a - p_b;  value_i = sqrtf(d . d)
+ *     BEND:     p2 = p_b - p_a, p3 = p_c - p_a, p4 = p_d - p_a;  e = cross(p2, p3), f = cross(p2, p4);
+ *               n1 = e / sqrtf(e . e), n2 = f / sqrtf(f . f);  value_i = n1 . n2
+ *               - the cosine of the dihedral angle exactly as the bend projection forms it before its acos (Constraints.cpp:321-339).
+ * out_actuator[2 i] = r_i (of an actuator that is not live: the rest its constraint keeps), out_actuator[2 i + 1] = value_i.
+ * out_sums[2 c] sums value_i over the LIVE actuators of channel c and out_sums[2 c + 1] sums r_i over the same actuators, in a fixed
+ * two-level order: per tile of 256 consecutive actuator indices in ascending index from 0.0f (another channel's actuator, and one
+ * that is not live, adds 0), then the tiles in ascending index from 0.0f.  out_live[c] counts the live actuators of channel c.
+ * Nothing is summed with atomics and the order is a function of the set alone - not of a kernel variant, a schedule or
+ * PIES_FLAG_RENUMBER_NODES -, so two calls agree bit for bit.  Node state is not written.
+ * A drive runs on the handle's stream behind whatever ticks and begun frames are queued, finalizes a changed scene first, and is one
+ * launch plus the fold of the tile sums; captured graphs, pies_launch_counts and export frames begun earlier are left as they were
+ * and nothing enters the captured substep.  pies_drive_actuators synchronises once before it returns.
+ * pies_drive_actuators_device takes activation and the outputs as DEVICE pointers (floats and uint32 words, 4-byte aligned, device
+ * memory of the handle's device) and follows pies_write_nodes_device's stream rule word for word: the solver's stream waits for what
+ * `stream` has queued, `stream` waits for the call's launches, no host synchronisation unless flags has PIES_IO_HOST_SYNC, and
+ * PIES_ERR_STATE when `stream` is capturing.  It cannot check the activations: the LIVE rule covers them.
+ * THE HOST MIRROR STAYS TRUTHFUL.  The edit is in HBM only: the mirror's rest lengths and angles are marked stale and copied back
+ * through the slot map when someone needs them - pies_get_rest, any scene edit, any rebuild -, so pies_get_rest returns the driven
+ * values, a later full rebuild (pies_set_schedule, pies_set_solver, an appended body, a flag that rebuilds) keeps them, and a
+ * pies_set_rest made after a drive overrides it for its range.
+ * pies_add_actuators: PIES_ERR_INVALID for NULL actuators or n == 0, a type other than PIES_DISTANCE / PIES_BEND, an index beyond its
+ * container, n_channels == 0 or > PIES_ACTUATOR_CHANNEL_MAX, channel >= n_channels, a non-finite gain, lo or hi, lo > hi, a
+ * negative lo on DISTANCE, an unknown flag, a constraint listed twice; PIES_ERR_UNSUPPORTED for more than 2^24 actuators or more
+ * than PIES_ACTUATOR_SET_MAX sets.  The drive calls: PIES_ERR_INVALID for an unknown set, n_channels different from the set's, a
+ * NULL activation, (host-pointer form) a non-finite activation, (device form) a pointer that fails pies_write_nodes_device's
+ * checks; PIES_ERR_HIP: a PIES_DEVICE_NONE handle (the arguments are checked first). */
+#define PIES_ACTUATOR_SET_MAX 64     /* sets per handle */
+#define PIES_ACTUATOR_CHANNEL_MAX 64 /* activation channels per set */
+enum { PIES_ACTUATOR_OFFSET = 1 };   /* flags: r = base + gain u instead of base (1 + gain u) */
+typedef struct pies_actuator {       /* 32 bytes */
+  int32_t type;      /* PIES_DISTANCE or PIES_BEND */
+  uint32_t index;    /* the constraint's index in its container, host order (pies_get_ids / pies_get_rest order) */
+  uint32_t channel;  /* index into the activations of a drive call */
+  float gain;        /* finite */
+  float lo, hi;      /* the written rest is clamped to [lo, hi]; lo <= hi, finite; DISTANCE: lo >= 0 */
+  float base;        /* written by the library at pies_add_actuators: the constraint's rest datum at that moment */
+  uint32_t flags;    /* 0 or PIES_ACTUATOR_OFFSET */
+} pies_actuator_t;
+int pies_add_actuators(pies_solver_t* s, uint32_t n, const pies_actuator_t* actuators, uint32_t n_channels, uint32_t* set);
+int pies_get_actuators(const pies_solver_t* s, uint32_t set, pies_actuator_t* actuators, uint32_t capacity, uint32_t* n, uint32_t* n_channels);
+int pies_drive_actuators(pies_solver_t* s, uint32_t set, uint32_t n_channels, const float* activation, float* out_sums,
+                         uint32_t* out_live, float* out_actuator);
+int pies_drive_actuators_device(pies_solver_t* s, uint32_t set, uint32_t n_channels, const void* activation, void* out_sums,
+                                void* out_live, void* out_actuator, void* stream, uint32_t flags);
 /* EXTENSION (the reference has no such query): STRAIN, VOLUME AND MOMENTUM MEASURES evaluated where HBM holds the body - how the
  * body is doing, without a read-back.  Both calls are READ-ONLY: node state, the host mirror's stale marks, export frames begun
  * earlier, captured graphs and pies_launch_counts are left exactly as they were.  They run on the handle's stream behind whatever

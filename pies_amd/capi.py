@@ -63,6 +63,8 @@ LOAD_TO_END = 0xFFFFFFFF  # pies_surface_load_t.count: to the container's end
 ANCHOR_SET_MAX, ANCHOR_FRAME_MAX = 64, 64  # PIES_ANCHOR_SET_MAX: sets per handle; PIES_ANCHOR_FRAME_MAX: frames per set
 ANCHOR_PIN = 1  # pies_anchor_t.flags: the node sits on the attachment point
 TIE_SET_MAX, TIE_GROUP_MAX = 64, 64  # PIES_TIE_SET_MAX: sets per handle; PIES_TIE_GROUP_MAX: groups per set
+ACTUATOR_SET_MAX, ACTUATOR_CHANNEL_MAX = 64, 64  # PIES_ACTUATOR_SET_MAX: sets per handle; PIES_ACTUATOR_CHANNEL_MAX: channels per set
+ACTUATOR_OFFSET = 1  # pies_actuator_t.flags: r = base + gain u instead of base (1 + gain u)
 ELEMENT_INVERTED, ELEMENT_OVER, ELEMENT_UNDER, ELEMENT_NONFINITE = 1, 2, 4, 8  # pies_element_measure_t.flags
 MEASURE_RANGE_MAX = 64  # PIES_MEASURE_RANGE_MAX: ranges per pies_measure_nodes call
 IO_HOST_SYNC = 1  # PIES_IO_HOST_SYNC: a device-side read or write returns after its launches have finished
@@ -90,6 +92,7 @@ SYMBOLS = [
     "pies_add_field", "pies_add_field_tri_mesh", "pies_get_field", "pies_collide_field_props", "pies_apply_forces",
     "pies_apply_surface_loads", "pies_add_anchors", "pies_get_anchors", "pies_apply_anchors",
     "pies_add_ties", "pies_get_ties", "pies_apply_ties", "pies_get_tie_state", "pies_reset_ties",
+    "pies_add_actuators", "pies_get_actuators", "pies_drive_actuators", "pies_drive_actuators_device",
     "pies_measure_elements", "pies_measure_nodes",
     "pies_read_nodes_device", "pies_write_nodes_device", "pies_read_skin_device",
     "pies_layer_rest_pack", "pies_layer_rest_unpack", "pies_layer_rest_usable",
@@ -364,6 +367,23 @@ class Anchor(C.Structure):
         return cls.make(node, frame_index, local, stiffness, damping, pin)
 
 
+class Actuator(C.Structure):
+    """pies_actuator_t field for field: constraint `index` of the DISTANCE or BEND container (host order) whose rest datum follows
+    activation channel `channel`: base (1 + gain u), or base + gain u with offset=True, clamped to [lo, hi].  `base` is written
+    by the library when the set is added."""
+    _fields_ = [
+        ("type", C.c_int32), ("index", C.c_uint32), ("channel", C.c_uint32), ("gain", C.c_float), ("lo", C.c_float), ("hi", C.c_float),
+        ("base", C.c_float), ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, ctype, index, channel=0, gain=1.0, lo=0.0, hi=3.0e38, offset=False):
+        a = cls()
+        a.type, a.index, a.channel, a.gain, a.lo, a.hi, a.base = ctype, index, channel, gain, lo, hi, 0.0
+        a.flags = ACTUATOR_OFFSET if offset else 0
+        return a
+
+
 class Tie(C.Structure):
     """pies_tie_t field for field: node `node` bound to the point sum weight_j p_to[j] by a spring-damper of group `group`."""
     _fields_ = [
@@ -533,6 +553,10 @@ def load():
     sig["pies_apply_ties"] = [vp, u32, u32, C.POINTER(TieGroup), f32, u32, pf, pf, pu, pf]
     sig["pies_get_tie_state"] = [vp, u32, C.POINTER(C.c_uint8), u32, pu]
     sig["pies_reset_ties"] = [vp, u32]
+    sig["pies_add_actuators"] = [vp, u32, C.POINTER(Actuator), u32, pu]
+    sig["pies_get_actuators"] = [vp, u32, C.POINTER(Actuator), u32, pu, pu]
+    sig["pies_drive_actuators"] = [vp, u32, u32, pf, pf, pu, pf]
+    sig["pies_drive_actuators_device"] = [vp, u32, u32, vp, vp, vp, vp, vp, u32]
     sig["pies_measure_elements"] =[vp, i32, u32, u32, C.POINTER(ElementMeasure), C.POINTER(ElementSummary)]
     sig["pies_measure_nodes"] = [vp, u32, pu, pf, C.POINTER(NodeSums)]
     sig["pies_read_nodes_device"] = [vp, C.POINTER(DeviceNodes), u32, vp, u32]
@@ -971,6 +995,56 @@ class Solver:
     def reset_ties(self, tie_set):
         """pies_reset_ties: no tie of the set is broken any more"""
         self._ck(self._L.pies_reset_ties(self._h, tie_set))
+
+    def add_actuators(self, actuators, n_channels=1):
+        """pies_add_actuators: stores a set of actuators (a sequence of Actuator) that refer to n_channels activation channels.
+        Returns the set id.  A set is an asset: it survives finalize, scene edits and ticks, and ends with clear() or the handle."""
+        if isinstance(actuators, C.Array):  # (a ctypes array of Actuator as it is: a large set built elsewhere)
+            arr = actuators
+        else:
+            actuators = list(actuators)
+            arr = (Actuator * max(len(actuators), 1))(*actuators)
+        out = C.c_uint32()
+        self._ck(self._L.pies_add_actuators(self._h, len(actuators), arr if len(actuators) else None, n_channels, C.byref(out)))
+        return out.value
+
+    def get_actuators(self, actuator_set):
+        """pies_get_actuators: (actuators: a list of Actuator in the set's own order with `base` filled in, n_channels), from the
+        library's host copy"""
+        n, channels = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.pies_get_actuators(self._h, actuator_set, None, 0, C.byref(n), C.byref(channels)))
+        arr = (Actuator * max(n.value, 1))()
+        self._ck(self._L.pies_get_actuators(self._h, actuator_set, arr, n.value, None, None))
+        return [Actuator.from_buffer_copy(arr[i]) for i in range(n.value)], channels.value
+
+    def drive_actuators(self, actuator_set, activation, sums=True, per_actuator=False):
+        """pies_drive_actuators: writes the rest lengths and angles of the set's constraints from the activations (one float per
+        channel of the set) where the device holds the rest records - no rebuild.  Returns (sums float32 (c, 2): per channel the
+        live actuators' measured values and written rests added, live uint32 (c)) with sums=True, followed by the per-actuator
+        array float32 (n, 2): the rest the constraint holds after the call and its measured value (a length, or the cosine of
+        the dihedral angle), in the set's own order, with per_actuator=True; None when neither is asked for."""
+        u = np.ascontiguousarray(activation, np.float32).reshape(-1)
+        k = len(u)
+        out, args = (), (None, None)
+        if sums:
+            out = (np.zeros((k, 2), np.float32), np.zeros(k, np.uint32))
+            args = (_pf(out[0]), _pu(out[1]))
+        if per_actuator:
+            n = C.c_uint32()
+            self._ck(self._L.pies_get_actuators(self._h, actuator_set, None, 0, C.byref(n), None))
+            out += (np.zeros((n.value, 2), np.float32),)
+            args += (_pf(out[-1]),)
+        else:
+            args += (None,)
+        self._ck(self._L.pies_drive_actuators(self._h, actuator_set, k, _pf(u) if k else None, *args))
+        return out or None
+
+    def drive_actuators_device(self, actuator_set, n_channels, activation, sums=0, live=0, per_actuator=0, stream=0, flags=0):
+        """pies_drive_actuators_device: the same with the activations and the outputs at device addresses (integers; 0: not wanted),
+        ordered against `stream` (0: the default stream) by events; no host synchronisation unless flags has IO_HOST_SYNC"""
+        self._ck(self._L.pies_drive_actuators_device(self._h, actuator_set, n_channels, C.c_void_p(activation or None), C.c_void_p(sums or None),
+                                                     C.c_void_p(live or None), C.c_void_p(per_actuator or None), C.c_void_p(stream or None),
+                                                     flags))
 
     def measure_elements(self, ctype, first=0, n=None, records=True, summary=True):
         """pies_measure_elements: elements [first, first + n) of the TET or VOLUME container (n None: to the container's end) at

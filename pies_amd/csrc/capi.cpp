@@ -130,6 +130,8 @@ int pies_clear(pies_solver_t* s) {
   s->h_fields.clear();  // (their device copies go with free_device below)
   s->h_anchors.clear();  // (the same)
   s->h_ties.clear();  // (the same)
+  s->h_actuators.clear();  // (the same)
+  s->restStale = 0;  // (the constraints whose rest data HBM held newer go too)
   if (s->device != PIES_DEVICE_NONE) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
@@ -344,6 +346,7 @@ int pies_finalize(pies_solver_t* s) {
   s->collideFast = true;
   if (collide) { uint64_t e; collision_grid_bound(s, e, s->collideFast); }
   if (int rc = download_nodes(s)) return rc;
+  if (int rc = download_rest(s)) return rc;  // (driven rest lengths and angles survive the rebuild)
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   free_device(s);
 
@@ -908,6 +911,8 @@ int pies_get_group(const pies_solver_t* s, int type, uint32_t index, uint32_t* i
 
 int pies_get_rest(const pies_solver_t* s, int type, float* out, uint32_t capacity) {
   if (!s || !out) return PIES_ERR_INVALID;
+  if (s->restStale)  // a pies_drive_actuators since the mirror held the truth: the driven values are what the scene has
+    if (int rc = download_rest(const_cast<pies_solver*>(s))) return rc;
   size_t k = 0;
   auto put = [&](float v) { if (k < capacity) out[k] = v; ++k; };
   switch (type) {

@@ -36,6 +36,7 @@ bool tet_volume_pairs(const pies_solver* s);
 void free_device(pies_solver* s);  // the captured graph, the skins' records, every allocation of s->dev; s->dev starts over
 int upload_nodes(pies_solver* s);
 int download_nodes(pies_solver* s, uint32_t mask = 7u);
+int download_rest(pies_solver* s);     // host mirror <- HBM: the rest lengths and angles a pies_drive_actuators left stale
 int scene_sync_host(pies_solver* s);  // brings the host mirror up to date before a scene edit
 int build_plans(pies_solver* s, int sched);
 // the steps of pies_finalize, in its order; each returns a PIES_* code
@@ -51,6 +52,14 @@ int nc_build(pies_solver* s);             // PIES_FLAG_PD_NODE_CONTACTS
 int pd_rest_dictionary(pies_solver* s);   // PD: volume records and the rest dictionary (before pd_build)
 int alloc_pd_snapshots(pies_solver* s);   // PD: the retry snapshots (after pd_build)
 void pcg_ceiling_rule(pies_solver* s);
+
+// ---- node_io.cpp : the stream rule of the device-pointer entry points (pies_write_nodes_device states it) ----
+// `bytes` at p are device memory of the handle's device (p == nullptr: nothing to check)
+int check_device_range(pies_solver* s, const char* call, const void* p, size_t bytes);
+// The caller's stream must not be capturing (PIES_ERR_STATE); then the solver's stream waits for what the caller has queued so far.
+int io_begin(pies_solver* s, const char* call, hipStream_t caller);
+// ... and the caller's stream waits for the call's launches; PIES_IO_HOST_SYNC: the host too
+int io_end(pies_solver* s, hipStream_t caller, uint32_t flags);
 
 }  // namespace pies
 

@@ -96,9 +96,36 @@ int download_nodes(pies_solver* s, uint32_t mask) {
   return PIES_OK;
 }
 
+// Host mirror <- HBM: the rest lengths and rest angles, when pies_drive_actuators (actuators.cpp) has written them since the mirror
+// held the truth.  Slot k of the device's records is constraint plan.order[k] - the plan the records were uploaded by, which
+// only pies_finalize replaces, after it has called this.  The rule of the drive is not restated here: the words are copied.
+int download_rest(pies_solver* s) {
+  if (!s->restStale) return PIES_OK;
+  if (s->device == PIES_DEVICE_NONE) { s->restStale = 0; return PIES_OK; }
+  HIP_TRY(s, hipSetDevice(s->device));
+  std::vector<float2> words;
+  for (int k = 0; k < 2; ++k) {
+    if (!(s->restStale & (1u << k))) continue;
+    const float2* src = k == 0 ? s->dev.d_dc_rw : s->dev.d_bc_aw;
+    const std::vector<uint32_t>& order = s->plan[k == 0 ? PIES_DISTANCE : PIES_BEND].order;
+    if (src && !order.empty()) {
+      words.resize(order.size());
+      HIP_TRY(s, hipMemcpyAsync(words.data(), src, words.size() * sizeof(float2), hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(s, hipStreamSynchronize(s->stream));
+      for (size_t q = 0; q < order.size(); ++q) {
+        if (k == 0 && order[q] < s->h_distance.size()) s->h_distance[order[q]].target = words[q].x;
+        if (k == 1 && order[q] < s->h_bend.size()) s->h_bend[order[q]].angle = words[q].x;
+      }
+    }
+    s->restStale &= ~(1u << k);
+  }
+  return PIES_OK;
+}
+
 int scene_sync_host(pies_solver* s) {
   if (s->device == PIES_DEVICE_NONE) return PIES_OK;
   if (hipSetDevice(s->device) != hipSuccess) return fail(s, PIES_ERR_HIP, "hipSetDevice failed");
+  if (int rc = download_rest(s)) return rc;
   return download_nodes(s);
 }
 

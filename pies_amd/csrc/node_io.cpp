@@ -13,20 +13,7 @@
 
 using namespace pies;
 
-namespace {
-
-// the argument checks that need no device; PIES_OK or the entry point's answer
-int check_nodes(pies_solver* s, const char* call, const pies_device_nodes_t* a, bool write) {
-  const auto who = [&] { return std::string(call) + ": "; };
-  const void* p[5] = {a->position, a->prev_position, a->velocity, a->radius, a->inv_mass};
-  if (!p[0] && !p[1] && !p[2] && !p[3] && !p[4]) return fail(s, PIES_ERR_INVALID, who() + "every array pointer is NULL");
-  if (a->stride != 3 && a->stride != 4) return fail(s, PIES_ERR_INVALID, who() + "stride must be 3 or 4");
-  for (const void* q : p)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return fail(s, PIES_ERR_INVALID, who() + "an array pointer is not 4-byte aligned");
-  if (write && (p[3] || p[4]))
-    return fail(s, PIES_ERR_UNSUPPORTED, who() + "radius and inv_mass cannot be written on the device (pies_write_nodes is their path)");
-  return PIES_OK;
-}
+namespace pies {
 
 // `bytes` at p are device memory of the handle's device (p == nullptr: nothing to check)
 int check_device_range(pies_solver* s, const char* call, const void* p, size_t bytes) {
@@ -46,15 +33,6 @@ int check_device_range(pies_solver* s, const char* call, const void* p, size_t b
   const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(p);
   if (at < lo || at - lo > size || bytes > size - (at - lo))
     return fail(s, PIES_ERR_INVALID, std::string(call) + ": an array's allocation ends before the array does");
-  return PIES_OK;
-}
-
-int io_variant(pies_solver* s, const char* call, bool* staged) {
-  const char* e = tuning_env("PIES_NODE_IO_VARIANT");
-  *staged = false;  // the default: DESIGN.md section 8j
-  if (!e || std::strcmp(e, "plain") == 0) return PIES_OK;
-  if (std::strcmp(e, "staged") != 0) return fail(s, PIES_ERR_INVALID, std::string(call) + ": PIES_NODE_IO_VARIANT must be plain or staged");
-  *staged = true;
   return PIES_OK;
 }
 
@@ -78,6 +56,32 @@ int io_end(pies_solver* s, hipStream_t caller, uint32_t flags) {
   HIP_TRY(s, hipEventRecord(s->evIoOut, s->stream));
   HIP_TRY(s, hipStreamWaitEvent(caller, s->evIoOut, 0));
   if (flags & PIES_IO_HOST_SYNC) HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PIES_OK;
+}
+
+}  // namespace pies
+
+namespace {
+
+// the argument checks that need no device; PIES_OK or the entry point's answer
+int check_nodes(pies_solver* s, const char* call, const pies_device_nodes_t* a, bool write) {
+  const auto who = [&] { return std::string(call) + ": "; };
+  const void* p[5] = {a->position, a->prev_position, a->velocity, a->radius, a->inv_mass};
+  if (!p[0] && !p[1] && !p[2] && !p[3] && !p[4]) return fail(s, PIES_ERR_INVALID, who() + "every array pointer is NULL");
+  if (a->stride != 3 && a->stride != 4) return fail(s, PIES_ERR_INVALID, who() + "stride must be 3 or 4");
+  for (const void* q : p)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return fail(s, PIES_ERR_INVALID, who() + "an array pointer is not 4-byte aligned");
+  if (write && (p[3] || p[4]))
+    return fail(s, PIES_ERR_UNSUPPORTED, who() + "radius and inv_mass cannot be written on the device (pies_write_nodes is their path)");
+  return PIES_OK;
+}
+
+int io_variant(pies_solver* s, const char* call, bool* staged) {
+  const char* e = tuning_env("PIES_NODE_IO_VARIANT");
+  *staged = false;  // the default: DESIGN.md section 8j
+  if (!e || std::strcmp(e, "plain") == 0) return PIES_OK;
+  if (std::strcmp(e, "staged") != 0) return fail(s, PIES_ERR_INVALID, std::string(call) + ": PIES_NODE_IO_VARIANT must be plain or staged");
+  *staged = true;
   return PIES_OK;
 }
 

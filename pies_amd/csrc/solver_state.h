@@ -22,6 +22,7 @@
 #include "measure_kernels.h"
 #include "anchor_kernels.h"
 #include "tie_kernels.h"
+#include "actuator_kernels.h"
 
 namespace pies {
 
@@ -234,6 +235,16 @@ struct TieSetDevice {  // nullptr: not staged
   TieEntry* entries = nullptr;
 };
 
+// A set of actuators (pies_add_actuators, actuators.cpp): the host copy pies_get_actuators reads - `base` filled in -, and what the
+// device copy is staged from: the records with every host index replaced by its slot in the plan the device holds (built at the
+// staging, alive until the next one: the copy is asynchronous).
+struct HostActuatorSet {
+  std::vector<pies_actuator_t> actuators;  // the set's own order
+  uint32_t nChannels = 0;
+  uint32_t restBits = 0;                   // bit 0: some actuator drives a distance constraint, bit 1: a bend constraint
+  std::vector<ActuatorRecord> staged;
+};
+
 // Device buffers of pies_raycast.  free_device drops them, so the triangle list never outlives the scene or the node numbering
 // it was built from; every buffer grows on demand and a handle that never casts a ray holds none.
 struct RayBuffers {
@@ -303,6 +314,17 @@ struct RayBuffers {
   float4* tieTorque = nullptr;
   float4* tieScratch = nullptr;                 // 2 per tie
   size_t tieCap = 0;                            // ties all four hold
+  // pies_drive_actuators (actuators.cpp) has its buffers to itself: the device copies of its sets (nullptr: not staged - the slots
+  // are those of the plan this scene was built with), the activations and the folded outputs of a host-pointer call, one entry per
+  // actuator and the tile records
+  ActuatorRecord* actuatorSets[PIES_ACTUATOR_SET_MAX] = {};
+  float* actuatorActivation = nullptr;          // PIES_ACTUATOR_CHANNEL_MAX words
+  float* actuatorSums = nullptr;                // PIES_ACTUATOR_CHANNEL_MAX x 2
+  uint32_t* actuatorLive = nullptr;             // PIES_ACTUATOR_CHANNEL_MAX
+  float2* actuatorOut = nullptr;                // per actuator: (rest, value)
+  size_t actuatorOutCap = 0;                    // actuators
+  uint32_t* actuatorTileRecords = nullptr;      // per (tile, channel): kActuatorTileWords words
+  size_t actuatorTileCap = 0;                   // (tile, channel) records
   // pies_measure_elements / pies_measure_nodes (measure.cpp) have their buffers to themselves.  Per container (0: PIES_TET, 1:
   // PIES_VOLUME) the elements staged in HOST order with node ids in DEVICE numbering, upload_tets' layout - the scene's own
   // tetrahedral records are in plan order and PBD stages no volume records
@@ -421,12 +443,16 @@ struct pies_solver {
   std::vector<pies::HostField> h_fields;  // extension: signed distance fields (pies_add_field*); assets: only pies_clear drops them
   std::vector<pies::HostAnchorSet> h_anchors;  // extension: anchor sets (pies_add_anchors); assets like the fields
   std::vector<pies::HostTieSet> h_ties;        // extension: tie sets (pies_add_ties); assets like the anchor sets
+  std::vector<pies::HostActuatorSet> h_actuators;  // extension: actuator sets (pies_add_actuators); assets like the anchor sets
   uint32_t constraintId = 0;
 
   bool sceneDirty = true;    // topology/rest data changed: rebuild plans + upload everything
   // which host mirror arrays are older than the device's (bit 0 positions, 1 previous positions, 2 velocities):
   // a read of one array copies that array only, through the pinned staging buffer
   uint32_t stale = 0;
+  // which rest data of the host mirror is older than the device's (bit 0: h_distance[].target, bit 1: h_bend[].angle) - a
+  // pies_drive_actuators wrote HBM; download_rest copies the records back through the plan's order before anyone reads them
+  uint32_t restStale = 0;
   bool graphDirty = false;   // only the launch sequence changed (releaseHinge, CG budget): re-capture, no re-upload
   bool hostNodesDirty = false;  // host node state edited (pies_write_nodes): upload nodes only
 

@@ -152,6 +152,33 @@ class Tensors:
     def set_velocities(self, t, ids=None):
         self._write("velocity", t, ids)
 
+    # -- actuators -------------------------------------------------------------------------------
+    def _words(self, t, shape, dtypes, name):
+        if t is None:
+            return 0
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype not in dtypes or tuple(t.shape) != tuple(shape) \
+                or not t.is_contiguous() or t.requires_grad:
+            raise capi.PiesError("%s must be a contiguous %s tensor of shape %s on %s that does not require grad"
+                                 % (name, " or ".join(str(d) for d in dtypes), tuple(shape), self.device))
+        return t.data_ptr()
+
+    def drive_actuators(self, actuator_set, activation, sums=None, live=None, per_actuator=None):
+        """pies_drive_actuators_device: the set's rest lengths and angles written from `activation`, a float32 tensor with one
+        entry per channel of the set - the output of a policy, say - without the host in the loop.  The optional outputs are
+        tensors the library fills: sums float32 (c, 2), live int32 or uint32 (c), per_actuator float32 (n, 2).  A non-finite
+        activation leaves its actuators' constraints as they are (the call cannot check the tensor)."""
+        if not isinstance(activation, torch.Tensor) or activation.device != self.device or activation.dim() != 1:
+            raise capi.PiesError("activation must be a 1-d tensor on %s" % (self.device,))
+        u = activation.detach().to(torch.float32).contiguous()
+        c = u.shape[0]
+        n = len(self.solver.get_actuators(actuator_set)[0]) if per_actuator is not None else 0
+        self.solver.drive_actuators_device(actuator_set, c, u.data_ptr(),
+                                           sums=self._words(sums, (c, 2), (torch.float32,), "sums"),
+                                           live=self._words(live, (c,), (torch.int32, torch.uint32), "live"),
+                                           per_actuator=self._words(per_actuator, (n, 2), (torch.float32,), "per_actuator"),
+                                           stream=self._stream())
+        # (u stays alive until the launch is queued; the caching allocator keeps its memory for the stream's later work)
+
     # -- skins -----------------------------------------------------------------------------------
     def skin(self, k, normals=True):
         """(positions, normals) of skin k as (n, 3) tensors, or the positions alone with normals=False"""
