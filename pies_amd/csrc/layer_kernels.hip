@@ -48,6 +48,30 @@ constexpr int kStampsPerTile = 128;
 #define PIES_STAMP_REAL()
 #endif
 
+// Round 15: the colour loops' gathers of node records stay ONE 16-byte read each.  The tetrahedral and the distance projection never
+// touch .w, and the compiler narrows a float4 read whose .w is dead to ds_read_b96 - which the LDS serves in 8 lane groups of 8
+// where ds_read_b128 takes 4 of 16: twice the LDS cycles for a quarter fewer bytes.  An empty statement that names
+// the .w of the records read keeps them whole; it emits no instruction, and where it stands nothing is waited for that the
+// wavefront has not waited for already.  -DPIES_LAYER_NARROW_READS (A/B builds only) leaves the reads to the compiler.
+PIES_DEV void keep_w(const float4& a, const float4& b) {
+#ifndef PIES_LAYER_NARROW_READS
+  asm volatile("" ::"v"(a.w), "v"(b.w));
+#endif
+}
+PIES_DEV void keep_w(const float4& a, const float4& b, const float4& c, const float4& d) {
+#ifndef PIES_LAYER_NARROW_READS
+  asm volatile("" ::"v"(a.w), "v"(b.w), "v"(c.w), "v"(d.w));
+#endif
+}
+
+// ... and the scatters stay the 12-byte stores they were while .w was dead (ds_write_b96: 10 cycles of operand transfer against 13)
+// (WIDE = false, the 128-register instantiations: the record as written, which the compiler narrows itself - their code is untouched)
+template <bool WIDE = true>
+PIES_DEV void put_xyz(float4* __restrict__ slot, const float4& v) {
+  if (WIDE) { slot->x = v.x; slot->y = v.y; slot->z = v.z; }
+  else *slot = v;
+}
+
 PIES_DEV uint32_t lo16(uint32_t v) { return v & 0xFFFFu; }
 PIES_DEV uint32_t hi16(uint32_t v) { return v >> 16; }
 
@@ -66,6 +90,8 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
   static_assert(FORM == 0 || TETV == 0, "the row-pair form is the full projection");
   static_assert(3 * kLayerRestMaxSets <= BLOCK, "the prologue requests the rest dictionary with one load per lane");
   constexpr int kDistPreload = (WPE > 1 || BLOCK > 512) ? 6 : kDistPreloadMax;
+  // (the 128-register instantiations keep the reads the compiler chooses: the four words cost them 12 more bytes of scratch)
+  constexpr bool kWideReads = !(WPE > 1 || BLOCK > 512);
   constexpr int kDistAhead = 3;  // colours of a distance segment whose records are in flight
   extern __shared__ float4 lds[];
   float4* __restrict__ sp = lds;                                                  // node records of the group
@@ -261,7 +287,8 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
 #ifdef PIES_EXPERIMENTS
           if (stampBase) { asm volatile("" : "+v"(x1.x), "+v"(x2.x), "+v"(x3.x), "+v"(x4.x)); PIES_STAMP(); }  // the projection is done
 #endif
-          sp[i1] = x1; sp[i2] = x2; sp[i3] = x3; sp[i4] = x4;
+          put_xyz(sp + i1, x1); put_xyz(sp + i2, x2); put_xyz(sp + i3, x3); put_xyz(sp + i4, x4);
+          keep_w(x1, x2, x3, x4);  // (behind the scatter: in front of the projection it would stand between the gather and the rest table's reads)
         }
         for (uint32_t t = lo + tid + BLOCK; t < hi; t += BLOCK) {  // classes larger than the workgroup
           PIES_RARE_PATH();
@@ -273,7 +300,8 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
           if (!DICT) { q0 = D.tc_q0[t]; q1 = D.tc_q1[t]; q2 = D.tc_q2[t]; }
           float4 x1 = sp[j1], x2 = sp[j2], x3 = sp[j3], x4 = sp[j4];
           project(jd, x1, x2, x3, x4, q0, q1, q2);
-          sp[j1] = x1; sp[j2] = x2; sp[j3] = x3; sp[j4] = x4;
+          put_xyz(sp + j1, x1); put_xyz(sp + j2, x2); put_xyz(sp + j3, x3); put_xyz(sp + j4, x4);
+          keep_w(x1, x2, x3, x4);
         }
         lds_barrier();
         PIES_STAMP();
@@ -309,14 +337,18 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
           }
           if (off[c] + tid < off[c + 1] && PIES_IN_BOUNDS(max(lo16(id[c]), hi16(id[c])) < m, 12u)) {
             float4 a = sp[lo16(id[c])];
-            distance_core<DIST != 0>(a, sp[hi16(id[c])], rw[c]);
-            sp[lo16(id[c])] = a;
+            const float4 b = sp[hi16(id[c])];
+            if (kWideReads) keep_w(a, b);
+            distance_core<DIST != 0>(a, b, rw[c]);
+            put_xyz<kWideReads>(sp + lo16(id[c]), a);
           }
           for (uint32_t t = off[c] + tid + BLOCK; t < off[c + 1]; t += BLOCK) {  // classes larger than the workgroup
             const uint32_t jd = D.dc_lid[t];
             float4 a = sp[lo16(jd)];
-            distance_core<DIST != 0>(a, sp[hi16(jd)], D.dc_rw[t]);
-            sp[lo16(jd)] = a;
+            const float4 b = sp[hi16(jd)];
+            if (kWideReads) keep_w(a, b);
+            distance_core<DIST != 0>(a, b, D.dc_rw[t]);
+            put_xyz<kWideReads>(sp + lo16(jd), a);
           }
           lds_barrier();
           PIES_STAMP();
@@ -326,8 +358,10 @@ __global__ void __launch_bounds__(BLOCK, WPE) k_layer(NodeArrays nd, LayerData D
         for (uint32_t t = off[c] + tid; t < off[c + 1]; t += BLOCK) {
           const uint32_t jd = D.dc_lid[t];
           float4 a = sp[lo16(jd)];
-          distance_core<DIST != 0>(a, sp[hi16(jd)], D.dc_rw[t]);
-          sp[lo16(jd)] = a;
+          const float4 b = sp[hi16(jd)];
+          if (kWideReads) keep_w(a, b);
+          distance_core<DIST != 0>(a, b, D.dc_rw[t]);
+          put_xyz<kWideReads>(sp + lo16(jd), a);
         }
         lds_barrier();
       }

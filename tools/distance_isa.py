@@ -5,11 +5,18 @@ lane loads two node records and a (rest, w) pair, projects, stores.  Two kernels
 behind its per-lane range test (distance_core<true>).  For the second the path with every lane in range is counted as well: the
 region with the fallback's division (v_div_scale), which a branch on the empty execution mask jumps over, left out.  Cross-compilation only: runs without a GPU.
 
-usage: python tools/distance_isa.py > profiles/rNN_distance_isa.txt"""
+Then the LDS instructions of a distance colour as k_layer's product build emits them, by width: the stretches between two workgroup
+barriers of k_layer<512, 0, 1, true, 1, 1> that gather at most four and scatter at most two node records (tools/layer_isa.py
+cuts the kernel; a colour has a path for its first 512 members and a loop for the rest).
+
+usage: python tools/distance_isa.py [extra compiler flags for k_layer] > profiles/rNN_distance_isa.txt"""
 import os
 import re
 import subprocess
+import sys
 import tempfile
+
+import layer_isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = """#include "pbd_project.h"
@@ -81,6 +88,16 @@ def main():
             res[0] = tally(every)
     print("off the common path: %d instructions, of them VALU %d, s_nop %d; scalar %+d" %
           (res[0]["all"] - res[1]["all"], res[0]["valu"] - res[1]["valu"], res[0]["s_nop"] - res[1]["s_nop"], res[1]["salu"] - res[0]["salu"]))
+    with tempfile.TemporaryDirectory() as tmp:
+        txt = layer_isa.compile_isa(tmp, "layer.s", sys.argv[1:])
+    lines = layer_isa.kernel_text(txt, "_ZN4pies7k_layerILi512ELi0ELi1ELb1ELi1ELi1EEE")[0]
+    print("LDS instructions of a distance colour in k_layer<512, 0, 1, true, 1, 1> (product build, between two workgroup barriers):")
+    for key, n in sorted(layer_isa.barrier_segments(lines).items(), key=lambda kv: -kv[1]):
+        wide = dict(kv.rsplit(" ", 1) for kv in key.split(", "))
+        reads = sum(int(v) for k, v in wide.items() if k in ("ds_read_b96", "ds_read_b128"))
+        writes = sum(int(v) for k, v in wide.items() if k in ("ds_write_b96", "ds_write_b128"))
+        if 0 < reads <= 4 and 0 < writes <= 2:
+            print("  %3d x  %s" % (n, key))
 
 
 if __name__ == "__main__":

@@ -7,7 +7,10 @@ scatter and the barrier.
 The main loop's gather and the rare paths (the start of an element with fewer than two pairs out of tolerance, the rotating sweeps, the completion
 of a collapsed direction, the loop for classes larger than the workgroup) are told from the common one by a comment the
 sources emit under -DPIES_PATH_NOTES (dev_math.h: PIES_MAIN_TET_PATH, PIES_RARE_PATH); the tool compiles once with and once without it and reports
-both kernels' lengths, so that a difference made by the notes shows.  --dump writes the instructions along the path of the
+both kernels' lengths, so that a difference made by the notes shows.  LDS instructions are reported by width: along the main loop's
+product build only (the notes change which widths the compiler picks, so the path walk says nothing about them): over the whole
+kernel and per stretch between two workgroup barriers - a colour step; the distance colours are the stretches with two gathers
+and one scatter per path, the bend step the one with four 16-byte gathers and four 16-byte scatters.  --dump writes the instructions along the path of the
 tet_rows.h kernel, block by block: where the moves of a source region stand.
 
 usage: python tools/layer_isa.py [--block 512] [--streamed] [--json profiles/rNN_layer_critical_path.json] [--dump path.s] [extra compiler flags]
@@ -89,6 +92,36 @@ def counts(b):
             "waits": sum(o.startswith("s_waitcnt") for o in ops),
             "scalar": sum(o.startswith("s_") and not o.startswith("s_waitcnt") for o in ops),
             "memory": sum(o.startswith(MEMORY) for o in ops)}
+
+
+def lds_widths(ops):
+    """LDS instructions by mnemonic (the width is part of it): 'ds_read_b128 4, ds_write_b96 4'"""
+    tally = {}
+    for o in ops:
+        if o.startswith("ds_"):
+            tally[o] = tally.get(o, 0) + 1
+    return ", ".join("%s %d" % kv for kv in sorted(tally.items())) or "none"
+
+
+def barrier_segments(lines):
+    """the product build's kernel cut at its workgroup barriers, in the order of the text: a colour step is what stands between
+    two barriers.  Returns {LDS instructions of a segment, by width: number of such segments} for the segments that gather or
+    scatter node records (12 or 16 bytes wide): the tetrahedral steps (four gathers, four scatters, with the dictionary the rest
+    table's rows), the distance colours (two gathers, one scatter), the prologue and the per-node steps."""
+    found, ops = {}, []
+    for raw in list(lines) + ["s_barrier"]:
+        t = raw.strip()
+        if not t or t.startswith((";", ".")):
+            continue
+        op = t.split()[0]
+        if op == "s_barrier":
+            if any(o.endswith(("_b96", "_b128")) for o in ops if o.startswith("ds_")):
+                key = lds_widths(ops)
+                found[key] = found.get(key, 0) + 1
+            ops = []
+        else:
+            ops.append(op)
+    return found
 
 
 def main_loop_path(blocks):
@@ -203,6 +236,12 @@ def main():
         n_plain = len(kernel_text(plain, sym)[0])
         vg, sc = kernel_text(plain, sym)[1][:2]
         print("  (the product build of this kernel, without the notes: %d lines of ISA against %d with them; %s VGPRs, scratch %s)\n" % (n_plain, n_noted, vg, sc))
+        lines = kernel_text(plain, sym)[0]
+        print("  LDS instructions of the product build of this kernel: " + lds_widths(t.split()[0] for t in map(str.strip, lines) if t))
+        print("  between two workgroup barriers of it (segments that gather or scatter node records; a distance colour: two gathers, one scatter):")
+        for key, n in sorted(barrier_segments(lines).items(), key=lambda kv: -kv[1]):
+            print("    %3d x  %s" % (n, key))
+        print()
         out[form] = total
     print("registers of every instantiation (product flags):")
     for m in re.finditer(r"^(_ZN4pies7k_layerI\S+):.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", plain, re.S | re.M):
